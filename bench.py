@@ -2,6 +2,7 @@
 """bench.py -- headline benchmark: ADI steps/s and HBM GB/s, 512^3 fp64 Cartesian Robin, 1..8 MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 512] [--scaling weak|strong] [--mask box|ellipsoid] [--no-cpu]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -70,7 +71,15 @@ def parse(argv=None):
                     help='N = 1: skip the `also` object (the other BASELINE.json configs, 20 steps each, after the timed region)')
     ap.add_argument('--pg-timeout', type=float, default=120.0,
                     help='seconds a collective of the process group may wait before the rank aborts with a stack trace')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the field the last timed step returned as DIR/<name>.npy (fp64, at most '
+                         '64e6 bytes on disk in all: the whole field when it fits, else a fixed seeded sample of distinct cells '
+                         'and its middle plane; with N > 1 ranks each writes its slab as T_rank<r>*.npy in its 1/N share); the '
+                         'line lists every file in `dumped_outputs`.  Two builds can be compared output for output')
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    return a
 
 
 # ---- plain `python bench.py --gpus N`: this process starts the ranks -------------------------------------------------
@@ -346,6 +355,54 @@ def timed_steps(step_fn, nstages, steps=20, warmup=5, every=1):
     return e0.elapsed_time(e1) / steps, st.mean(axis=0)
 
 
+DUMP_BUDGET = 64 * 10 ** 6     # bytes on disk, .npy headers included: every file one --dump-outputs run writes, all ranks together
+DUMP_SAMPLE = 2 ** 21          # cells in the seeded sample of a field that does not fit
+DUMP_SEED = 20240601
+NPY_HEADER_MAX = 256           # bytes reserved per file for its .npy header (np.save writes 128 for these 1-D to 3-D arrays)
+
+
+def dump_sample_cells(numel, k):
+    """the k distinct flat C-order indices, drawn without replacement with DUMP_SEED and sorted, that a sampled dump holds"""
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(numel, k, replace=False))
+
+
+def dump_field(dirpath, name, t, budget):
+    """--dump-outputs: the (nx, ny, nz) fp64 field `t` (any strides) as DIR/<name>.npy when that file fits in `budget` bytes;
+    otherwise DIR/<name>_mid_plane.npy, the whole plane nx // 2 (when it takes at most a quarter of the budget), and
+    DIR/<name>_sample.npy, the values at dump_sample_cells(nx * ny * nz, k) -- the same cells for the same shape and budget on
+    every run -- with k = DUMP_SAMPLE or as many as the rest of the budget holds.  The files together stay within `budget`
+    bytes on disk.  Runs after the timed region.  Returns the names of the files written."""
+    os.makedirs(dirpath, exist_ok=True)
+    nx, ny, nz = (int(v) for v in t.shape)
+    if t.numel() * 8 + NPY_HEADER_MAX <= budget:
+        files = {name: t.contiguous().cpu().numpy()}
+    else:
+        files = {}
+        if ny * nz * 8 + NPY_HEADER_MAX <= budget // 4:
+            files[name + '_mid_plane'] = t[nx // 2].contiguous().cpu().numpy()
+        left = budget - sum(f.nbytes + NPY_HEADER_MAX for f in files.values()) - NPY_HEADER_MAX
+        flat = dump_sample_cells(t.numel(), min(DUMP_SAMPLE, left // 8))
+        idx = [torch.from_numpy(np.ascontiguousarray(v)).to(t.device) for v in np.unravel_index(flat, (nx, ny, nz))]
+        files[name + '_sample'] = t[idx[0], idx[1], idx[2]].cpu().numpy()
+    paths = [os.path.join(dirpath, nm + '.npy') for nm in files]
+    for p, arr in zip(paths, files.values()):
+        np.save(p, np.ascontiguousarray(arr, dtype=np.float64))
+    written = sum(os.path.getsize(p) for p in paths)
+    assert written <= budget, (written, budget)
+    return sorted(nm + '.npy' for nm in files)
+
+
+def dump_outputs(dirpath, T, world, rank, dist):
+    """dump_field of this rank's field (T, or T_rank<r> when several ranks run) within its share of DUMP_BUDGET; with several
+    ranks every rank learns the names all of them wrote (collective).  Returns the sorted names of every file of the run."""
+    names = dump_field(dirpath, 'T' if world == 1 else 'T_rank%d' % rank, T, DUMP_BUDGET // world)
+    if world > 1:
+        per_rank = [None] * world
+        dist.all_gather_object(per_rank, names)
+        names = [nm for r in per_rank for nm in r]
+    return sorted(names)
+
+
 def _kernel_table(names, bpc, ms, cells):
     out = {}
     for nm, b, m in zip(names, bpc, ms):
@@ -477,6 +534,7 @@ def main_cyl(a):
     T = cyl.DeviceField(X)
     elapsed = col.max(time.perf_counter() - t0)
     assert bool(torch.isfinite(T.t).all().item())
+    dumped = dump_outputs(a.dump_outputs, T.t, world, rank, dist) if a.dump_outputs else None
     if rank != 0:
         dist.destroy_process_group()
         return
@@ -504,6 +562,8 @@ def main_cyl(a):
                 roofline=dict(bound='hbm', kernel=dom, achieved=kernels[dom]['achieved_gbs'], peak=HBM_PEAK_GBS,
                               unit='GB/s', frac=kernels[dom]['frac'], traffic=measured_traffic(dom, 'cyl')),
                 kernels=kernels)
+    if dumped is not None:
+        line['dumped_outputs'] = dumped
     if not a.no_cpu:
         # the NumPy restatement of adi3d_cyl_phi_v3.adi_step (BE) on a bounded sample of the same workload
         from oracle import cyl_oracle as orc
@@ -697,6 +757,8 @@ def main(argv=None):
     gc.enable()
     elapsed = col.max(t1 - t0)
     assert bool(torch.isfinite(T.t).all().item())
+    # this rank's slab (the whole field on one GPU) as the last timed step returned it
+    dumped = dump_outputs(a.dump_outputs, T.t, world, rank, dist) if a.dump_outputs else None
 
     stage_ms = np.array([[ev[s][i].elapsed_time(ev[s][i + 1]) for i in range(nst)] for s in range(a.steps)])
     mean_ms = stage_ms.mean(axis=0)
@@ -772,6 +834,8 @@ def main(argv=None):
         **({'ranks': ranks_info} if ranks_info is not None else {}),
         **({'parity_vs_one_domain': parity_1d} if parity_1d is not None else {}),
     )
+    if dumped is not None:
+        line['dumped_outputs'] = dumped
     if xs is not None:
         line['general_pack_sweeps_42B'] = xs
         line['prewarm'] = ('the 42 B/cell sweep measurements (3 x 13 launches, about 45 ms of GPU work) run before the warm-up steps: '

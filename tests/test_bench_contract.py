@@ -8,6 +8,8 @@ import sys
 
 import pytest
 
+import bench
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ['metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
@@ -100,6 +102,61 @@ def test_single_rank_rccl_line_runs_the_parity_calls_over_nccl():
     p = d['parity_vs_one_domain']
     assert p['ok'] is True and p['rel_linf'] <= 1e-12 and p['planes_per_rank'] == [128]
     assert d['ranks']['backend'] == 'nccl' and d['ranks']['world_size_from_process_group'] == 1
+
+
+def test_dump_outputs_is_the_field_of_the_last_timed_step(tmp_path):
+    """--dump-outputs: at 64^3 the whole field fits the budget, so T.npy is the field after warmup + steps steps from the seeded T0,
+    checked against the single-thread oracle taking the same steps; the 128 MB cylindrical field goes out as a seeded sample plus
+    its middle plane, all files fp64 and within the cap together"""
+    import numpy as np
+    d = _bench('--n', '64', '--steps', '3', '--warmup', '2', '--no-cpu', '--no-also', '--dump-outputs', str(tmp_path / 'cart'))
+    assert d['steps'] == 3 and d['dumped_outputs'] == ['T.npy']
+    got = np.load(str(tmp_path / 'cart' / 'T.npy'))
+    assert got.dtype == np.float64 and got.shape == (64, 64, 64)
+    sys.path.insert(0, ROOT)
+    from oracle import adi_oracle as orc
+    grid = orc.Grid3D(64, 64, 64, 5e-4, np.ones((64, 64, 64), bool))
+    mat = orc.Material(7800.0, 490.0, 54.0)
+    prm = orc.Params(200.0 * grid.dx ** 2 / (mat.k / (mat.rho * mat.cp)), 0.5)
+    packs = orc.precompute_coeff_packs_unified(grid, mat, robin_h=500.0)
+    T0 = np.random.default_rng(1).uniform(20.0, 1000.0, (64, 64, 64))
+    want = orc.adi_run(T0, grid, mat, prm, packs, Tinf=20.0, nsteps=5)
+    assert np.abs(got - want).max() <= 1e-10 * np.abs(want).max()
+
+    d = _bench('--config', 'cyl', '--steps', '2', '--warmup', '1', '--no-cpu', '--dump-outputs', str(tmp_path / 'cyl'))
+    assert d['dumped_outputs'] == ['T_mid_plane.npy', 'T_sample.npy']
+    files = [str(tmp_path / 'cyl' / f) for f in d['dumped_outputs']]
+    assert sum(os.path.getsize(f) for f in files) <= bench.DUMP_BUDGET
+    plane, sample = (np.load(f) for f in files)
+    assert plane.dtype == sample.dtype == np.float64 and plane.shape == (256, 512) and sample.size == bench.DUMP_SAMPLE
+    assert np.isfinite(sample).all() and 19.999 <= sample.min() and sample.max() <= 1000.001     # BE from T0 in [20, 1000]
+    # the sampled cells are the ones dump_sample_cells names: those in plane nr // 2 equal the dumped middle plane
+    i, j, k = np.unravel_index(bench.dump_sample_cells(128 * 256 * 512, sample.size), (128, 256, 512))
+    mid = i == 64
+    assert mid.sum() > 1000 and np.array_equal(sample[mid], plane[j[mid], k[mid]])
+    T0 = np.full((128, 256, 512), 20.0); T0[:, :, -16:] = 1000.0
+    assert np.any(sample != T0[i, j, k])                                                       # stepped, not the initial field
+
+
+def test_dump_outputs_of_two_ranks_are_all_listed(tmp_path):
+    """--gpus 2 (two real processes on the one GPU, gloo-staged test transport): each rank writes its own files in its half of the
+    budget and the line lists the files of both ranks -- whole slabs (128^3 each) and sampled cylindrical replicas, which, started
+    from the same field, are identical"""
+    import numpy as np
+    d = _bench('--gpus', '2', '--n', '128', '--steps', '2', '--warmup', '1', '--no-cpu', '--transport', 'gloo-staged',
+               '--dump-outputs', str(tmp_path / 'cart'))
+    assert d['dumped_outputs'] == ['T_rank0.npy', 'T_rank1.npy'] == sorted(os.listdir(str(tmp_path / 'cart')))
+    for f in d['dumped_outputs']:
+        a = np.load(str(tmp_path / 'cart' / f))
+        assert a.dtype == np.float64 and a.shape == (128, 128, 128) and np.isfinite(a).all()
+    d = _bench('--config', 'cyl', '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-cpu', '--transport', 'gloo-staged',
+               '--dump-outputs', str(tmp_path / 'cyl'))
+    names = ['T_rank%d_%s.npy' % (r, w) for r in (0, 1) for w in ('mid_plane', 'sample')]
+    assert d['dumped_outputs'] == names == sorted(os.listdir(str(tmp_path / 'cyl')))
+    assert sum(os.path.getsize(str(tmp_path / 'cyl' / f)) for f in names) <= bench.DUMP_BUDGET
+    for w in ('mid_plane', 'sample'):
+        assert np.array_equal(np.load(str(tmp_path / 'cyl' / ('T_rank0_%s.npy' % w))),
+                              np.load(str(tmp_path / 'cyl' / ('T_rank1_%s.npy' % w))))
 
 
 def test_cylindrical_replicas_line():
