@@ -120,6 +120,15 @@ SIGNATURES = {
     'adi_cyl_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_double, c_double, c_void_p]),
     'adi_cyl_sweep': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p]),
+    'adi_source_sample': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_void_p, c_void_p]),
+    'adi_source_set': (c_int, [c_void_p, c_void_p, c_double, c_double, ctypes.c_longlong, c_void_p]),
+    'adi_source_tick': (c_int, [c_void_p, c_void_p]),
+    'adi_source_lines0': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long,
+                                  c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double_p, c_void_p,
+                                  c_size_t, c_void_p]),
+    'adi_source_workspace_bytes': (c_int, [c_void_p, c_int, c_int, c_int, c_double, ctypes.POINTER(c_size_t)]),
+    'adi_explicit_rhs_src': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double,
+                                     c_double, c_double, c_double, c_void_p, c_void_p]),
     'adi_ctx_create': (c_int, [c_int, c_int, c_int, c_double, c_int, c_void_pp]),
     'adi_ctx_destroy': (c_int, [c_void_p]),
     'adi_ctx_set_mask': (c_int, [c_void_p, c_void_p]),
@@ -131,6 +140,17 @@ SIGNATURES = {
     'adi_ctx_step': (c_int, [c_void_p, c_double, c_double, c_double, c_double, c_double, c_double, c_int]),
     'adi_ctx_last_step_ms': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_float)]),
 }
+
+SOURCE_BLOCK_BYTES = 128     # ADI_SOURCE_BLOCK_BYTES
+SOURCE_E_CUT = 40.0          # ADI_SOURCE_E_CUT
+
+
+class HeatSource(ctypes.Structure):
+    """adi_heat_source (include/adi_hip.h)"""
+    _fields_ = [('power', c_double), ('eta', c_double), ('a', c_double), ('b', c_double), ('c_f', c_double),
+                ('c_r', c_double), ('f_f', c_double), ('origin', c_double * 3), ('velocity', c_double),
+                ('travel_axis', c_int), ('travel_sign', c_int), ('depth_axis', c_int), ('reserved', c_int)]
+
 
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)   # AttributeError here = the .so does not export what the header declares

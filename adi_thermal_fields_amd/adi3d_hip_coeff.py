@@ -38,7 +38,8 @@ from ._lib import lib, check, ptr_array, FACES
 __all__ = ['Grid3D', 'Material', 'Params', 'AxisCoeffPack', 'exposed_mask', 'precompute_coeff_packs_unified',
            'adi_step_hip_coeff', 'adi_step_numba_coeff', 'adi_step_gpu_coeff', 'DeviceField', 'to_device',
            'adi_explicit_rhs', 'adi_sweep_axis', 'StagedStepper', 'Layout', 'apply_surface_impulse_Q',
-           'exposed_faces_per_layer', 'count_exposed_faces', 'perimeter_ratio', 'birth_planes', 'BirthPacks']
+           'exposed_faces_per_layer', 'count_exposed_faces', 'perimeter_ratio', 'birth_planes', 'BirthPacks',
+           'GoldakSource']
 
 
 # Mask versions come from ONE process-wide counter: a pack remembers the version of the mask it was built for, and a
@@ -743,24 +744,193 @@ def _ensure_general(pack):
         pack.d_qflux = L.empty(zero=True)
 
 
-def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0):
+def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0):
     """adi3d_numba_coeff.py:290-302 / adi3d_gpu_coeff.py:213-230: explicit stage, then the three
     implicit sweeps in the order axis 0, 1, 2.  Returns a NEW array of the kind it was given;
-    `Tn` is never modified."""
-    t, kind = _as_state(Tn, grid)
+    `Tn` is never modified.
+
+    S: volumetric heat source in W/m^3 (include/adi_hip.h, "Volumetric heat source"): R0 gains dt*q/(rho cp) on in-mask
+    cells, q evaluated at the step's mid-time.  None: the step of the reference, the same launches as without the keyword.
+    An array of the grid's shape (NumPy / torch / DeviceField): the field form -- explicit stage with the source
+    (adi_explicit_rhs_src), then the three unfused sweeps.  A GoldakSource: evaluated at t + dt/2 on the device and added
+    to the output of sweep 0 by superposition (adi_source_lines0), after whichever sweep-0 form the step uses.
+    t: the step's start time, used only by a source object."""
+    if S is not None and not isinstance(S, GoldakSource):
+        return _step_field_source(Tn, grid, mat, params, packs, Tinf, S)
+    t_in, kind = _as_state(Tn, grid)
     packx, packy, packz = packs
     (ta, tb), _, _ = grid.scratch(2)
     kappa, _ = _gam(grid, mat, params)
     out = grid.layout.empty()
     if fused_supported(grid):
-        _explicit_sweep0_into(t, tb, grid, mat, params, packx, Tinf)
+        _explicit_sweep0_into(t_in, tb, grid, mat, params, packx, Tinf)
     else:
-        check(lib.adi_explicit_rhs(_p(t), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt,
+        check(lib.adi_explicit_rhs(_p(t_in), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt,
                                    kappa, params.theta, _p(ta), _stream()))
         _sweep_into(0, ta, tb, grid, mat, params, packx, Tinf)
+    if S is not None:
+        S.set_block(_source_block(grid), t, params.dt)
+        _source_lines0_into(tb, grid, mat, params, packx, S, grid)
     _sweep_into(1, tb, ta, grid, mat, params, packy, Tinf)
     _sweep_into(2, ta, out, grid, mat, params, packz, Tinf)
     return _wrap(out, kind)
+
+
+def _explicit_src_into(t, d_S, out, grid, mat, params):
+    kappa, _ = _gam(grid, mat, params)
+    check(lib.adi_explicit_rhs_src(_p(t), _p(d_S), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt, kappa,
+                                   params.theta, mat.rho, mat.cp, _p(out), _stream()))
+
+
+def _step_field_source(Tn, grid, mat, params, packs, Tinf, S):
+    """the step with a source FIELD: R0 with the source, then the three unfused sweeps"""
+    t, kind = _as_state(Tn, grid)
+    if tuple(S.shape) != grid.shape:
+        raise ValueError("S has shape %s, the grid %s" % (tuple(S.shape), grid.shape))
+    d_S = grid.layout.to_layout(S, torch.float64)
+    (ta, tb), _, _ = grid.scratch(2)
+    out = grid.layout.empty()
+    _explicit_src_into(t, d_S, ta, grid, mat, params)
+    _sweep_into(0, ta, tb, grid, mat, params, packs[0], Tinf)
+    _sweep_into(1, tb, ta, grid, mat, params, packs[1], Tinf)
+    _sweep_into(2, ta, out, grid, mat, params, packs[2], Tinf)
+    return _wrap(out, kind)
+
+
+def _source_block(owner):
+    """the device parameter block of a moving source (ADI_SOURCE_BLOCK_BYTES), one per grid / stepper"""
+    blk = getattr(owner, '_src_block', None)
+    if blk is None or blk.device != _device():
+        blk = owner._src_block = torch.zeros(_lib.SOURCE_BLOCK_BYTES, dtype=torch.uint8, device=_device())
+    return blk
+
+
+def _source_work(owner, grid, src):
+    """workspace of adi_source_lines0 (lines longer than the in-register limit only; None otherwise), one per grid /
+    stepper, grown when a larger support needs more"""
+    b = ctypes.c_size_t(0)
+    check(lib.adi_source_workspace_bytes(ctypes.byref(src.as_c()), *grid.layout.pd[:3], grid.dx, ctypes.byref(b)))
+    if b.value == 0:
+        return None
+    w = getattr(owner, '_src_work', None)
+    if w is None or w.numel() < b.value or w.device != _device():
+        w = owner._src_work = torch.empty(b.value, dtype=torch.uint8, device=_device())
+    return w
+
+
+def _source_lines0_into(U, grid, mat, params, pack, src, owner):
+    """U += A0^-1 s on the axis-0 lines the support can meet (adi_source_lines0), in place; the block and the workspace
+    are `owner`'s"""
+    _, gam = _gam(grid, mat, params)
+    sp = _sparse_arg(grid, pack, False)
+    work = _source_work(owner, grid, src)
+    check(lib.adi_source_lines0(_p(_source_block(owner)), ctypes.byref(src.as_c()), _p(U), _p(grid.d_flags),
+                                _p(pack.d_coeff), _p(pack.d_dir_mask if pack.has_dir else None), *grid.layout.pd, sp,
+                                grid.dx, params.theta, gam, params.dt, mat.rho, mat.cp, _fc_arg(grid, pack, sp),
+                                _p(work), 0 if work is None else work.numel(), _stream()))
+
+
+class GoldakSource:
+    """Goldak's double-ellipsoid heat source (Goldak, Chakravarti & Bibby 1984), axis-aligned, for the `S=` argument of
+    adi_step_numba_coeff and the `source=` argument of StagedStepper.  power P [W], efficiency eta, a (transverse
+    half-width), b (depth), c_f / c_r (front / rear length) [m], front fraction f_f (f_r = 2 - f_f).  The centre at time t
+    is origin + travel_sign * velocity * t along travel_axis; depth_axis != travel_axis, the transverse axis is the third.
+        q = 6 sqrt(3) f eta P / (a b c pi^1.5) exp(-3 xi^2/c^2 - 3 y^2/a^2 - 3 z^2/b^2),  (f, c) = (f_f, c_f) ahead of
+        the centre (travel_sign*xi >= 0), (f_r, c_r) behind it; q = 0 where the exponent exceeds E_CUT = 40.
+    Over all space q integrates to 2 eta P, over the half-space on one side of the centre plane normal to depth_axis to
+    eta P: Goldak's normalisation for a centre on the surface.  The mask cuts the rest; nothing is renormalised.
+    power, eta, f_f, origin and velocity may change between the runs of a StagedStepper without a new graph."""
+    E_CUT = _lib.SOURCE_E_CUT
+
+    def __init__(self, power, eta, a, b, c_f, c_r, f_f=0.6, origin=(0.0, 0.0, 0.0), velocity=0.0, travel_axis=1,
+                 travel_sign=+1, depth_axis=2):
+        self.power, self.eta, self.a, self.b, self.c_f, self.c_r, self.f_f = power, eta, a, b, c_f, c_r, f_f
+        self.origin, self.velocity = origin, velocity
+        self.travel_axis, self.travel_sign, self.depth_axis = travel_axis, travel_sign, depth_axis
+        self.validate()
+
+    def validate(self):
+        """ValueError for any parameter adi_heat_source rejects (include/adi_hip.h)"""
+        try:
+            vals = [float(v) for v in (self.power, self.eta, self.a, self.b, self.c_f, self.c_r, self.f_f,
+                                       self.velocity)]
+            org = tuple(float(v) for v in self.origin)
+        except (TypeError, ValueError):
+            raise ValueError("GoldakSource: parameters must be real numbers, origin three of them")
+        if len(org) != 3:
+            raise ValueError("GoldakSource: origin must have three coordinates")
+        if not all(np.isfinite(v) for v in vals + list(org)):
+            raise ValueError("GoldakSource: non-finite parameter")
+        P, eta, a, b, cf, cr, ff, v = vals
+        if P < 0:
+            raise ValueError("GoldakSource: power < 0")
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError("GoldakSource: eta outside [0, 1]")
+        if min(a, b, cf, cr) <= 0:
+            raise ValueError("GoldakSource: lengths a, b, c_f, c_r must be > 0")
+        if not 0.0 < ff < 2.0:
+            raise ValueError("GoldakSource: f_f outside (0, 2)")
+        if v < 0:
+            raise ValueError("GoldakSource: velocity < 0 (the direction is travel_sign)")
+        for name in ('travel_axis', 'depth_axis'):
+            ax = getattr(self, name)
+            if isinstance(ax, bool) or not isinstance(ax, (int, np.integer)) or not 0 <= ax <= 2:
+                raise ValueError("GoldakSource: %s must be 0, 1 or 2" % name)
+        if self.travel_axis == self.depth_axis:
+            raise ValueError("GoldakSource: travel_axis == depth_axis")
+        if self.travel_sign not in (1, -1) or isinstance(self.travel_sign, bool):
+            raise ValueError("GoldakSource: travel_sign must be +1 or -1")
+        return vals, org
+
+    def as_c(self):
+        (P, eta, a, b, cf, cr, ff, v), org = self.validate()
+        return _lib.HeatSource(P, eta, a, b, cf, cr, ff, (ctypes.c_double * 3)(*org), v, int(self.travel_axis),
+                               int(self.travel_sign), int(self.depth_axis), 0)
+
+    def shape_key(self):
+        """what the launch box of the moving-source kernel depends on (a change recaptures a stepper's graph)"""
+        return (float(self.a), float(self.b), float(self.c_f), float(self.c_r), int(self.travel_axis),
+                int(self.travel_sign), int(self.depth_axis))
+
+    def center(self, t):
+        c = np.array([float(v) for v in self.origin], dtype=np.float64)
+        c[self.travel_axis] = c[self.travel_axis] + (float(self.travel_sign) * float(self.velocity)) * float(t)
+        return c
+
+    def q(self, x0, x1, x2, t):
+        """q [W/m^3] at points (broadcast NumPy arrays, metres) -- the host evaluator, same expression as the kernels'"""
+        (P, eta, a, b, cf, cr, ff, _), _ = self.validate()
+        c = self.center(t)
+        o = (np.asarray(x0, dtype=np.float64) - c[0], np.asarray(x1, dtype=np.float64) - c[1],
+             np.asarray(x2, dtype=np.float64) - c[2])
+        ta, da = self.travel_axis, self.depth_axis
+        xi, y, z = o[ta], o[3 - ta - da], o[da]
+        front = float(self.travel_sign) * xi >= 0.0
+        f = np.where(front, ff, 2.0 - ff)
+        cl = np.where(front, cf, cr)
+        E = (3.0 * (xi * xi) / (cl * cl) + 3.0 * (y * y) / (a * a)) + 3.0 * (z * z) / (b * b)
+        amp = (6.0 * np.sqrt(3.0) * f * eta * P) / (a * b * cl * np.pi ** 1.5)
+        with np.errstate(under='ignore'):
+            return np.where(E <= self.E_CUT, amp * np.exp(-np.minimum(E, 745.0)), 0.0)
+
+    def sample(self, grid, t):
+        """q at the cell centres ((i+1/2)dx, (j+1/2)dx, (k+1/2)dx) at time t: float64 array of the grid's shape, 0 off the
+        mask (NumPy: the ground truth the tests hold the kernels to)"""
+        dx = float(grid.dx)
+        x = [(np.arange(n, dtype=np.float64) + 0.5) * dx for n in (grid.nx, grid.ny, grid.nz)]
+        q = self.q(x[0][:, None, None], x[1][None, :, None], x[2][None, None, :], t)
+        q = np.broadcast_to(q, (grid.nx, grid.ny, grid.nz))
+        return np.where(np.asarray(grid.mask, dtype=bool), q, 0.0)
+
+    def sample_device(self, grid, t):
+        """the same on the device (adi_source_sample): a DeviceField"""
+        out = grid.layout.empty()
+        check(lib.adi_source_sample(ctypes.byref(self.as_c()), _p(grid.d_flags), *grid.layout.pd, grid.dx, float(t),
+                                    _p(out), _stream()))
+        return DeviceField(out)
+
+    def set_block(self, blk, t0, dt, n=0):
+        check(lib.adi_source_set(_p(blk), ctypes.byref(self.as_c()), float(t0), float(dt), int(n), _stream()))
 
 
 def apply_surface_impulse_Q(T, grid, mat, Q, face='z-'):
@@ -892,8 +1062,14 @@ class StagedStepper:
     quick_compare_dirichlet_robin.py:169-178).  `events`: optional list of 5 torch.cuda.Event recorded on
     the launch stream before/between/after the four stage kernels (per-stage HIP-event timing)."""
 
-    def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None):
+    def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None):
         self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
+        if source is not None and not isinstance(source, GoldakSource):
+            raise TypeError("StagedStepper: source must be a GoldakSource (pass a source field to adi_step_numba_coeff)")
+        # moving source: corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step counter
+        # a captured tick advances -- power, origin, velocity, eta and f_f may change between runs without a new graph
+        self.source = source
+        self.captures = 0              # HIP graphs captured by run() so far
         self.fused = fused_supported(grid) if fused is None else (bool(fused) and fused_supported(grid))
         if self.fused:
             # the fused kernel reads T + flags (+ the pack arrays of the axis-0 sweep) and writes U: the sweep's own
@@ -921,26 +1097,35 @@ class StagedStepper:
             check(lib.adi_explicit_rhs(_p(t), _p(g.d_flags), *g.layout.pd, g.dx, prm.dt, kappa, prm.theta,
                                        _p(ta), _stream()))
             self.sweep_into(0, ta, tb)
+        if self.source is not None:
+            _source_lines0_into(tb, g, self.mat, prm, self.packs[0], self.source, self)
+            check(lib.adi_source_tick(_p(_source_block(self)), _stream()))
         self.sweep_into(1, tb, ta)
         self.sweep_into(2, ta, out)
 
-    def run(self, T, nsteps, graph=True):
+    def run(self, T, nsteps, graph=True, t0=0.0):
         """The drivers' `nsub` loop (quick_compare_dirichlet_robin.py:169-178, waam_from_stl_v7_mm.py:525-528): `nsteps`
         steps with the same packs and dt on a device-resident field, returned as a new DeviceField.  The launches of
         two steps (X -> Y -> X) are captured once into a HIP graph and replayed, so small grids are not bound by the
         host's launch path (64^3: 3 kernels + 3 memsets per step, each a ctypes call); the graph is rebuilt when dt,
-        theta, Tinf, the mask or the packs change.  graph=False: plain launches."""
+        theta, Tinf, the mask or the packs change.  graph=False: plain launches.
+        t0: time at the start of the first step (a source's step i runs at t0 + i*dt + dt/2); the source's block is
+        written here, so its power / origin / velocity as they are now hold for this run, and a change of its support's
+        extent recaptures."""
         g, prm = self.grid, self.params
         nsteps = int(nsteps)
         key = (float(prm.dt), float(prm.theta), self.Tinf, g.mask_version, tuple(id(p) for p in self.packs),
                tuple(getattr(p, 'mask_version', None) for p in self.packs),
-               tuple(None if p.d_coeff is None else p.d_coeff.data_ptr() for p in self.packs), self.fused)
+               tuple(None if p.d_coeff is None else p.d_coeff.data_ptr() for p in self.packs), self.fused,
+               None if self.source is None else self.source.shape_key())
         st = getattr(self, '_graph', None)
         if st is None or st['key'] != key:
             X, Y = g.layout.empty(), g.layout.empty()
             st = self._graph = dict(key=key, X=X, Y=Y, g=None)
         X, Y = st['X'], st['Y']
         X.copy_(g.layout.to_layout(T, torch.float64))
+        if self.source is not None:
+            self.source.set_block(_source_block(self), t0, prm.dt)
         if graph and nsteps >= 2 and st['g'] is None:
             g.scratch(2)                                   # every buffer exists before the capture
             self._step_into(X, Y); self._step_into(Y, X)   # warm-up outside the capture (lazy module loads, and the
@@ -952,6 +1137,9 @@ class StagedStepper:
                 self._step_into(X, Y)
                 self._step_into(Y, X)
             st['g'] = cg
+            self.captures += 1
+        if self.source is not None:
+            self.source.set_block(_source_block(self), t0, prm.dt)   # (after the warm-up: the counter starts at 0)
         done = 0
         if graph and st['g'] is not None:
             for _ in range(nsteps // 2):
@@ -965,8 +1153,11 @@ class StagedStepper:
         out.copy_(cur)
         return DeviceField(out)
 
-    def step(self, T, events=None):
+    def step(self, T, events=None, t=0.0):
+        """one step from time t (the source, if any, at t + dt/2)"""
         g, prm = self.grid, self.params
+        if self.source is not None:
+            self.source.set_block(_source_block(self), t, prm.dt)
         t = g.layout.to_layout(T, torch.float64)
         (ta, tb), _, _ = g.scratch(2)
         kappa, _ = _gam(g, self.mat, prm)
@@ -986,6 +1177,8 @@ class StagedStepper:
                                        _p(ta), _stream()))
             mark()
             self.sweep_into(0, ta, tb)
+        if self.source is not None:
+            _source_lines0_into(tb, g, self.mat, prm, self.packs[0], self.source, self)
         mark()
         self.sweep_into(1, tb, ta)
         mark()

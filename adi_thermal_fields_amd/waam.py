@@ -190,10 +190,23 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     return np.asarray(T), nsteps
 
 
+def track_source(heat_source, track_box, dx, yi, t_step):
+    """the heat source of column yi of run_single_track: `heat_source`'s power, efficiency and shape, its centre on the top
+    of the column at the column's start -- ((x0 + x1)/2 dx, (yi + 1/2) dx, z1 dx) -- travelling along +axis 1 at
+    dx / t_step, depth along axis 2; time counts from the start of the column"""
+    x0, x1, z0, z1, _ = track_box
+    s = heat_source
+    return type(s)(s.power, s.eta, s.a, s.b, s.c_f, s.c_r, f_f=s.f_f,
+                   origin=(0.5 * (x0 + x1) * dx, (yi + 0.5) * dx, z1 * dx), velocity=dx / t_step,
+                   travel_axis=1, travel_sign=1, depth_axis=2)
+
+
 def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_track, theta, dt, t_step,
-                     device_resident=True):
+                     device_resident=True, heat_source=None):
     """single_track_on_plate.py:150-177: the deposit advances one column per t_step along axis 1; packs are
-    rebuilt after every column.  track_box = (x0, x1, z0, z1, n_columns)."""
+    rebuilt after every column.  track_box = (x0, x1, z0, z1, n_columns).
+    heat_source (a GoldakSource of the backend): the arc / laser as a moving volumetric source (track_source) during the
+    sub-steps of every column, on top of the newborn cells set to T_track.  None: the reference's driver, unchanged."""
     x0, x1, z0, z1, ncol = track_box
     nx, ny, nz = plate_mask.shape
     mask = plate_mask.copy()
@@ -220,8 +233,13 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         n_sub = max(1, int(math.ceil(t_step / dt)))
         dt_orig = params.dt
         params.dt = t_step / n_sub
-        for _ in range(n_sub):
-            T = _step(backend, T, grid, mat, params, packs, Tinf)
+        if heat_source is None:
+            for _ in range(n_sub):
+                T = _step(backend, T, grid, mat, params, packs, Tinf)
+        else:
+            src = track_source(heat_source, track_box, dx, yi, t_step)
+            for i in range(n_sub):
+                T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=src, t=i * params.dt)
         params.dt = dt_orig
     return np.asarray(T)
 

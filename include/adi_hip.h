@@ -431,6 +431,64 @@ int adi_cyl_sweep(const adi_cyl_plan *plan, int axis, const double *d_in, double
                   const uint8_t *d_active, double T_void, double T_inner, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Volumetric heat source of the Cartesian step (no counterpart in the reference's Cartesian path; the cylindrical step's
+ * `S` is adi3d_cyl_phi_v3.py:339).  For a step t_n -> t_n + dt with a source q(x, t) in W/m^3:
+ *     R0 = Tn + dt*kappa*(1-theta)*(Lx+Ly+Lz) + dt * q(x_c, t_n + dt/2) / (rho*cp)      on in-mask cells
+ * and the three sweeps run unchanged.  Cell centres x_c = ((i+1/2)dx, (j+1/2)dx, (k+1/2)dx); off-mask cells (padding of a
+ * physical box included) receive nothing, Dirichlet rows keep dir_val.
+ *
+ * adi_heat_source: Goldak's double ellipsoid (Goldak, Chakravarti & Bibby 1984), axis-aligned.  With xi, y, z the offsets
+ * of a point from the centre along travel_axis, the transverse axis (the remaining one) and depth_axis:
+ *     q = 6 sqrt(3) f eta P / (a b c pi^1.5) * exp(-3 xi^2/c^2 - 3 y^2/a^2 - 3 z^2/b^2)
+ *     (f, c) = (f_f, c_f) where travel_sign*xi >= 0, else (2 - f_f, c_r);  q = 0 exactly where the exponent exceeds
+ *     ADI_SOURCE_E_CUT (support: +-sqrt(E_CUT/3) times a, b, c).
+ * Over all space q integrates to 2 eta P, over the half-space on one side of the centre plane normal to depth_axis to
+ * eta P (Goldak's normalisation for a centre on the surface; the mask cuts the rest, nothing is renormalised).
+ * The centre at time t is origin + travel_sign * velocity * t along travel_axis (metres; same origin as the cell centres).
+ * Valid: finite values, power >= 0, 0 <= eta <= 1, a, b, c_f, c_r > 0, 0 < f_f < 2, velocity >= 0, axes in 0..2 with
+ * travel_axis != depth_axis, travel_sign = +-1.  Everything else is ADI_ERR_ARG, checked before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct adi_heat_source {
+    double power;        /* P [W] */
+    double eta;          /* efficiency */
+    double a, b;         /* transverse half-width, depth [m] */
+    double c_f, c_r;     /* front / rear length [m] */
+    double f_f;          /* front fraction; f_r = 2 - f_f */
+    double origin[3];    /* centre at t = 0 [m] */
+    double velocity;     /* travel speed [m/s] */
+    int travel_axis, travel_sign, depth_axis, reserved;
+} adi_heat_source;
+
+#define ADI_SOURCE_E_CUT 40.0
+/* device parameter block of a moving source: the source, t0, dt and a 64-bit step counter n (t_n = t0 + n*dt, computed,
+ * never accumulated).  Kernels read it through a pointer, so a captured graph follows the source as the block changes. */
+#define ADI_SOURCE_BLOCK_BYTES 128
+
+/* the source sampled at the cell centres at time t into d_out (box layout; 0 on off-mask cells) */
+int adi_source_sample(const adi_heat_source *h_src, const uint8_t *d_flags, int nx, int ny, int nz, long plane_stride,
+                      double dx, double t, double *d_out, void *stream);
+/* writes the parameter block d_block (ADI_SOURCE_BLOCK_BYTES, device) on `stream`: the source, t0, dt and the counter n */
+int adi_source_set(void *d_block, const adi_heat_source *h_src, double t0, double dt, long long n, void *stream);
+/* n += 1 in the block (one thread; what a captured step ends with) */
+int adi_source_tick(void *d_block, void *stream);
+/* The moving source of one step by superposition: sweep 0 is linear in its right-hand side, so the source term
+ * s = dt*q(t_n + dt/2)/(rho*cp) of R0 adds w = A0^-1 s to its output U.  On the axis-0 lines whose (j, k) can meet the
+ * support (placed on the device from the block's current centre) this solves A0 w = s over the whole line -- A0 assembled
+ * exactly as adi_sweep(axis 0) assembles it for the same pack: d_coeff, or h_face_consts under `sparse` bit 0, d_dir_mask
+ * (NULL: no Dirichlet cells) -- and adds w to d_U in place.  h_src gives the support's extent (the launch grid); its
+ * shape (a, b, c_f, c_r, axes, sign) must be the block's.  The block's counter is not advanced.  Lines of up to 1024 rows
+ * are solved in registers; longer lines need d_work / work_bytes >= adi_source_workspace_bytes (0 for nx <= 1024). */
+int adi_source_workspace_bytes(const adi_heat_source *h_src, int nx, int ny, int nz, double dx, size_t *bytes);
+int adi_source_lines0(const void *d_block, const adi_heat_source *h_src, double *d_U, const uint8_t *d_flags,
+                      const double *d_coeff, const uint8_t *d_dir_mask, int nx, int ny, int nz, long plane_stride,
+                      int sparse, double dx, double theta, double gam, double dt, double rho, double cp,
+                      const double *h_face_consts, void *d_work, size_t work_bytes, void *stream);
+/* adi_explicit_rhs with a source FIELD d_S [W/m^3] (box layout): R0 += dt*S/(rho*cp) on in-mask cells */
+int adi_explicit_rhs_src(const double *d_T, const double *d_S, const uint8_t *d_flags, int nx, int ny, int nz,
+                         long plane_stride, double dx, double dt, double kappa, double theta, double rho, double cp,
+                         double *d_R0, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Context API: the library owns the device memory; callers hand over HOST arrays.
  * One context per GPU and thread; no hidden global state.
  * ---------------------------------------------------------------------------------------------- */
