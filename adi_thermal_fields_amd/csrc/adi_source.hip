@@ -83,11 +83,14 @@ inline int src_box_lines(const adi_heat_source &s, int axis, double dx)
     src_extent(s, axis, lo, hi);
     return (int)floor((lo + hi) / dx) + 4;
 }
+// first line of the launch box, never below -2: a box clamped to n + 4 lines (lines0_box) then still reaches line n + 1,
+// and an unclamped box that starts lower covers no in-grid line the raised one misses (its lines below 0 are off the grid)
 __device__ inline int src_box_first(const adi_heat_source &s, const double (&c)[3], int axis, double dx)
 {
     double lo, hi;
     src_extent(s, axis, lo, hi);
-    return (int)floor((c[axis] - lo) / dx - 0.5) - 1;
+    const int first = (int)floor((c[axis] - lo) / dx - 0.5) - 1;
+    return first > -2 ? first : -2;
 }
 
 // t_n + dt/2 from the block: t_n = t0 + n*dt, computed from the integer counter (no accumulation, no fused multiply-add:
@@ -347,7 +350,8 @@ static int check_source(const adi_heat_source *h, const char *fn)
     return ADI_OK;
 }
 
-// lines of the launch box along axes 1 / 2 (a support wider than the grid: the lines beyond it exit on their own)
+// lines of the launch box along axes 1 / 2, at most n + 4 for a support wider than the grid: the box then starts at line
+// -2 at the lowest (src_box_first) and so reaches every in-grid line; the lines beyond the grid exit on their own
 static void lines0_box(const adi_heat_source &s, int ny, int nz, double dx, int &nj, int &nk)
 {
     nj = src_box_lines(s, 1, dx);
