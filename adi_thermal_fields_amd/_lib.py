@@ -47,6 +47,8 @@ SIGNATURES = {
                                  c_void_pp, c_void_pp, c_void_p]),
     'adi_build_nbr_flags': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
     'adi_build_nbr_flags_planes': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_int, c_int, c_void_p]),
+    'adi_flag_bricks_words': (ctypes.c_long, [c_int, c_int, c_int]),
+    'adi_build_flag_bricks': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_int, c_int, c_void_p]),
     'adi_build_coeffs_planes': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double,
                                         c_int_p, c_double_p, c_void_pp, c_int_p, c_double_p, c_void_pp,
                                         c_void_pp, c_void_pp, c_int, c_int, c_void_p]),
@@ -57,6 +59,9 @@ SIGNATURES = {
     'adi_sweep': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                           c_int, c_int, c_int, c_long, c_int, c_double, c_double, c_double, c_double,
                           c_void_p, c_void_p, c_void_p, c_double_p, c_void_p, c_size_t, c_void_p]),
+    'adi_sweep_bricks': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int, c_int, c_int, c_long, c_int, c_double, c_double, c_double, c_double,
+                                 c_void_p, c_void_p, c_void_p, c_double_p, c_void_p, c_size_t, c_void_p]),
     'adi_face_constants': (c_int, [c_double, c_double, c_double, c_int_p, c_double_p, c_int_p, c_double_p, c_double_p, c_int_p]),
     'adi_sweep_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, c_long, ctypes.POINTER(c_size_t)]),
     'adi_sweep_condense': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -66,6 +71,9 @@ SIGNATURES = {
     'adi_explicit_sweep0': (c_int, [c_int, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int, c_int, c_int, c_long, c_int, c_double, c_double, c_double, c_double, c_double,
                                     c_void_p, c_void_p, c_void_p, c_double_p, c_void_p, c_size_t, c_void_p]),
+    'adi_explicit_sweep0_bricks': (c_int, [c_int, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_int, c_int, c_int, c_long, c_int, c_double, c_double, c_double, c_double,
+                                           c_double, c_void_p, c_void_p, c_void_p, c_double_p, c_void_p, c_size_t, c_void_p]),
     'adi_explicit_condense0': (c_int, [c_int, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int, c_int, c_int, c_long, c_int, c_double, c_double, c_double, c_double,
                                        c_double, c_void_p, c_void_p, c_double_p, c_void_p, c_size_t, c_void_p]),
@@ -101,6 +109,12 @@ SIGNATURES = {
     'adi_step_queued': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_pp, c_void_p, c_void_p,
                          c_void_pp, c_int, c_int, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double,
                          c_double, c_double, c_double, c_double_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'adi_step_bricks': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_pp, c_void_p, c_void_p,
+                                c_void_pp, c_int, c_int, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double,
+                                c_double, c_double, c_double, c_double_p, c_void_p, c_size_t, c_void_p]),
+    'adi_step_queued_bricks': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_pp, c_void_p, c_void_p,
+                                       c_void_pp, c_int, c_int, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double,
+                                       c_double, c_double, c_double, c_double_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     'adi_morph6': (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'adi_flood_outside': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int_p, c_void_p]),
     'adi_pack_frame_f32be': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),

@@ -280,6 +280,7 @@ class Grid3D:
         self._mask = None
         self._d_mask = None
         self._d_flags = None
+        self._d_bricks = None
         self._all_solid = None
         self._scratch = None
         self.mask_version = next(_MASK_VERSIONS)
@@ -315,6 +316,12 @@ class Grid3D:
         k_end = self.layout.pz if k_end is None else k_end
         check(lib.adi_build_nbr_flags_planes(_p(self._d_mask), *self.layout.pd, _p(self._d_flags),
                                              int(k_begin), int(k_end), _stream()))
+        # ... and its summary over the same planes (adi_build_flag_bricks): the FAST kernels skip the flags of set bricks
+        if self._d_bricks is None:
+            self._d_bricks = torch.zeros(int(lib.adi_flag_bricks_words(*self.layout.pd[:3])), dtype=torch.int32,
+                                         device=_device())
+        check(lib.adi_build_flag_bricks(_p(self._d_flags), *self.layout.pd, _p(self._d_bricks), int(k_begin), int(k_end),
+                                        _stream()))
         self.mask_version = next(_MASK_VERSIONS)
         self._all_solid = None
 
@@ -369,6 +376,11 @@ class Grid3D:
     def d_flags(self):
         """neighbour-flags digest of the mask (adi_build_nbr_flags), what the step kernels read"""
         return self._d_flags
+
+    @property
+    def d_bricks(self):
+        """summary of d_flags, one bit per 16^3 brick (adi_build_flag_bricks), rebuilt with the flags; None: none kept"""
+        return getattr(self, '_d_bricks', None)
 
     def scratch(self, n):
         """n cached scratch fields + the long-line workspace (None when not needed)."""
@@ -674,7 +686,7 @@ def _sweep_into(axis, t_in, t_out, grid, mat, params, pack, Tinf, variant=None, 
     v = pack.variant if variant is None else variant
     sp = _sparse_arg(grid, pack, dense)
     nf = _NoFallback(grid, pack, 'sweep', axis, v, sp, work)
-    check(lib.adi_sweep(axis, v, _p(t_in), _p(grid.d_flags), _p(pack.d_coeff), _p(pack.d_dir_mask),
+    check(lib.adi_sweep_bricks(axis, v, _p(t_in), _p(grid.d_flags), _p(grid.d_bricks), _p(pack.d_coeff), _p(pack.d_dir_mask),
                         _p(pack.d_dir_val), _p(pack.d_qflux), *grid.layout.pd,
                         sp | nf.bit, params.theta,
                         gam, params.dt, float(Tinf), _p(t_out),
@@ -704,7 +716,8 @@ def _explicit_sweep0_into(t, t_out, grid, mat, params, pack, Tinf, variant=None,
     vlo, vhi = valid_range(t)
     sp = _sparse_arg(grid, pack, dense)
     nf = _NoFallback(grid, pack, 'fused', 0, v, sp, work)
-    check(lib.adi_explicit_sweep0(v, _p(t), vlo, vhi, _p(grid.d_flags), _p(pack.d_coeff), _p(pack.d_dir_mask),
+    check(lib.adi_explicit_sweep0_bricks(v, _p(t), vlo, vhi, _p(grid.d_flags), _p(grid.d_bricks), _p(pack.d_coeff),
+                                         _p(pack.d_dir_mask),
                                   _p(pack.d_dir_val), _p(pack.d_qflux), *grid.layout.pd,
                                   sp | nf.bit, grid.dx, params.dt, kappa, params.theta,
                                   float(Tinf), _p(t_out), None, None, _fc_arg(grid, pack, sp), _p(work), wb, _stream()))

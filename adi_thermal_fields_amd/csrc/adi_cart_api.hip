@@ -80,7 +80,7 @@ static int sweep_entry(int axis, int variant, const double *d_in, const uint8_t 
                        long plane_stride, int sparse, double theta, double gam, double dt, double Tinf, double *d_out,
                        const double *d_xlo, const double *d_xhi, void *d_work, size_t work_bytes, void *stream,
                        const Fuse *fz, const double *fcs, const double *c_lo = nullptr, const double *c_hi = nullptr,
-                       const double *c_w = nullptr)
+                       const double *c_w = nullptr, const uint32_t *bricks = nullptr)
 {
     ADI_REQUIRE(axis >= 0 && axis < 3, "adi_sweep: bad axis %d", axis);
     bool has_dir, has_q;
@@ -103,6 +103,13 @@ static int sweep_entry(int axis, int variant, const double *d_in, const uint8_t 
     if (s.tg < kMixedMinTg) s.sparse = 0;   // a vanishing time step: GENERAL kernels only (mixed_condense's recurrence would overflow)
     s.nt = store_policy_nt(L.nx, L.sx);
     set_face_consts(s, fcs);
+    if (bricks != nullptr) {
+        // flags summary of d_flags over this box (adi_build_flag_bricks): the FAST kernels synthesize the flags of set bricks
+        s.bricks = bricks;
+        s.lnx = nx; s.lny = ny; s.lnz = nz;
+        s.bnz = (nz + kBrick - 1) / kBrick;
+        s.bwx = ((nx + kBrick - 1) / kBrick + 31) / 32;
+    }
     if (c_w != nullptr && (c_lo != nullptr || c_hi != nullptr)) {
         // deferred interface correction (adi_sweep_corrected): the strided kernels of memory axis 1 add it to what they load
         ADI_REQUIRE(axis == 1 && fz == nullptr && !d_xlo && !d_xhi, "adi_sweep_corrected: axis 1 sweeps only");
@@ -134,15 +141,26 @@ static int sweep_entry(int axis, int variant, const double *d_in, const uint8_t 
     return ADI_OK;
 }
 
+int adi_sweep_bricks(int axis, int variant, const double *d_in, const uint8_t *d_flags, const uint32_t *d_bricks,
+                     const double *d_coeff, const uint8_t *d_dir_mask, const double *d_dir_val, const double *d_qflux, int nx,
+                     int ny, int nz, long plane_stride, int sparse, double theta, double gam, double dt, double Tinf,
+                     double *d_out, const double *d_xlo, const double *d_xhi, const double *h_face_consts, void *d_work,
+                     size_t work_bytes, void *stream)
+{
+    return sweep_entry(axis, variant, d_in, d_flags, d_coeff, d_dir_mask, d_dir_val, d_qflux, nx, ny, nz, plane_stride,
+                       sparse, theta, gam, dt, Tinf, d_out, d_xlo, d_xhi, d_work, work_bytes, stream, nullptr,
+                       h_face_consts, nullptr, nullptr, nullptr, d_bricks);
+}
+
 int adi_sweep(int axis, int variant, const double *d_in, const uint8_t *d_flags, const double *d_coeff,
               const uint8_t *d_dir_mask, const double *d_dir_val, const double *d_qflux, int nx, int ny, int nz,
               long plane_stride, int sparse, double theta, double gam, double dt, double Tinf, double *d_out,
               const double *d_xlo, const double *d_xhi, const double *h_face_consts, void *d_work, size_t work_bytes,
               void *stream)
 {
-    return sweep_entry(axis, variant, d_in, d_flags, d_coeff, d_dir_mask, d_dir_val, d_qflux, nx, ny, nz, plane_stride,
-                       sparse, theta, gam, dt, Tinf, d_out, d_xlo, d_xhi, d_work, work_bytes, stream, nullptr,
-                       h_face_consts);
+    return adi_sweep_bricks(axis, variant, d_in, d_flags, nullptr, d_coeff, d_dir_mask, d_dir_val, d_qflux, nx, ny, nz,
+                            plane_stride, sparse, theta, gam, dt, Tinf, d_out, d_xlo, d_xhi, h_face_consts, d_work, work_bytes,
+                            stream);
 }
 
 int adi_sweep_corrected(int variant, const double *d_in, const uint8_t *d_flags, const double *d_coeff,
@@ -193,18 +211,30 @@ int adi_explicit_fused_supported(int nx, int ny, int nz, long plane_stride, int 
     }
     return pass == 0 ? (nx <= kMaxFastLine) : (condense_is_tiled(0, nx) ? 1 : 0);
 }
-int adi_explicit_sweep0(int variant, const double *d_T, long valid_lo, long valid_hi, const uint8_t *d_flags,
-                        const double *d_coeff, const uint8_t *d_dir_mask, const double *d_dir_val,
-                        const double *d_qflux, int nx, int ny, int nz, long plane_stride, int sparse, double dx,
-                        double dt, double kappa, double theta, double Tinf, double *d_out, const double *d_xlo,
-                        const double *d_xhi, const double *h_face_consts, void *d_work, size_t work_bytes, void *stream)
+int adi_explicit_sweep0_bricks(int variant, const double *d_T, long valid_lo, long valid_hi, const uint8_t *d_flags,
+                               const uint32_t *d_bricks, const double *d_coeff, const uint8_t *d_dir_mask,
+                               const double *d_dir_val, const double *d_qflux, int nx, int ny, int nz, long plane_stride,
+                               int sparse, double dx, double dt, double kappa, double theta, double Tinf, double *d_out,
+                               const double *d_xlo, const double *d_xhi, const double *h_face_consts, void *d_work,
+                               size_t work_bytes, void *stream)
 {
     ADI_REQUIRE(valid_lo <= 0 && valid_hi >= (long)(nx - 1) * (plane_stride ? plane_stride : (long)ny * nz) + (long)ny * nz,
                 "adi_explicit_sweep0: the readable range [%ld, %ld) does not cover the box", valid_lo, valid_hi);
     const Fuse fz = make_fuse(nx, ny, nz, plane_stride, dx, dt, kappa, theta, valid_lo, valid_hi);
     const double gam = kappa * dt / (dx * dx);   // adi3d_numba_coeff.py:292
     return sweep_entry(0, variant, d_T, d_flags, d_coeff, d_dir_mask, d_dir_val, d_qflux, nx, ny, nz, plane_stride,
-                       sparse, theta, gam, dt, Tinf, d_out, d_xlo, d_xhi, d_work, work_bytes, stream, &fz, h_face_consts);
+                       sparse, theta, gam, dt, Tinf, d_out, d_xlo, d_xhi, d_work, work_bytes, stream, &fz, h_face_consts,
+                       nullptr, nullptr, nullptr, d_bricks);
+}
+int adi_explicit_sweep0(int variant, const double *d_T, long valid_lo, long valid_hi, const uint8_t *d_flags,
+                        const double *d_coeff, const uint8_t *d_dir_mask, const double *d_dir_val,
+                        const double *d_qflux, int nx, int ny, int nz, long plane_stride, int sparse, double dx,
+                        double dt, double kappa, double theta, double Tinf, double *d_out, const double *d_xlo,
+                        const double *d_xhi, const double *h_face_consts, void *d_work, size_t work_bytes, void *stream)
+{
+    return adi_explicit_sweep0_bricks(variant, d_T, valid_lo, valid_hi, d_flags, nullptr, d_coeff, d_dir_mask, d_dir_val,
+                                      d_qflux, nx, ny, nz, plane_stride, sparse, dx, dt, kappa, theta, Tinf, d_out, d_xlo,
+                                      d_xhi, h_face_consts, d_work, work_bytes, stream);
 }
 static int condense_entry(int axis, int variant, const double *d_in, const uint8_t *d_flags, const double *d_coeff,
                           const uint8_t *d_dir_mask, const double *d_dir_val, const double *d_qflux, int nx, int ny,
@@ -270,7 +300,8 @@ static int step_impl(const double *d_T_in, double *d_T_out, double *d_tmp_a, dou
                      const double *const *d_coeff, const uint8_t *d_dir_mask, const double *d_dir_val,
                      const double *const *d_qflux, int variant, int sparse, int nx, int ny, int nz, long plane_stride,
                      double dx, double rho, double cp, double k, double dt, double theta, double Tinf,
-                     const double *h_face_consts, void *d_work, size_t work_bytes, void *stream, unsigned *h_queued)
+                     const double *h_face_consts, void *d_work, size_t work_bytes, void *stream, unsigned *h_queued,
+                     const uint32_t *d_bricks)
 {
     ADI_REQUIRE(d_T_in && d_T_out && d_tmp_a && d_tmp_b && d_coeff, "adi_step: null argument");
     const double *fc0 = h_face_consts, *fc1 = h_face_consts ? h_face_consts + 4 : nullptr, *fc2 = h_face_consts ? h_face_consts + 8 : nullptr;
@@ -298,22 +329,22 @@ static int step_impl(const double *d_T_in, double *d_T_out, double *d_tmp_a, dou
     if (adi_explicit_fused_supported(nx, ny, nz, plane_stride, 0)) {
         // stages 1+2 in one pass: R0 is evaluated inside the loads of the axis-0 sweep
         const long sxe = plane_stride ? plane_stride : (long)ny * nz;
-        rc = adi_explicit_sweep0(variant, d_T_in, 0, (long)(nx - 1) * sxe + (long)ny * nz, d_flags, d_coeff[0], d_dir_mask,
+        rc = adi_explicit_sweep0_bricks(variant, d_T_in, 0, (long)(nx - 1) * sxe + (long)ny * nz, d_flags, d_bricks, d_coeff[0], d_dir_mask,
                                  d_dir_val, q0, nx, ny, nz, plane_stride, sparse, dx, dt, kappa, theta, Tinf, d_tmp_b,
                                  nullptr, nullptr, fc0, d_work, work_bytes, stream);
     } else {
         rc = adi_explicit_rhs(d_T_in, d_flags, nx, ny, nz, plane_stride, dx, dt, kappa, theta, d_tmp_a, stream);
         if (rc) return rc;
-        rc = adi_sweep(0, variant, d_tmp_a, d_flags, d_coeff[0], d_dir_mask, d_dir_val, q0, nx, ny, nz, plane_stride, sparse, theta, gam, dt, Tinf, d_tmp_b, nullptr, nullptr, fc0, d_work, work_bytes, stream);
+        rc = adi_sweep_bricks(0, variant, d_tmp_a, d_flags, d_bricks, d_coeff[0], d_dir_mask, d_dir_val, q0, nx, ny, nz, plane_stride, sparse, theta, gam, dt, Tinf, d_tmp_b, nullptr, nullptr, fc0, d_work, work_bytes, stream);
     }
     if (rc) return rc;
     report(0);
     arm(1);
-    rc = adi_sweep(1, variant, d_tmp_b, d_flags, d_coeff[1], d_dir_mask, d_dir_val, q1, nx, ny, nz, plane_stride, sparse, theta, gam, dt, Tinf, d_tmp_a, nullptr, nullptr, fc1, d_work, work_bytes, stream);
+    rc = adi_sweep_bricks(1, variant, d_tmp_b, d_flags, d_bricks, d_coeff[1], d_dir_mask, d_dir_val, q1, nx, ny, nz, plane_stride, sparse, theta, gam, dt, Tinf, d_tmp_a, nullptr, nullptr, fc1, d_work, work_bytes, stream);
     if (rc) return rc;
     report(1);
     arm(2);
-    rc = adi_sweep(2, variant, d_tmp_a, d_flags, d_coeff[2], d_dir_mask, d_dir_val, q2, nx, ny, nz, plane_stride, sparse, theta, gam, dt, Tinf, d_T_out, nullptr, nullptr, fc2, d_work, work_bytes, stream);
+    rc = adi_sweep_bricks(2, variant, d_tmp_a, d_flags, d_bricks, d_coeff[2], d_dir_mask, d_dir_val, q2, nx, ny, nz, plane_stride, sparse, theta, gam, dt, Tinf, d_T_out, nullptr, nullptr, fc2, d_work, work_bytes, stream);
     if (rc) return rc;
     report(2);
     return ADI_OK;
@@ -328,19 +359,41 @@ int adi_step(const double *d_T_in, double *d_T_out, double *d_tmp_a, double *d_t
              const double *h_face_consts, void *d_work, size_t work_bytes, void *stream)
 {
     return step_impl(d_T_in, d_T_out, d_tmp_a, d_tmp_b, d_flags, d_coeff, d_dir_mask, d_dir_val, d_qflux, variant, sparse, nx, ny,
-                     nz, plane_stride, dx, rho, cp, k, dt, theta, Tinf, h_face_consts, d_work, work_bytes, stream, nullptr);
+                     nz, plane_stride, dx, rho, cp, k, dt, theta, Tinf, h_face_consts, d_work, work_bytes, stream, nullptr, nullptr);
 }
 
+int adi_step_bricks(const double *d_T_in, double *d_T_out, double *d_tmp_a, double *d_tmp_b, const uint8_t *d_flags,
+                    const uint32_t *d_bricks, const double *const *d_coeff, const uint8_t *d_dir_mask, const double *d_dir_val,
+                    const double *const *d_qflux, int variant, int sparse, int nx, int ny, int nz, long plane_stride,
+                    double dx, double rho, double cp, double k, double dt, double theta, double Tinf,
+                    const double *h_face_consts, void *d_work, size_t work_bytes, void *stream)
+{
+    return step_impl(d_T_in, d_T_out, d_tmp_a, d_tmp_b, d_flags, d_coeff, d_dir_mask, d_dir_val, d_qflux, variant, sparse, nx, ny,
+                     nz, plane_stride, dx, rho, cp, k, dt, theta, Tinf, h_face_consts, d_work, work_bytes, stream, nullptr,
+                     d_bricks);
+}
+
+int adi_step_queued_bricks(const double *d_T_in, double *d_T_out, double *d_tmp_a, double *d_tmp_b, const uint8_t *d_flags,
+                           const uint32_t *d_bricks, const double *const *d_coeff, const uint8_t *d_dir_mask,
+                           const double *d_dir_val, const double *const *d_qflux, int variant, int sparse, int nx, int ny, int nz,
+                           long plane_stride, double dx, double rho, double cp, double k, double dt, double theta, double Tinf,
+                           const double *h_face_consts, void *d_work, size_t work_bytes, void *stream, unsigned *h_queued)
+{
+    ADI_REQUIRE(h_queued && d_work && work_bytes >= sizeof(unsigned), "adi_step_queued: needs a workspace and three host words");
+    ADI_REQUIRE((sparse & 4) == 0, "adi_step_queued: the no-fallback promise skips the queue it is asked to report");
+    h_queued[0] = h_queued[1] = h_queued[2] = 0xffffffffu;
+    return step_impl(d_T_in, d_T_out, d_tmp_a, d_tmp_b, d_flags, d_coeff, d_dir_mask, d_dir_val, d_qflux, variant, sparse, nx, ny,
+                     nz, plane_stride, dx, rho, cp, k, dt, theta, Tinf, h_face_consts, d_work, work_bytes, stream, h_queued,
+                     d_bricks);
+}
 int adi_step_queued(const double *d_T_in, double *d_T_out, double *d_tmp_a, double *d_tmp_b, const uint8_t *d_flags,
                     const double *const *d_coeff, const uint8_t *d_dir_mask, const double *d_dir_val,
                     const double *const *d_qflux, int variant, int sparse, int nx, int ny, int nz, long plane_stride,
                     double dx, double rho, double cp, double k, double dt, double theta, double Tinf,
                     const double *h_face_consts, void *d_work, size_t work_bytes, void *stream, unsigned *h_queued)
 {
-    ADI_REQUIRE(h_queued && d_work && work_bytes >= sizeof(unsigned), "adi_step_queued: needs a workspace and three host words");
-    ADI_REQUIRE((sparse & 4) == 0, "adi_step_queued: the no-fallback promise skips the queue it is asked to report");
-    h_queued[0] = h_queued[1] = h_queued[2] = 0xffffffffu;
-    return step_impl(d_T_in, d_T_out, d_tmp_a, d_tmp_b, d_flags, d_coeff, d_dir_mask, d_dir_val, d_qflux, variant, sparse, nx, ny,
-                     nz, plane_stride, dx, rho, cp, k, dt, theta, Tinf, h_face_consts, d_work, work_bytes, stream, h_queued);
+    return adi_step_queued_bricks(d_T_in, d_T_out, d_tmp_a, d_tmp_b, d_flags, nullptr, d_coeff, d_dir_mask, d_dir_val, d_qflux,
+                                  variant, sparse, nx, ny, nz, plane_stride, dx, rho, cp, k, dt, theta, Tinf, h_face_consts,
+                                  d_work, work_bytes, stream, h_queued);
 }
 }  // extern "C"

@@ -95,6 +95,12 @@ struct SweepScal {
     int fconst = 0;
     double fc[4] = {0.0, 0.0, 0.0, 0.0};
     int nt = 1;   // streaming output stores (fields beyond the Infinity Cache); 0: plain stores (host: store_policy_nt)
+    // Flags summary (adi_build_flag_bricks; null: every FAST kernel loads its flags bytes): one bit per 16^3 brick of the box
+    // (lnx, lny, lnz), set where every flags byte of the brick is the one its position implies (pos_flags).  The FAST kernels
+    // synthesize the flags of a segment whose bricks are all set instead of loading them (brick_set).  bnz: bricks along
+    // axis 2, bwx: 32-bit words per (axis 1, axis 2) brick column.
+    const unsigned *bricks = nullptr;
+    int lnx = 0, lny = 0, lnz = 0, bnz = 0, bwx = 0;
 };
 
 // fields of at most this many bytes are written with plain stores (scripts/nt_probe.py: plain wins up to 134 - 168 MB per
@@ -381,6 +387,58 @@ __device__ __forceinline__ void wave_lds_fence()
 struct Lay {
     int nx, ny, nz;
     long sx;   // plane stride in elements (>= ny*nz); row stride is nz
+};
+
+// The flags byte a cell at (i, j, k) of an (nx, ny, nz) box holds when it and every neighbour inside the box are in the mask
+// (k_build_flags: bit 0 in mask, bits 1 / 2, 3 / 4, 5 / 6 the minus / plus neighbour along axis 0, 1, 2)
+__host__ __device__ __forceinline__ unsigned pos_flags(int i, int j, int k, int nx, int ny, int nz)
+{
+    return 1u | (i > 0 ? 2u : 0u) | (i + 1 < nx ? 4u : 0u) | (j > 0 ? 8u : 0u) | (j + 1 < ny ? 16u : 0u) | (k > 0 ? 32u : 0u) |
+           (k + 1 < nz ? 64u : 0u);
+}
+// Word of the flags summary that holds the bit of the brick of cell (i, j, k), and that bit: bricks of 16 x 16 x 16 cells,
+// bit (i/16) % 32 of word ((j/16) * bnz + k/16) * bwx + i/512
+__host__ __device__ __forceinline__ long brick_word(int i, int j, int k, int bnz, int bwx)
+{
+    return ((long)(j >> 4) * bnz + (k >> 4)) * bwx + (i >> 9);
+}
+__device__ __forceinline__ unsigned brick_bit(int i) { return 1u << ((i >> 4) & 31); }
+constexpr int kBrick = 16;
+
+// The flags summary of one FAST segment: M rows (M a power of two up to 32, the first row a multiple of M) along `axis` from
+// cell (i, j, k).  load() issues the loads of the words that hold the bits of the bricks the segment meets (one, two at
+// 32 rows); set() tests them -- call it as late as possible, the loads are in flight until then; flags(r) is the flags byte
+// of row r when set() holds.
+template <int M>
+struct SegBricks {
+    static constexpr bool OK = M == 2 || M == 4 || M == 8 || M == 16 || M == 32;
+    static constexpr int NB = M > kBrick ? M / kBrick : 1;
+    unsigned w[NB];
+    unsigned fo, lo, hi;      // the segment's flags bits off the axis; the minus / plus bit of the axis
+    int c, n, axis, i;        // coordinate of row 0 along the axis, line length; axis; i (the word's bit, axes 1 and 2)
+    __device__ __forceinline__ void load(const SweepScal &s, int ax, int ci, int cj, int ck, bool on = true)
+    {                         // (on = false: a lane that owns no rows -- no load, its bits count as set)
+        axis = ax; i = ci;
+        const int cc[3] = {ci, cj, ck}, nn[3] = {s.lnx, s.lny, s.lnz};
+        c = cc[ax]; n = nn[ax];
+        lo = 2u << (2 * ax); hi = lo << 1;
+        fo = pos_flags(ci, cj, ck, s.lnx, s.lny, s.lnz) & ~(lo | hi);
+#pragma unroll
+        for (int q = 0; q < NB; ++q)
+            w[q] = !on ? ~0u : s.bricks[brick_word(ci + (ax == 0 ? kBrick * q : 0), cj + (ax == 1 ? kBrick * q : 0),
+                                       ck + (ax == 2 ? kBrick * q : 0), s.bnz, s.bwx)];
+    }
+    __device__ __forceinline__ bool set() const
+    {
+        bool ok = true;
+#pragma unroll
+        for (int q = 0; q < NB; ++q) ok = ok && (w[q] & brick_bit(axis == 0 ? i + kBrick * q : i)) != 0u;
+        return ok;
+    }
+    __device__ __forceinline__ unsigned flags(int r) const
+    {
+        return fo | (c + r > 0 ? lo : 0u) | (c + r + 1 < n ? hi : 0u);
+    }
 };
 
 // Work queue shared by the FAST and the GENERAL kernel of one sweep: q[0] = number of queued units,

@@ -108,7 +108,12 @@ __global__ __launch_bounds__(256) void k_sweep_contig_fast(
     const long wbase = __shfl(base, 0);
     double d[M];
     unsigned fb[M], db[M];
-    load_bytes_contig<M, VEC>(flags, base, r0, n, active, fb);
+    // flags summary (SweepScal::bricks): the words of this lane's brick go out ahead of the state rows and are tested behind
+    // them; a wave whose bricks are all set loads no flags byte
+    const bool use_b = SegBricks<M>::OK && s.bricks != nullptr;
+    SegBricks<M> B;
+    if (use_b) B.load(s, 2, (int)pi, (int)(line - pi * (unsigned)L.ny), r0, active && r0 < n);
+    else load_bytes_contig<M, VEC>(flags, base, r0, n, active, fb);
     if (HAS_DIR) load_bytes_contig<M, VEC>(dmask, base, r0, n, active, db);
     if constexpr (MODE == 2) coal_load<M>(in + wbase, strip, lane, d);
     else if constexpr (MODE == 3) {
@@ -118,6 +123,14 @@ __global__ __launch_bounds__(256) void k_sweep_contig_fast(
             for (int r = 0; r < M; ++r) d[r] = 0.0;
         }
     } else load_rows_contig<M, VEC>(in, base, r0, n, active, d);
+    if (use_b) {
+        if (__all(B.set())) {
+#pragma unroll
+            for (int r = 0; r < M; ++r) fb[r] = (active && r0 + r < n) ? B.flags(r) : 0u;
+        } else {
+            load_bytes_contig<M, VEC>(flags, base, r0, n, active, fb);
+        }
+    }
     // the two ends of a line are always exposed: fetch their coefficient / flux with the first batch of loads
     const bool sp0 = active && li == 0, spS = active && (r0 + M == n);
     // (per-face scalars, SweepScal::fconst: nothing is loaded, the values follow from the flags below)

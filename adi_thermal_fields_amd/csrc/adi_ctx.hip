@@ -33,6 +33,7 @@ struct adi_ctx {
     long sx;             // padded plane stride (elements)
     size_t N;            // allocated elements per field = nx * sx
     uint8_t *mask, *flags, *dir_mask;
+    uint32_t *bricks;    // summary of the flags (adi_build_flag_bricks), rebuilt with them
     double *T[2];        // ping-pong state
     double *tmp[2];      // stage scratch
     double *coeff[3], *qflux[3], *dir_val;
@@ -54,7 +55,7 @@ static void ctx_free(adi_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    void *ptrs[] = {c->mask, c->flags, c->dir_mask, c->T[0], c->T[1], c->tmp[0], c->tmp[1], c->coeff[0], c->coeff[1],
+    void *ptrs[] = {c->mask, c->flags, c->bricks, c->dir_mask, c->T[0], c->T[1], c->tmp[0], c->tmp[1], c->coeff[0], c->coeff[1],
                     c->coeff[2], c->qflux[0], c->qflux[1], c->qflux[2], c->dir_val, c->work};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -122,6 +123,7 @@ int adi_ctx_create(int nx, int ny, int nz, double dx, int device, adi_ctx **out)
     } while (0)
     CTX_ALLOC(c->mask, c->N);
     CTX_ALLOC(c->flags, c->N);
+    CTX_ALLOC(c->bricks, (size_t)adi_flag_bricks_words(nx, ny, nz) * sizeof(uint32_t));
     CTX_ALLOC(c->dir_mask, c->N);
     CTX_ALLOC(c->dir_val, fb);
     for (int i = 0; i < 2; ++i) { CTX_ALLOC(c->T[i], fb); CTX_ALLOC(c->tmp[i], fb); }
@@ -157,6 +159,8 @@ int adi_ctx_set_mask(adi_ctx *c, const uint8_t *h_mask)
     ADI_HIP_TRY(hipMemsetAsync(c->mask, 0, c->N, c->stream));
     ADI_HIP_TRY(copy_planes(c, c->mask, h_mask, 1, true));
     int rc = adi_build_nbr_flags(c->mask, c->nx, c->ny, c->nz, c->sx, c->flags, c->stream);
+    if (rc != ADI_OK) return rc;
+    rc = adi_build_flag_bricks(c->flags, c->nx, c->ny, c->nz, c->sx, c->bricks, 0, c->nz, c->stream);
     if (rc != ADI_OK) return rc;
     ADI_HIP_TRY(hipStreamSynchronize(c->stream));
     bool all = true;
@@ -281,14 +285,14 @@ int adi_ctx_step(adi_ctx *c, double rho, double cp, double k, double dt, double 
             // first step after a mask / pack change: count the units each sweep's FAST kernel queues (a function of the mask
             // and the packs, not of the field); if there are none, the later steps skip the queue reset and the fallback launch
             unsigned q[3];
-            rc = adi_step_queued(c->T[c->cur], c->T[nxt], c->tmp[0], c->tmp[1], c->flags, c->coeff, c->dir_mask, c->dir_val,
+            rc = adi_step_queued_bricks(c->T[c->cur], c->T[nxt], c->tmp[0], c->tmp[1], c->flags, c->bricks, c->coeff, c->dir_mask, c->dir_val,
                                  c->qflux, c->variant, sp, c->nx, c->ny, c->nz, c->sx, c->dx, rho, cp, k, dt, theta, Tinf,
                                  c->fconsts_ok ? c->fconsts : nullptr, c->work, c->work_bytes, c->stream, q);
             if (rc != ADI_OK) return rc;
             ADI_HIP_TRY(hipStreamSynchronize(c->stream));
             c->promise = (q[0] == 0 && q[1] == 0 && q[2] == 0) ? 1 : 0;
         } else {
-            rc = adi_step(c->T[c->cur], c->T[nxt], c->tmp[0], c->tmp[1], c->flags, c->coeff, c->dir_mask, c->dir_val, c->qflux,
+            rc = adi_step_bricks(c->T[c->cur], c->T[nxt], c->tmp[0], c->tmp[1], c->flags, c->bricks, c->coeff, c->dir_mask, c->dir_val, c->qflux,
                           c->variant, sp | (c->promise == 1 ? 4 : 0), c->nx, c->ny, c->nz, c->sx, c->dx, rho, cp, k, dt, theta, Tinf,
                           c->fconsts_ok ? c->fconsts : nullptr, c->work, c->work_bytes, c->stream);
             if (rc != ADI_OK) return rc;

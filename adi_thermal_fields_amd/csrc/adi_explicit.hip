@@ -3,6 +3,7 @@
 //                     2.5-D marching form; <.., DOTS>: pass A of the slab decomposition folded in
 //   k_explicit_cell   the same, one thread per cell (odd nz, unaligned views)
 //   k_build_flags     the neighbour-flags digest of the mask every step kernel reads
+//   k_build_flag_bricks  its summary: one bit per 16^3 brick whose flags bytes are all the ones their positions imply
 //   k_build_coeffs    Robin coefficient + Neumann flux fields of the three axes in one pass
 //                     (precompute_coeff_packs_unified, adi3d_numba_coeff.py:57-118)
 //   k_exposed         exposed_mask (adi3d_numba_coeff.py:38-55)
@@ -306,6 +307,37 @@ __global__ __launch_bounds__(256) void k_build_flags(const uint8_t *__restrict__
     flags[p] = (uint8_t)f;
 }
 
+// Flags summary (SweepScal::bricks): the bit of a 16 x 16 x 16 brick is set iff every flags byte of the brick (inside the box
+// L) equals pos_flags of its cell -- decided from the flags themselves, so padding, slab halo planes and hand-built flags
+// leave their bricks clear.  One workgroup per brick of the axis-2 brick range [bk0, bk1): thread (di, dj) compares the 16
+// bytes of row (i, j).  Neighbouring bricks share a word: the bit is set / cleared atomically.
+__global__ __launch_bounds__(256) void k_build_flag_bricks(const uint8_t *__restrict__ flags, Lay L, int bk0, int bk1,
+                                                           unsigned *__restrict__ bricks)
+{
+    const int nbx = (L.nx + kBrick - 1) / kBrick, nbz = (L.nz + kBrick - 1) / kBrick, nbr = bk1 - bk0;
+    const int bwx = (nbx + 31) >> 5;
+    const unsigned b = blockIdx.x;
+    const int bi = (int)(b % (unsigned)nbx), bk = bk0 + (int)((b / (unsigned)nbx) % (unsigned)nbr),
+              bj = (int)(b / ((unsigned)nbx * (unsigned)nbr));
+    const int i = bi * kBrick + (int)(threadIdx.x >> 4), j = bj * kBrick + (int)(threadIdx.x & 15u);
+    bool ok = true;
+    if (i < L.nx && j < L.ny) {
+        const uint8_t *row = flags + (long)i * L.sx + (long)j * L.nz;
+#pragma unroll
+        for (int dk = 0; dk < kBrick; ++dk) {
+            const int k = bk * kBrick + dk;
+            if (k < L.nz) ok = ok && row[k] == pos_flags(i, j, k, L.nx, L.ny, L.nz);
+        }
+    }
+    ok = __syncthreads_and(ok);
+    if (threadIdx.x == 0) {
+        unsigned *w = bricks + brick_word(bi * kBrick, bj * kBrick, bk * kBrick, nbz, bwx);
+        const unsigned bit = brick_bit(bi * kBrick);
+        if (ok) atomicOr(w, bit);
+        else atomicAnd(w, ~bit);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K0: coefficient build.  Same accumulation order as the reference ('-' face then '+' face per axis,
 // (h * A) / Ccell with IEEE division), contraction off -> bit-identical packs.
@@ -555,6 +587,31 @@ int adi_build_nbr_flags(const uint8_t *d_mask, int nx, int ny, int nz, long plan
                         void *stream)
 {
     return adi_build_nbr_flags_planes(d_mask, nx, ny, nz, plane_stride, d_flags, 0, nz, stream);
+}
+
+long adi_flag_bricks_words(int nx, int ny, int nz)
+{
+    if (nx <= 0 || ny <= 0 || nz <= 0) return 0;
+    const long nbx = (nx + kBrick - 1) / kBrick, nby = (ny + kBrick - 1) / kBrick, nbz = (nz + kBrick - 1) / kBrick;
+    return nby * nbz * ((nbx + 31) / 32);
+}
+
+int adi_build_flag_bricks(const uint8_t *d_flags, int nx, int ny, int nz, long plane_stride, uint32_t *d_bricks, int k_begin,
+                          int k_end, void *stream)
+{
+    ADI_REQUIRE(d_flags && d_bricks, "adi_build_flag_bricks: null argument");
+    Lay L;
+    if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
+    ADI_REQUIRE(k_begin >= 0 && k_end <= nz && k_begin <= k_end, "adi_build_flag_bricks: bad plane range [%d, %d)", k_begin, k_end);
+    if (k_begin == k_end) return ADI_OK;
+    // every brick that holds a plane of the range
+    const int bk0 = k_begin / kBrick, bk1 = (k_end + kBrick - 1) / kBrick;
+    const long nblocks = (long)((nx + kBrick - 1) / kBrick) * ((ny + kBrick - 1) / kBrick) * (bk1 - bk0);
+    ADI_REQUIRE(nblocks < 0x7fffffffL, "adi_build_flag_bricks: box too large");
+    hipLaunchKernelGGL(k_build_flag_bricks, dim3((unsigned)nblocks), dim3(256), 0, as_stream(stream), d_flags, L, bk0, bk1,
+                       (unsigned *)d_bricks);
+    ADI_CHECK_LAUNCH();
+    return ADI_OK;
 }
 
 int adi_explicit_rhs_planes(const double *d_T, const uint8_t *d_flags, int nx, int ny, int nz, long plane_stride,

@@ -312,7 +312,8 @@ template <int M, bool HAS_DIR>
 __device__ __forceinline__ bool fast_segment_load_buf(const double *__restrict__ in_t, const uint8_t *__restrict__ flags_t,
                                                       const uint8_t *__restrict__ dmask_t, const LineGeom &g, unsigned voff,
                                                       double (&d)[M], unsigned &f0, unsigned &fS, bool &dirS, int &kind,
-                                                      int &Lm, uint8_t *strip = nullptr)
+                                                      int &Lm, uint8_t *strip = nullptr, const SweepScal *bs = nullptr,
+                                                      int ci = 0, int cj = 0, int ck = 0)
 {
     const unsigned FULL = 1u | (3u << g.lbit), ROW0 = 1u | (2u << g.lbit);
     const __amdgpu_buffer_rsrc_t rT = __builtin_amdgcn_make_buffer_rsrc((void *)in_t, 0, 0x7fffffff, 0x00020000);
@@ -321,19 +322,31 @@ __device__ __forceinline__ bool fast_segment_load_buf(const double *__restrict__
     bool uni = true;
     unsigned inm = 0;
     f0 = 0; fS = 0;
+    // flags summary (SweepScal::bricks): (ci, cj, ck) is row 0 of the segment; the words go out ahead of the state rows and
+    // are tested behind them -- a wave whose bricks are all set loads no flags byte
+    const bool use_b = SegBricks<M>::OK && bs != nullptr && bs->bricks != nullptr;
+    SegBricks<M> B;
+    if (use_b) {
+        B.load(*bs, (g.lbit - 1) >> 1, ci, cj, ck);
+#pragma unroll
+        for (int r = 0; r < M; ++r) d[r] = buf_load_f64_once(rT, voff * 8u, (unsigned)r * st * 8u);
+    }
+    const bool syn = use_b && __all(B.set());
     unsigned fw[M >= 4 ? M / 4 : 1];
     if constexpr (M % 4 == 0 && M <= 16) {
-        if (strip != nullptr) load_bytes_packed16<M>(flags_t, voff - (threadIdx.x & 15u), st, (int)(threadIdx.x & 15u), strip, fw);
+        if (strip != nullptr && !syn) load_bytes_packed16<M>(flags_t, voff - (threadIdx.x & 15u), st, (int)(threadIdx.x & 15u), strip, fw);
     }
 #pragma unroll
     for (int r = 0; r < M; ++r) {
         unsigned f;
-        if constexpr (M % 4 == 0 && M <= 16) {
+        if (syn) {
+            f = B.flags(r);
+        } else if constexpr (M % 4 == 0 && M <= 16) {
             f = (strip != nullptr) ? packed_byte<M>(fw, r) : __builtin_amdgcn_raw_buffer_load_b8(rF, voff, (unsigned)r * st, ADI_LOAD_AUX);
         } else {
             f = __builtin_amdgcn_raw_buffer_load_b8(rF, voff, (unsigned)r * st, ADI_LOAD_AUX);
         }
-        d[r] = buf_load_f64_once(rT, voff * 8u, (unsigned)r * st * 8u);
+        if (!use_b) d[r] = buf_load_f64_once(rT, voff * 8u, (unsigned)r * st * 8u);
         inm |= (f & 1u) << r;
         if (r == 0) { f0 = f; uni = uni && ((f & ROW0) == ROW0); }
         else if (r == M - 1) fS = f;
@@ -370,7 +383,7 @@ __device__ __forceinline__ bool fast_segment_load_fused(const double *__restrict
                                                         const uint8_t *__restrict__ dmask_t, const LineGeom &g,
                                                         unsigned voff, int r0, int kk, long tbase, const Fuse &fz,
                                                         double (&d)[M], unsigned &f0, unsigned &fS, bool &dirS, int &kind,
-                                                        int &Lm, uint8_t *strip = nullptr)
+                                                        int &Lm, uint8_t *strip = nullptr, const SweepScal *bs = nullptr)
 {
 #pragma clang fp contract(off)
     constexpr int LINES = 16;
@@ -387,18 +400,33 @@ __device__ __forceinline__ bool fast_segment_load_fused(const double *__restrict
     // the per-thread register, where the descriptor's range check turns an address before or after the window into a
     // load of 0 -- such a neighbour does not exist and the flags byte says so.
     unsigned fb[M];
-    if (strip != nullptr) {
-        if constexpr (M % 4 == 0 && M <= 16) {
-            unsigned fw[M / 4];
-            load_bytes_packed16<M>(flags_t, voff - (threadIdx.x & 15u), (unsigned)g.stride, (int)(threadIdx.x & 15u), strip, fw);
+    // flags summary (SweepScal::bricks; 8 / 16 rows: a segment lies in one brick): the word of this segment's brick goes out
+    // ahead of the state rows and is tested behind them; a wave whose bricks are all set synthesizes its flags bytes
+    const bool use_b = SegBricks<M>::OK && bs != nullptr && bs->bricks != nullptr;
+    SegBricks<M> B;
+    if (use_b) {
+        const int j = (int)(tbase / bs->lnz);                         // (axis 0: a tile is 16 columns k of one row j)
+        B.load(*bs, 0, r0, j, (int)(tbase - (long)j * bs->lnz) + kk);
 #pragma unroll
-            for (int r = 0; r < M; ++r) fb[r] = packed_byte<M>(fw, r);
-        }
+        for (int r = 0; r < M; ++r) d[r] = buf_load_f64(rT, vb, R0 + (unsigned)r * st8);
     }
+    if (use_b && __all(B.set())) {
 #pragma unroll
-    for (int r = 0; r < M; ++r) {
-        if (strip == nullptr) fb[r] = __builtin_amdgcn_raw_buffer_load_b8(rF, voff, (unsigned)r * (unsigned)g.stride, ADI_LOAD_AUX);
-        d[r] = buf_load_f64(rT, vb, R0 + (unsigned)r * st8);
+        for (int r = 0; r < M; ++r) fb[r] = B.flags(r);
+    } else {
+        if (strip != nullptr) {
+            if constexpr (M % 4 == 0 && M <= 16) {
+                unsigned fw[M / 4];
+                load_bytes_packed16<M>(flags_t, voff - (threadIdx.x & 15u), (unsigned)g.stride, (int)(threadIdx.x & 15u), strip, fw);
+#pragma unroll
+                for (int r = 0; r < M; ++r) fb[r] = packed_byte<M>(fw, r);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < M; ++r) {
+            if (strip == nullptr) fb[r] = __builtin_amdgcn_raw_buffer_load_b8(rF, voff, (unsigned)r * (unsigned)g.stride, ADI_LOAD_AUX);
+            if (!use_b) d[r] = buf_load_f64(rT, vb, R0 + (unsigned)r * st8);
+        }
     }
     const unsigned vw = vb + R0;                                     // this thread's row 0, bytes from the window start
     const unsigned vl = vw + (unsigned)(M - 1) * st8;                // its last row

@@ -64,18 +64,22 @@ __global__ __launch_bounds__(512, FUSE ? ADI_FUSE_OCC : 1) void k_sweep_strided_
         const int r0e = pad ? 0 : r0;
         lane_fast = fast_segment_load_fused<M, HAS_DIR, MIXED>(in, flags + tbase, HAS_DIR ? dmask + tbase : dmask, g,
                                                                pad ? (unsigned)kk : voff, r0e, kk, tbase, fz, d, f0, fS, dirS,
-                                                               kind, Lm, strip) || pad;
+                                                               kind, Lm, strip, &s) || pad;
         if (pad) kind = SEG_PAD;
     } else {
         // whole tiles whose rows fit 31-bit byte offsets take the buffer-addressed loader (block-uniform choice)
         const bool whole = kBufStrided && (ti + 1) * LINES <= g.n_inner && Lp * M == g.n &&
                            (long)g.n * g.stride * 8 < 0x7fffffffL;
-        if (whole)
+        if (whole) {
+            // row 0 of this thread's segment (flags summary): axis 0 -- one line per column (j, k); axis 1 -- plane i = to
+            int ci = (int)to, cj = r0, ck = kcol;
+            if (g.lbit == 1 && s.bricks != nullptr) { cj = (int)((unsigned)kcol / (unsigned)s.lnz); ck = kcol - cj * s.lnz; ci = r0; }
             lane_fast = fast_segment_load_buf<M, HAS_DIR>(in + tbase, flags + tbase, HAS_DIR ? dmask + tbase : dmask, g, voff, d,
-                                                          f0, fS, dirS, kind, Lm, strip);
-        else
+                                                          f0, fS, dirS, kind, Lm, strip, &s, ci, cj, ck);
+        } else {
             lane_fast = fast_segment_load<M, HAS_DIR>(in + tbase, flags + tbase, HAS_DIR ? dmask + tbase : dmask, g, voff, r0,
                                                       active, d, f0, fS, dirS, kind, Lm);
+        }
     }
     if (pad) { f0 = 0; fS = 0; dirS = false; }       // (the fused loader showed a padding thread segment 0's flags)
     if (!MIXED && kind >= SEG_TAIL) lane_fast = false;

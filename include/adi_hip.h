@@ -137,6 +137,17 @@ int adi_build_nbr_flags(const uint8_t *d_mask, int nx, int ny, int nz, long plan
  * the one below / above it change (waam_from_stl_v7_mm.py:487-495 rebuilds everything; the result is the same). */
 int adi_build_nbr_flags_planes(const uint8_t *d_mask, int nx, int ny, int nz, long plane_stride, uint8_t *d_flags,
                                int k_begin, int k_end, void *stream);
+/* Flags summary: one bit per brick of 16 x 16 x 16 cells of the box (nx, ny, nz), set iff every flags byte of the brick is
+ * the one its position implies -- in the mask, and each of the six neighbour bits set iff that neighbour lies inside the
+ * box.  The bit of the brick of cell (i, j, k) is bit (i/16) % 32 of word ((j/16) * nbz + k/16) * nwx + i/512, with
+ * nbz = ceil(nz/16), nwx = ceil(ceil(nx/16)/32); adi_flag_bricks_words gives the number of 32-bit words (0: bad box).
+ * adi_build_flag_bricks compares d_flags with the implied bytes on the device and rewrites the bits of every brick that holds
+ * a plane of [k_begin, k_end) of axis 2: call it over the same range whenever the flags change.  A stale summary gives
+ * wrong results.  The *_bricks entry points below take it (d_bricks NULL: the plain entry point): their FAST kernels
+ * synthesize the flags bytes of segments whose bricks are set instead of loading them; results are bit-identical. */
+long adi_flag_bricks_words(int nx, int ny, int nz);
+int adi_build_flag_bricks(const uint8_t *d_flags, int nx, int ny, int nz, long plane_stride, uint32_t *d_bricks,
+                          int k_begin, int k_end, void *stream);
 
 /* lap1D_x/y/z + R0 = Tn + dt*kappa*(1-theta)*(Lx+Ly+Lz): adi3d_numba_coeff.py:240-288, :298 */
 int adi_explicit_rhs(const double *d_T, const uint8_t *d_flags, int nx, int ny, int nz, long plane_stride,
@@ -180,6 +191,13 @@ int adi_sweep(int axis, int variant, const double *d_in, const uint8_t *d_flags,
               double theta, double gam, double dt, double Tinf,
               double *d_out, const double *d_xlo, const double *d_xhi, const double *h_face_consts,
               void *d_work, size_t work_bytes, void *stream);
+/* adi_sweep with the flags summary of d_flags (adi_build_flag_bricks) */
+int adi_sweep_bricks(int axis, int variant, const double *d_in, const uint8_t *d_flags, const uint32_t *d_bricks,
+                     const double *d_coeff, const uint8_t *d_dir_mask, const double *d_dir_val, const double *d_qflux,
+                     int nx, int ny, int nz, long plane_stride, int sparse,
+                     double theta, double gam, double dt, double Tinf,
+                     double *d_out, const double *d_xlo, const double *d_xhi, const double *h_face_consts,
+                     void *d_work, size_t work_bytes, void *stream);
 /* (c-, c+, q-, q+) per axis for adi_sweep & co.: h_consts[12] = [axis][4], h_valid[3] = 1 where both faces of the axis carry
  * scalars or nothing (ADI_FACE_SCALAR / ADI_FACE_NONE) for h AND q -- only then may h_consts + 4*axis be passed on.
  * Host arithmetic, the very expressions of adi_build_coeffs. */
@@ -219,6 +237,13 @@ int adi_explicit_sweep0(int variant, const double *d_T, long valid_lo, long vali
                         double dx, double dt, double kappa, double theta, double Tinf,
                         double *d_out, const double *d_xlo, const double *d_xhi, const double *h_face_consts,
                         void *d_work, size_t work_bytes, void *stream);
+/* adi_explicit_sweep0 with the flags summary of d_flags (adi_build_flag_bricks) */
+int adi_explicit_sweep0_bricks(int variant, const double *d_T, long valid_lo, long valid_hi, const uint8_t *d_flags,
+                               const uint32_t *d_bricks, const double *d_coeff, const uint8_t *d_dir_mask,
+                               const double *d_dir_val, const double *d_qflux, int nx, int ny, int nz, long plane_stride,
+                               int sparse, double dx, double dt, double kappa, double theta, double Tinf,
+                               double *d_out, const double *d_xlo, const double *d_xhi, const double *h_face_consts,
+                               void *d_work, size_t work_bytes, void *stream);
 int adi_explicit_condense0(int variant, const double *d_T, long valid_lo, long valid_hi, const uint8_t *d_flags,
                            const double *d_coeff, const uint8_t *d_dir_mask, const double *d_dir_val,
                            const double *d_qflux, int nx, int ny, int nz, long plane_stride, int sparse,
@@ -364,6 +389,19 @@ int adi_step(const double *d_T_in, double *d_T_out, double *d_tmp_a, double *d_t
  * every later step of the same configuration; adi_ctx_step does this on the first step after a mask / pack change. */
 int adi_step_queued(const double *d_T_in, double *d_T_out, double *d_tmp_a, double *d_tmp_b,
              const uint8_t *d_flags, const double *const *d_coeff, const uint8_t *d_dir_mask,
+             const double *d_dir_val, const double *const *d_qflux, int variant, int sparse,
+             int nx, int ny, int nz, long plane_stride, double dx, double rho, double cp, double k,
+             double dt, double theta, double Tinf, const double *h_face_consts,
+             void *d_work, size_t work_bytes, void *stream, unsigned *h_queued);
+/* adi_step / adi_step_queued with the flags summary of d_flags (adi_build_flag_bricks) */
+int adi_step_bricks(const double *d_T_in, double *d_T_out, double *d_tmp_a, double *d_tmp_b,
+             const uint8_t *d_flags, const uint32_t *d_bricks, const double *const *d_coeff, const uint8_t *d_dir_mask,
+             const double *d_dir_val, const double *const *d_qflux, int variant, int sparse,
+             int nx, int ny, int nz, long plane_stride, double dx, double rho, double cp, double k,
+             double dt, double theta, double Tinf, const double *h_face_consts,
+             void *d_work, size_t work_bytes, void *stream);
+int adi_step_queued_bricks(const double *d_T_in, double *d_T_out, double *d_tmp_a, double *d_tmp_b,
+             const uint8_t *d_flags, const uint32_t *d_bricks, const double *const *d_coeff, const uint8_t *d_dir_mask,
              const double *d_dir_val, const double *const *d_qflux, int variant, int sparse,
              int nx, int ny, int nz, long plane_stride, double dx, double rho, double cp, double k,
              double dt, double theta, double Tinf, const double *h_face_consts,
