@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: ADI steps/s and HBM GB/s, 512^3 fp64 Cartesian Robin, 1..8 MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 512] [--scaling weak|strong] [--mask box|ellipsoid] [--no-cpu]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 512] [--scaling weak|strong] [--mask box|ellipsoid]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-also]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -20,6 +20,12 @@ reduced interface system of the sharded-axis sweep travel over RCCL.
 
 Prints ONE JSON line on rank 0.  `value` = 512^3-cell-equivalent ADI steps per second summed over all
 ranks (= plain steps/s at N = 1, n = 512).
+
+A plain run does only what that line's headline needs: set up, warm up, time the K steps, write --dump-outputs, print.
+--full adds everything else the benchmark measures or checks, each outside the timed region: the CPU baseline and the
+parity of the timed stepper against the CPU oracle (N = 1), the 42 B/cell general-pack sweep figures and
+`north_star_x_sweep` (N = 1), the other BASELINE.json configurations in `also` (N = 1), and `parity_vs_one_domain`
+(N > 1 and --force-dist).
 """
 import argparse
 import gc
@@ -46,7 +52,10 @@ def parse(argv=None):
     ap.add_argument('--config', choices=['cart', 'cyl'], default='cart',
                     help="cart: the headline 512^3 Cartesian workload (default); cyl: BASELINE.json configs[3], the "
                          "cylindrical 128 x 256 x 512 BE step on one GPU (replicas only at N > 1: it does not shard)")
-    ap.add_argument('--no-cpu', action='store_true', help='skip the CPU baseline leg')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline does not need (see the module docstring): CPU baseline and oracle parity, '
+                         'the 42 B/cell sweep figures, the `also` configurations, parity_vs_one_domain at N > 1')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: skip the CPU baseline leg')
     ap.add_argument('--cpu-n', type=int, default=512, help='edge of the CPU-baseline sample (512: BASELINE.md section 3)')
     ap.add_argument('--force-dist', action='store_true',
                     help='one GPU only: run the slab code path over a real single-rank RCCL process group (checks the '
@@ -68,7 +77,8 @@ def parse(argv=None):
                          'every rank on cuda:0 and stages the payloads through pinned host memory (dist_slab.HostStagedDistComm): '
                          'runs the whole N > 1 code path with real processes on a one-GPU box; the line is marked')
     ap.add_argument('--no-also', action='store_true',
-                    help='N = 1: skip the `also` object (the other BASELINE.json configs, 20 steps each, after the timed region)')
+                    help='with --full, N = 1: skip the `also` object (the other BASELINE.json configs, 20 steps each, after the '
+                         'timed region)')
     ap.add_argument('--pg-timeout', type=float, default=120.0,
                     help='seconds a collective of the process group may wait before the rank aborts with a stack trace')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -564,7 +574,7 @@ def main_cyl(a):
                 kernels=kernels)
     if dumped is not None:
         line['dumped_outputs'] = dumped
-    if not a.no_cpu:
+    if a.full and not a.no_cpu:
         # the NumPy restatement of adi3d_cyl_phi_v3.adi_step (BE) on a bounded sample of the same workload
         from oracle import cyl_oracle as orc
         cn = (128, 256, 512)      # the full workload: one NumPy step takes 15-20 s
@@ -689,11 +699,12 @@ def main(argv=None):
             if rehearse:      # a middle rank of `rehearse`: loopback copies, or (--force-dist) RCCL send/recv to itself
                 return (dist_slab.SelfLoopDistComm if force_dist else dist_slab.LoopbackComm)(rehearse, rehearse // 2)
             return dist_slab.HostStagedDistComm() if staged else dist_slab.TorchDistComm()
-        # Before anything is timed: does this job's decomposition reproduce the one-domain result?  (1) the n^3 grid cut over
-        # the ranks (BASELINE.json configs[2]; the strong-scaling workload itself); (2) with weak scaling also this job's own slab
-        # thickness -- n planes per rank, hence the interface form of the timed loop -- on a grid of reduced lateral extent
-        # (W*n x 128 x 128), which rank 0 can step on one domain in milliseconds.
-        if world > 1 or (force_dist and not rehearse):      # (--force-dist: the same calls over a one-rank RCCL group, a plumbing check)
+        # --full, before anything is timed: does this job's decomposition reproduce the one-domain result?  (1) the n^3 grid
+        # cut over the ranks (BASELINE.json configs[2]; the strong-scaling workload itself); (2) with weak scaling also this job's
+        # own slab thickness -- n planes per rank, hence the interface form of the timed loop -- on a grid of reduced lateral
+        # extent (W*n x 128 x 128), which rank 0 can step on one domain in milliseconds.
+        # (--force-dist: the same calls over a one-rank RCCL group, a plumbing check)
+        if a.full and (world > 1 or (force_dist and not rehearse)):
             from adi_thermal_fields_amd.dist_slab import split_planes as _split
             parity_1d = parity_vs_one_domain(a, adi, dist_slab, dist, world, rank, mat, prm, dx, Tinf, make_comm, staged,
                                              _split(n, world), n, n, '%d^3 cut into slabs over the %d ranks (strong split)' % (n, world))
@@ -716,7 +727,8 @@ def main(argv=None):
     # contiguous one is the kernel the 60 % target of BASELINE.json is written against.  Measured with the same event method,
     # outside the timed region -- and BEFORE it: these ~45 ms of GPU work also bring the device to its steady clocks, which the
     # W warm-up steps alone (7 ms at the driver's W = 5) do not (same box, same build: 672 steps/s over 20 steps from a cold
-    # start, 695 over 50; the line says so in `prewarm`).
+    # start, 695 over 50; the line says so in `prewarm`).  A plain run makes the same launches, so that its timed region starts
+    # from the same device state and allocator layout (the general packs stay allocated); only --full reports their figures.
     quiet_gc()             # no cyclic collection from here to the end of the timed region (a collection takes 0.1 s of host time or
     xs = None              # more: inside the loop it is a 40 ms outlier, between the warm-up and the loop it lets the GPU clock down)
     if not multi:
@@ -837,9 +849,10 @@ def main(argv=None):
     if dumped is not None:
         line['dumped_outputs'] = dumped
     if xs is not None:
-        line['general_pack_sweeps_42B'] = xs
         line['prewarm'] = ('the 42 B/cell sweep measurements (3 x 13 launches, about 45 ms of GPU work) run before the warm-up steps: '
                            'the timed region starts on a device at its steady clocks')
+    if xs is not None and a.full:
+        line['general_pack_sweeps_42B'] = xs
         # BASELINE.json's target is written against this kernel: ">= 60 % of MI355X HBM peak on the x-sweep batched
         # Thomas solve for a 512^3 fp64 Cartesian grid at 1 GPU" (x = the contiguous axis), the reference's own data model
         x = xs['sweep_axis2_contig']
@@ -847,9 +860,9 @@ def main(argv=None):
                                           achieved=x['achieved_gbs'], peak=HBM_PEAK_GBS, unit='GB/s', frac=x['frac'],
                                           target_frac=0.60,
                                           lean_sparse_variant_in_step=kernels.get('sweep_axis2_contig'))
-    if not multi and not a.no_also:
+    if a.full and not multi and not a.no_also:
         line['also'] = also_configs(a, adi, mat, prm, dx, Tinf, dev)
-    if not multi and not a.no_cpu:
+    if a.full and not multi and not a.no_cpu:
         # parity of the very kernels that were timed: PARITY_STEPS steps of the timed stepper from T0 (or, with --cpu-n,
         # of the same workload at that edge) against the single-thread oracle leg started from the same host array
         PARITY_STEPS = 3

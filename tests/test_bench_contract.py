@@ -1,6 +1,6 @@
-"""GPU: bench.py prints ONE JSON line with the contract's keys (small grid, a few steps): the single-GPU line with `roofline`,
-`cpu_baseline` and `parity_rel_linf`, the rehearsal lines of both scaling modes marked as rehearsals, the cylindrical and the
-curved-solid variants."""
+"""GPU: bench.py prints ONE JSON line with the contract's keys (small grid, a few steps): the single-GPU --full line with
+`roofline`, `cpu_baseline` and `parity_rel_linf`, the plain lines without what only --full adds, the rehearsal lines of both
+scaling modes marked as rehearsals, the cylindrical and the curved-solid variants."""
 import json
 import os
 import subprocess
@@ -36,7 +36,7 @@ def _bench(*args):
 
 
 def test_single_gpu_line_with_cpu_baseline_and_parity():
-    d = _bench('--n', '64', '--cpu-n', '64', '--steps', '4', '--warmup', '2')
+    d = _bench('--n', '64', '--cpu-n', '64', '--steps', '4', '--warmup', '2', '--full')
     assert d['n_gpus'] == 1 and d['steps'] == 4 and d['warmup'] == 2 and d['scaling'] == 'weak'
     cb = d['cpu_baseline']
     for k in ('value', 'unit', 'cores', 'kind', 'sample'):
@@ -56,6 +56,19 @@ def test_single_gpu_line_with_cpu_baseline_and_parity():
     rf = al['robin_field_ellipsoid_64']
     assert rf['bytes_per_cell_step'] > al['ellipsoid_64']['bytes_per_cell_step']      # its sweeps load coefficient arrays
     assert rf['target_vs_scalar_h'] == 1.10 and rf['vs_scalar_h_ellipsoid'] > 0
+
+
+def test_plain_lines_leave_the_extras_to_full():
+    """without --full the line carries the headline and its per-stage figures, and nothing that takes runs of its own"""
+    full_only = {'cpu_baseline', 'cpu_baseline_all_cores', 'parity', 'parity_rel_linf', 'also', 'general_pack_sweeps_42B',
+                 'north_star_x_sweep', 'parity_vs_one_domain'}
+    d = _bench('--n', '64', '--cpu-n', '64', '--steps', '4', '--warmup', '2')
+    assert d['steps'] == 4 and d['warmup'] == 2 and 'prewarm' in d and len(d['kernels']) >= 3
+    assert not full_only & set(d), sorted(full_only & set(d))
+    d = _bench('--config', 'cyl', '--steps', '2', '--warmup', '1')
+    assert d['metric'].startswith('adi_cyl') and not full_only & set(d), sorted(full_only & set(d))
+    d = _bench('--n', '128', '--steps', '3', '--warmup', '2', '--force-dist')
+    assert d['ranks']['backend'] == 'nccl' and not full_only & set(d), sorted(full_only & set(d))
 
 
 @pytest.mark.parametrize('scaling,form', [('weak', 'deferred_exact'), ('strong', 'deferred_exact')])   # (256 rows at cfl 200: no decay)
@@ -80,7 +93,7 @@ def test_two_real_ranks_line_proves_itself_against_one_domain(scaling):
     cut over the ranks against the same steps on one domain, <= 1e-12 -- and, with weak scaling, the
     same for the timed job's own slab thickness; plus the `ranks` record."""
     d = _bench('--gpus', '2', '--n', '128', '--steps', '3', '--warmup', '2', '--no-cpu', '--transport', 'gloo-staged',
-               '--scaling', scaling)
+               '--scaling', scaling, '--full')
     assert d['n_gpus'] == 2 and d['scaling'] == scaling
     p = d['parity_vs_one_domain']
     assert p['ok'] is True and p['rel_linf'] <= 1e-12 and p['bar'] == 1e-12 and p['steps'] == 3 and p['forms_agree']
@@ -98,7 +111,7 @@ def test_two_real_ranks_line_proves_itself_against_one_domain(scaling):
 def test_single_rank_rccl_line_runs_the_parity_calls_over_nccl():
     """--force-dist: the slab path over a one-rank RCCL process group; the calls of parity_vs_one_domain (gather, object
     all-gather, the one-domain leg) go through the real `nccl` backend here, the only place a one-GPU box can exercise them"""
-    d = _bench('--n', '128', '--steps', '3', '--warmup', '2', '--no-cpu', '--force-dist')
+    d = _bench('--n', '128', '--steps', '3', '--warmup', '2', '--no-cpu', '--force-dist', '--full')
     p = d['parity_vs_one_domain']
     assert p['ok'] is True and p['rel_linf'] <= 1e-12 and p['planes_per_rank'] == [128]
     assert d['ranks']['backend'] == 'nccl' and d['ranks']['world_size_from_process_group'] == 1
