@@ -155,6 +155,7 @@ SIGNATURES = {
     'adi_ctx_last_step_ms': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_float)]),
 }
 
+MAX_BOX_CELLS = 1 << 32       # ADI_MAX_BOX_CELLS: nx * plane_stride of a Cartesian box stays below it
 SOURCE_BLOCK_BYTES = 128     # ADI_SOURCE_BLOCK_BYTES
 SOURCE_E_CUT = 40.0          # ADI_SOURCE_E_CUT
 

@@ -87,6 +87,9 @@ class Layout:
         assert self.px >= self.nx and self.py >= self.ny and self.pz >= self.nz
         self.sx = int(lib.adi_recommended_plane_stride(self.py, self.pz)) if sx is None else int(sx)
         assert self.sx >= self.py * self.pz
+        if self.px * self.sx >= _lib.MAX_BOX_CELLS:
+            raise ValueError("grid %d x %d x %d: its padded box of %d x %d cells reaches the 2^32-cell limit of the "
+                             "Cartesian kernels (ADI_MAX_BOX_CELLS)" % (self.nx, self.ny, self.nz, self.px, self.sx))
 
     @property
     def shape(self):

@@ -142,8 +142,11 @@ inline int make_lay(int nx, int ny, int nz, long plane_stride, Lay *L)
     if (plane_stride != 0 && plane_stride < dense)
         return set_err(ADI_ERR_ARG, "plane_stride %ld < ny*nz = %ld", plane_stride, dense);
     if (dense > 0x7fffffffL) return set_err(ADI_ERR_UNSUPPORTED, "plane of %ld cells is too large", dense);
+    const long sx = plane_stride ? plane_stride : dense;
+    if (sx > (kMaxBoxCells - 1) / nx)   // nx * sx >= 2^32 (without overflowing a long)
+        return set_err(ADI_ERR_UNSUPPORTED, "box of %d x %ld cells reaches the 2^32-cell limit of the Cartesian kernels", nx, sx);
     L->nx = nx; L->ny = ny; L->nz = nz;
-    L->sx = plane_stride ? plane_stride : dense;
+    L->sx = sx;
     return ADI_OK;
 }
 

@@ -39,4 +39,8 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
 // rows-per-thread limit of the in-register partition kernels: 64 lanes x 16 rows
 constexpr int kMaxFastLine = 1024;
 
+// largest padded box (nx x plane_stride cells) the Cartesian kernels address: the strided loaders carry a thread's offset
+// from its tile base as one 32-bit element count, which along axis 0 spans the whole box (ADI_MAX_BOX_CELLS)
+constexpr long kMaxBoxCells = 1L << 32;
+
 }  // namespace adi

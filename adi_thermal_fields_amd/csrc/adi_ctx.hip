@@ -105,6 +105,8 @@ int adi_ctx_create(int nx, int ny, int nz, double dx, int device, adi_ctx **out)
 {
     ADI_REQUIRE(out, "adi_ctx_create: null output");
     ADI_REQUIRE(nx > 0 && ny > 0 && nz > 0 && dx > 0.0, "adi_ctx_create: bad grid %d x %d x %d, dx=%g", nx, ny, nz, dx);
+    if (adi_recommended_plane_stride(ny, nz) > (kMaxBoxCells - 1) / nx)   // make_lay's limit, before any device memory is taken
+        return set_err(ADI_ERR_UNSUPPORTED, "adi_ctx_create: box of %d x %d x %d cells reaches the 2^32-cell limit", nx, ny, nz);
     ADI_HIP_TRY(hipSetDevice(device));
     adi_ctx *c = new (std::nothrow) adi_ctx();
     if (!c) return set_err(ADI_ERR_HIP, "adi_ctx_create: out of host memory");

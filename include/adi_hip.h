@@ -75,7 +75,13 @@ int         adi_copy_planes(void *dst, size_t dst_pitch, const void *src, size_t
  * plane_stride >= ny*nz in ELEMENTS (0 means dense, ny*nz).  A padded plane stride keeps the rows of an
  * axis-0 line off the same HBM channels; adi_recommended_plane_stride() returns the pitch this library
  * wants for a given (ny, nz).  Per-line arrays (d_xlo, d_xhi, d_cond) are dense.
+ *
+ * Box limit: nx * plane_stride < ADI_MAX_BOX_CELLS (2^32 cells, 32 GiB per fp64 field).  The strided kernels address a
+ * row as one 32-bit element offset from a tile base that, along axis 0, can be anywhere in the box; every Cartesian entry
+ * point (and adi_ctx_create) refuses a larger box with ADI_ERR_UNSUPPORTED before any HIP call.  Planes are limited to
+ * ny * nz < 2^31 cells.
  * ---------------------------------------------------------------------------------------------- */
+#define ADI_MAX_BOX_CELLS 4294967296LL
 long adi_recommended_plane_stride(int ny, int nz);
 
 /* Physical extents the library recommends for a logical (nx, ny, nz) grid (ABI v16): each >= the logical extent, chosen
