@@ -140,6 +140,11 @@ SIGNATURES = {
     'adi_source_lines0': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long,
                                   c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double_p, c_void_p,
                                   c_size_t, c_void_p]),
+    'adi_source_lines0_slab': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                       c_long, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double,
+                                       c_double_p, c_void_p, c_size_t, c_void_p]),
+    'adi_source_add_r0': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int,
+                                  c_int, c_int, c_double, c_double, c_double, c_double, c_void_p]),
     'adi_source_workspace_bytes': (c_int, [c_void_p, c_int, c_int, c_int, c_double, ctypes.POINTER(c_size_t)]),
     'adi_explicit_rhs_src': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double,
                                      c_double, c_double, c_double, c_void_p, c_void_p]),

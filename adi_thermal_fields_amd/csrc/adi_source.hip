@@ -6,7 +6,12 @@
 //                       solve of adi_core.hpp); k_source_lines0_long: the same for lines of more than 1024 rows, one
 //                       thread per line with the Thomas factors in a workspace
 //   k_source_set, k_source_tick   the device parameter block (source, t0, dt, step counter) a captured graph reads
-// No existing kernel changes: the correction runs after whichever sweep-0 form (fused or not) the step used.
+//   k_source_add_r0     the source added to R0 on the planes of a slab the support can meet (the slab forms whose axis-0 lines
+//                       cross ranks without a zero-boundary local solve: dist_slab's 'exact', 'slab', 'window')
+//   k_source_lines0_slab, k_source_lines0_long_slab   the lines kernels for one slab of a grid cut along axis 0
+// No existing kernel changes: the correction runs after whichever sweep-0 form (fused or not) the step used.  The slab
+// kernels take a plane origin i_org: local plane i of a slab that starts at global plane i_org has its centre at
+// (i_org + i + 1/2) dx; the single-domain kernels are the same bodies without it (their arguments and arithmetic as before).
 #include <math.h>
 
 #include "adi_cart_host.hpp"
@@ -154,6 +159,13 @@ struct LinesArgs {
     double fc0, fc1;            // c-, c+ of the axis-0 faces (fconst)
     int nj, nk;                 // lines of the launch box along axes 1 / 2
 };
+// the same for one slab of a grid cut along axis 0: local plane i lies at global plane i_org + i
+struct LinesArgsSlab : LinesArgs {
+    int i_org;
+};
+// global plane of local plane i: the single-domain kernels keep their arithmetic (and their code) as it was
+__device__ inline int lines0_plane(const LinesArgs &, int i) { return i; }
+__device__ inline int lines0_plane(const LinesArgsSlab &A, int i) { return A.i_org + i; }
 
 // The axis-0 line (j, k) = (first_j + jb, first_k + kb) of the launch box, placed from the centre at the block's mid-step
 // time.  It takes part when it lies in the grid and in the box and its (j, k) offsets alone do not put it outside the
@@ -176,9 +188,10 @@ __device__ inline bool lines0_line(const SrcBlock &B, const Lay &L, const LinesA
 // Row i of A0 w = s on the line at `base` = j*nz + k, assembled as adi_sweep(axis 0) assembles it (assemble_row): b the
 // diagonal, lo / hi whether the row couples to its minus / plus neighbour (coefficient -tg), rhs = s.  Off-mask and
 // Dirichlet rows are identity rows with s = 0.
+template <class AR>
 __device__ inline void lines0_row(const adi_heat_source &s, const double (&c)[3], const uint8_t *__restrict__ flags,
                                   const double *__restrict__ coeff, const uint8_t *__restrict__ dirm, const Lay &L,
-                                  const LinesArgs &A, int i, long base, double yj, double zk, double &b, bool &lo,
+                                  const AR &A, int i, long base, double yj, double zk, double &b, bool &lo,
                                   bool &hi, double &rhs)
 {
 #pragma clang fp contract(off)
@@ -199,17 +212,17 @@ __device__ inline void lines0_row(const adi_heat_source &s, const double (&c)[3]
     const double nnb = (double)((int)mL + (int)mR);
     b = 1.0 + A.tg * nnb + A.dt * co;      // assemble_row's diagonal, same operations
     lo = mL; hi = mR;
-    rhs = A.scale * goldak_q(s, c, (i + 0.5) * A.dx, yj, zk);
+    rhs = A.scale * goldak_q(s, c, (lines0_plane(A, i) + 0.5) * A.dx, yj, zk);
 }
 
 // Lines longer than the in-register limit (nx > kMaxFastLine): one thread per line, Thomas along the line with c' and d'
 // in the workspace ([2][nx][lines of the box], lines dense, so the threads of a wave touch adjacent words), then the back
 // substitution adds w to U.  Lanes are adjacent lines along k, so every row access of a wave is contiguous.
-__global__ __launch_bounds__(256) void k_source_lines0_long(const SrcBlock *__restrict__ blk, double *__restrict__ U,
-                                                            const uint8_t *__restrict__ flags,
-                                                            const double *__restrict__ coeff,
-                                                            const uint8_t *__restrict__ dirm, Lay L, LinesArgs A,
-                                                            double *__restrict__ work)
+template <class AR>
+__device__ __forceinline__ void lines0_long(const SrcBlock *__restrict__ blk, double *__restrict__ U,
+                                            const uint8_t *__restrict__ flags, const double *__restrict__ coeff,
+                                            const uint8_t *__restrict__ dirm, const Lay &L, const AR &A,
+                                            double *__restrict__ work)
 {
 #pragma clang fp contract(off)
     const SrcBlock &B = *blk;
@@ -246,18 +259,34 @@ __global__ __launch_bounds__(256) void k_source_lines0_long(const SrcBlock *__re
         }
     }
 }
+__global__ __launch_bounds__(256) void k_source_lines0_long(const SrcBlock *__restrict__ blk, double *__restrict__ U,
+                                                            const uint8_t *__restrict__ flags,
+                                                            const double *__restrict__ coeff,
+                                                            const uint8_t *__restrict__ dirm, Lay L, LinesArgs A,
+                                                            double *__restrict__ work)
+{
+    lines0_long(blk, U, flags, coeff, dirm, L, A, work);
+}
+__global__ __launch_bounds__(256) void k_source_lines0_long_slab(const SrcBlock *__restrict__ blk, double *__restrict__ U,
+                                                                 const uint8_t *__restrict__ flags,
+                                                                 const double *__restrict__ coeff,
+                                                                 const uint8_t *__restrict__ dirm, Lay L, LinesArgsSlab A,
+                                                                 double *__restrict__ work)
+{
+    lines0_long(blk, U, flags, coeff, dirm, L, A, work);
+}
 
 // One workgroup = KL adjacent lines along k x SEG segments of M rows; thread (kl, seg) owns rows [seg*M, seg*M + M) of line
 // kl, in registers.  Lanes kl of one segment are adjacent in memory, so every row load / store of a wave covers whole
 // 128-byte lines of U.  Rows past the end of the line are identity rows with s = 0.
-template <int M, int SEG>
-__global__ __launch_bounds__(512) void k_source_lines0(const SrcBlock *__restrict__ blk, double *__restrict__ U,
-                                                       const uint8_t *__restrict__ flags, const double *__restrict__ coeff,
-                                                       const uint8_t *__restrict__ dirm, Lay L, LinesArgs A)
+template <int M, int SEG, class AR>
+__device__ __forceinline__ void lines0_seg(const SrcBlock *__restrict__ blk, double *__restrict__ U,
+                                           const uint8_t *__restrict__ flags, const double *__restrict__ coeff,
+                                           const uint8_t *__restrict__ dirm, const Lay &L, const AR &A,
+                                           double (&sh)[4][SEG][512 / SEG])
 {
 #pragma clang fp contract(off)
     constexpr int KL = 512 / SEG;
-    __shared__ double sh[4][SEG][KL];
     const SrcBlock &B = *blk;            // (read in place: a local copy of the block would live in scratch)
     const adi_heat_source &s = B.s;
     const int kl = threadIdx.x % KL, seg = threadIdx.x / KL;
@@ -331,6 +360,59 @@ __global__ __launch_bounds__(512) void k_source_lines0(const SrcBlock *__restric
         }
     }
 }
+template <int M, int SEG>
+__global__ __launch_bounds__(512) void k_source_lines0(const SrcBlock *__restrict__ blk, double *__restrict__ U,
+                                                       const uint8_t *__restrict__ flags, const double *__restrict__ coeff,
+                                                       const uint8_t *__restrict__ dirm, Lay L, LinesArgs A)
+{
+    __shared__ double sh[4][SEG][512 / SEG];
+    lines0_seg<M, SEG>(blk, U, flags, coeff, dirm, L, A, sh);
+}
+template <int M, int SEG>
+__global__ __launch_bounds__(512) void k_source_lines0_slab(const SrcBlock *__restrict__ blk, double *__restrict__ U,
+                                                            const uint8_t *__restrict__ flags, const double *__restrict__ coeff,
+                                                            const uint8_t *__restrict__ dirm, Lay L, LinesArgsSlab A)
+{
+    __shared__ double sh[4][SEG][512 / SEG];
+    lines0_seg<M, SEG>(blk, U, flags, coeff, dirm, L, A, sh);
+}
+
+struct AddArgs {
+    double dx, scale;           // dx, dt/(rho cp)
+    int i_org, i_begin, i_end;  // global plane of local plane 0; the local planes [i_begin, i_end) to touch
+    int n0, nj, nk;             // planes of the launch box along axis 0 (at most i_end - i_begin), lines along axes 1 / 2
+};
+
+// R0 += dt*q(t_n + dt/2)/(rho cp) on the in-mask, non-Dirichlet cells of local planes [i_begin, i_end) inside the launch box,
+// one thread per cell of the box (lanes adjacent along k).  The box is placed from the block's mid-step centre as
+// lines0_line places it; along axis 0 it starts at the later of its first plane and i_begin.  Cells of the box outside the
+// support get q = 0 (goldak_q's cut) and are not written.
+__global__ __launch_bounds__(64) void k_source_add_r0(const SrcBlock *__restrict__ blk, double *__restrict__ R0,
+                                                      const uint8_t *__restrict__ flags, const uint8_t *__restrict__ dirm,
+                                                      Lay L, AddArgs A)
+{
+#pragma clang fp contract(off)
+    const SrcBlock &B = *blk;            // (read in place, as k_source_lines0 does)
+    const adi_heat_source &s = B.s;
+    const int kb = (int)(blockIdx.x * blockDim.x + threadIdx.x), jb = (int)blockIdx.y;
+    if (kb >= A.nk || jb >= A.nj) return;
+    double c[3];
+    src_centre(s, src_tmid(B), c);
+    const int j = src_box_first(s, c, 1, A.dx) + jb, k = src_box_first(s, c, 2, A.dx) + kb;
+    if (!(j >= 0 && j < L.ny && k >= 0 && k < L.nz)) return;
+    const int g0 = src_box_first(s, c, 0, A.dx) - A.i_org;
+    const int i_lo = g0 > A.i_begin ? g0 : A.i_begin;
+    const double yj = (j + 0.5) * A.dx, zk = (k + 0.5) * A.dx;
+    const long base = (long)j * L.nz + k;
+    for (int ib = (int)blockIdx.z; ib < A.n0; ib += (int)gridDim.z) {
+        const int i = i_lo + ib;
+        if (i >= A.i_end) return;
+        const long p = (long)i * L.sx + base;
+        if (!(flags[p] & 1u) || (dirm != nullptr && dirm[p])) continue;
+        const double q = goldak_q(s, c, ((A.i_org + i) + 0.5) * A.dx, yj, zk);
+        if (q != 0.0) R0[p] = R0[p] + A.scale * q;
+    }
+}
 
 static int check_source(const adi_heat_source *h, const char *fn)
 {
@@ -365,6 +447,78 @@ static void launch_lines0(dim3 grid, hipStream_t st, const SrcBlock *blk, double
                           const double *coeff, const uint8_t *dirm, const Lay &L, const LinesArgs &A)
 {
     hipLaunchKernelGGL((k_source_lines0<M, SEG>), grid, dim3(512), 0, st, blk, U, flags, coeff, dirm, L, A);
+}
+template <int M, int SEG>
+static void launch_lines0(dim3 grid, hipStream_t st, const SrcBlock *blk, double *U, const uint8_t *flags,
+                          const double *coeff, const uint8_t *dirm, const Lay &L, const LinesArgsSlab &A)
+{
+    hipLaunchKernelGGL((k_source_lines0_slab<M, SEG>), grid, dim3(512), 0, st, blk, U, flags, coeff, dirm, L, A);
+}
+static void launch_lines0_long(dim3 grid, hipStream_t st, const SrcBlock *blk, double *U, const uint8_t *flags,
+                               const double *coeff, const uint8_t *dirm, const Lay &L, const LinesArgs &A, double *work)
+{
+    hipLaunchKernelGGL(k_source_lines0_long, grid, dim3(64), 0, st, blk, U, flags, coeff, dirm, L, A, work);
+}
+static void launch_lines0_long(dim3 grid, hipStream_t st, const SrcBlock *blk, double *U, const uint8_t *flags,
+                               const double *coeff, const uint8_t *dirm, const Lay &L, const LinesArgsSlab &A, double *work)
+{
+    hipLaunchKernelGGL(k_source_lines0_long_slab, grid, dim3(64), 0, st, blk, U, flags, coeff, dirm, L, A, work);
+}
+
+// the in-register kernel for lines of nx <= kMaxFastLine rows: SEG segments of M rows
+template <class AR>
+static void launch_lines0_box(int nx, hipStream_t st, const SrcBlock *blk, double *U, const uint8_t *flags,
+                              const double *coeff, const uint8_t *dirm, const Lay &L, const AR &A)
+{
+    const dim3 g16((unsigned)((A.nk + 15) / 16), (unsigned)A.nj), g8((unsigned)((A.nk + 7) / 8), (unsigned)A.nj);
+    if (nx <= 128) launch_lines0<4, 32>(g16, st, blk, U, flags, coeff, dirm, L, A);
+    else if (nx <= 256) launch_lines0<8, 32>(g16, st, blk, U, flags, coeff, dirm, L, A);
+    else if (nx <= 512) launch_lines0<16, 32>(g16, st, blk, U, flags, coeff, dirm, L, A);
+    else launch_lines0<16, 64>(g8, st, blk, U, flags, coeff, dirm, L, A);
+}
+
+// adi_source_lines0 / adi_source_lines0_slab (fn: the entry point's name for the messages; slab: the kernels that take the
+// plane origin -- with slab = false the single-domain kernels, whose arguments and code are those without it)
+static int source_lines0(const void *d_block, const adi_heat_source *h_src, double *d_U, const uint8_t *d_flags,
+                         const double *d_coeff, const uint8_t *d_dir_mask, int nx, int ny, int nz, long plane_stride,
+                         int i_org, int sparse, double dx, double theta, double gam, double dt, double rho, double cp,
+                         const double *h_face_consts, void *d_work, size_t work_bytes, void *stream, bool slab,
+                         const char *fn)
+{
+    if (int rc = check_source(h_src, fn)) return rc;
+    ADI_REQUIRE(d_block && d_U && d_flags, "%s: null argument", fn);
+    const bool fconst = h_face_consts != nullptr && (sparse & 1);
+    ADI_REQUIRE(fconst || d_coeff, "%s: no coefficient array and no face constants", fn);
+    const double sc[] = {dx, theta, gam, dt, rho, cp};
+    for (double x : sc) ADI_REQUIRE(std::isfinite(x), "%s: non-finite scalar", fn);
+    ADI_REQUIRE(dx > 0.0 && dt > 0.0 && rho > 0.0 && cp > 0.0 && gam >= 0.0 && theta >= 0.0,
+                "%s: bad dx / dt / rho / cp / gam / theta", fn);
+    ADI_REQUIRE(i_org >= 0, "%s: plane origin < 0", fn);
+    Lay L;
+    if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
+    LinesArgsSlab A;
+    A.tg = theta * gam; A.dt = dt; A.dx = dx; A.scale = dt / (rho * cp);
+    A.fconst = fconst ? 1 : 0; A.sparse = (sparse & 1) ? 1 : 0;
+    A.fc0 = fconst ? h_face_consts[0] : 0.0; A.fc1 = fconst ? h_face_consts[1] : 0.0;
+    A.i_org = i_org;
+    lines0_box(*h_src, ny, nz, dx, A.nj, A.nk);
+    const SrcBlock *blk = (const SrcBlock *)d_block;
+    hipStream_t st = as_stream(stream);
+    if (nx > kMaxFastLine) {
+        const size_t need = 2 * sizeof(double) * (size_t)nx * (size_t)A.nj * (size_t)A.nk;
+        ADI_REQUIRE(d_work && work_bytes >= need, "%s: lines of %d rows need %zu bytes of workspace "
+                    "(adi_source_workspace_bytes), got %zu", fn, nx, need, d_work ? work_bytes : (size_t)0);
+        if (slab) launch_lines0_long(dim3((unsigned)((A.nk + 63) / 64), (unsigned)A.nj), st, blk, d_U, d_flags, d_coeff,
+                                     d_dir_mask, L, A, (double *)d_work);
+        else launch_lines0_long(dim3((unsigned)((A.nk + 63) / 64), (unsigned)A.nj), st, blk, d_U, d_flags, d_coeff,
+                                d_dir_mask, L, (const LinesArgs &)A, (double *)d_work);
+    } else if (slab) {
+        launch_lines0_box(nx, st, blk, d_U, d_flags, d_coeff, d_dir_mask, L, A);
+    } else {
+        launch_lines0_box(nx, st, blk, d_U, d_flags, d_coeff, d_dir_mask, L, (const LinesArgs &)A);
+    }
+    ADI_CHECK_LAUNCH();
+    return ADI_OK;
 }
 
 }  // namespace adi
@@ -425,38 +579,46 @@ int adi_source_lines0(const void *d_block, const adi_heat_source *h_src, double 
                       int sparse, double dx, double theta, double gam, double dt, double rho, double cp,
                       const double *h_face_consts, void *d_work, size_t work_bytes, void *stream)
 {
-    if (int rc = check_source(h_src, "adi_source_lines0")) return rc;
-    ADI_REQUIRE(d_block && d_U && d_flags, "adi_source_lines0: null argument");
-    const bool fconst = h_face_consts != nullptr && (sparse & 1);
-    ADI_REQUIRE(fconst || d_coeff, "adi_source_lines0: no coefficient array and no face constants");
-    const double sc[] = {dx, theta, gam, dt, rho, cp};
-    for (double x : sc) ADI_REQUIRE(std::isfinite(x), "adi_source_lines0: non-finite scalar");
-    ADI_REQUIRE(dx > 0.0 && dt > 0.0 && rho > 0.0 && cp > 0.0 && gam >= 0.0 && theta >= 0.0,
-                "adi_source_lines0: bad dx / dt / rho / cp / gam / theta");
+    return source_lines0(d_block, h_src, d_U, d_flags, d_coeff, d_dir_mask, nx, ny, nz, plane_stride, 0, sparse, dx, theta,
+                         gam, dt, rho, cp, h_face_consts, d_work, work_bytes, stream, false, "adi_source_lines0");
+}
+
+int adi_source_lines0_slab(const void *d_block, const adi_heat_source *h_src, double *d_U, const uint8_t *d_flags,
+                           const double *d_coeff, const uint8_t *d_dir_mask, int nx, int ny, int nz, long plane_stride,
+                           int i_org, int sparse, double dx, double theta, double gam, double dt, double rho, double cp,
+                           const double *h_face_consts, void *d_work, size_t work_bytes, void *stream)
+{
+    return source_lines0(d_block, h_src, d_U, d_flags, d_coeff, d_dir_mask, nx, ny, nz, plane_stride, i_org, sparse, dx,
+                         theta, gam, dt, rho, cp, h_face_consts, d_work, work_bytes, stream, true,
+                         "adi_source_lines0_slab");
+}
+
+int adi_source_add_r0(const void *d_block, const adi_heat_source *h_src, double *d_R0, const uint8_t *d_flags,
+                      const uint8_t *d_dir_mask, int nx, int ny, int nz, long plane_stride, int i_org, int i_begin,
+                      int i_end, double dx, double dt, double rho, double cp, void *stream)
+{
+    if (int rc = check_source(h_src, "adi_source_add_r0")) return rc;
+    ADI_REQUIRE(d_block && d_R0 && d_flags, "adi_source_add_r0: null argument");
+    const double sc[] = {dx, dt, rho, cp};
+    for (double x : sc) ADI_REQUIRE(std::isfinite(x), "adi_source_add_r0: non-finite scalar");
+    ADI_REQUIRE(dx > 0.0 && dt > 0.0 && rho > 0.0 && cp > 0.0, "adi_source_add_r0: bad dx / dt / rho / cp");
     Lay L;
     if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
-    LinesArgs A;
-    A.tg = theta * gam; A.dt = dt; A.dx = dx; A.scale = dt / (rho * cp);
-    A.fconst = fconst ? 1 : 0; A.sparse = (sparse & 1) ? 1 : 0;
-    A.fc0 = fconst ? h_face_consts[0] : 0.0; A.fc1 = fconst ? h_face_consts[1] : 0.0;
+    ADI_REQUIRE(i_org >= 0, "adi_source_add_r0: plane origin < 0");
+    ADI_REQUIRE(i_begin >= 0 && i_begin <= i_end && i_end <= nx, "adi_source_add_r0: planes [%d, %d) outside [0, %d]",
+                i_begin, i_end, nx);
+    if (i_begin == i_end) return ADI_OK;
+    AddArgs A;
+    A.dx = dx; A.scale = dt / (rho * cp);
+    A.i_org = i_org; A.i_begin = i_begin; A.i_end = i_end;
+    double lo, hi;
+    src_extent(*h_src, 0, lo, hi);
+    const double n0 = floor((lo + hi) / dx) + 4.0;          // src_box_lines along axis 0, in double: no int overflow
+    A.n0 = n0 < (double)(i_end - i_begin) ? (int)n0 : i_end - i_begin;
     lines0_box(*h_src, ny, nz, dx, A.nj, A.nk);
-    const SrcBlock *blk = (const SrcBlock *)d_block;
-    hipStream_t st = as_stream(stream);
-    if (nx > kMaxFastLine) {
-        const size_t need = 2 * sizeof(double) * (size_t)nx * (size_t)A.nj * (size_t)A.nk;
-        ADI_REQUIRE(d_work && work_bytes >= need, "adi_source_lines0: lines of %d rows need %zu bytes of workspace "
-                    "(adi_source_workspace_bytes), got %zu", nx, need, d_work ? work_bytes : (size_t)0);
-        hipLaunchKernelGGL(k_source_lines0_long, dim3((unsigned)((A.nk + 63) / 64), (unsigned)A.nj), dim3(64), 0, st, blk,
-                           d_U, d_flags, d_coeff, d_dir_mask, L, A, (double *)d_work);
-    } else if (nx <= 128) {
-        launch_lines0<4, 32>(dim3((unsigned)((A.nk + 15) / 16), (unsigned)A.nj), st, blk, d_U, d_flags, d_coeff, d_dir_mask, L, A);
-    } else if (nx <= 256) {
-        launch_lines0<8, 32>(dim3((unsigned)((A.nk + 15) / 16), (unsigned)A.nj), st, blk, d_U, d_flags, d_coeff, d_dir_mask, L, A);
-    } else if (nx <= 512) {
-        launch_lines0<16, 32>(dim3((unsigned)((A.nk + 15) / 16), (unsigned)A.nj), st, blk, d_U, d_flags, d_coeff, d_dir_mask, L, A);
-    } else {
-        launch_lines0<16, 64>(dim3((unsigned)((A.nk + 7) / 8), (unsigned)A.nj), st, blk, d_U, d_flags, d_coeff, d_dir_mask, L, A);
-    }
+    const unsigned gz = (unsigned)(A.n0 < 65535 ? A.n0 : 65535);
+    hipLaunchKernelGGL(k_source_add_r0, dim3((unsigned)((A.nk + 63) / 64), (unsigned)A.nj, gz), dim3(64), 0,
+                       as_stream(stream), (const SrcBlock *)d_block, d_R0, d_flags, d_dir_mask, L, A);
     ADI_CHECK_LAUNCH();
     return ADI_OK;
 }

@@ -675,6 +675,37 @@ class HipEngine:
         self.check(self.lib.adi_interface_pair(h._p(my_lo), h._p(my_hi), h._p(prev_hi), h._p(next_lo), nlines,
                                                h._p(xlo), h._p(xhi), self._sp()))
 
+    # moving heat source (include/adi_hip.h, "Volumetric heat source"): one device block and one workspace per rank
+    def source_set(self, src, t, dt):
+        """the block of this rank: `src` (a GoldakSource) for the step that starts at t"""
+        if getattr(self, '_src_block', None) is None:
+            self._src_block = torch.zeros(self._lib.SOURCE_BLOCK_BYTES, dtype=torch.uint8, device=self.device)
+        self.check(self.lib.adi_source_set(self.hip._p(self._src_block), ctypes.byref(src.as_c()), float(t), float(dt), 0,
+                                           self._sp()))
+
+    def source_lines0(self, src, Li, U, flags, pack, dx, theta, gam, dt, rho, cp, i_org):
+        """U += A0^-1 s on the slab's axis-0 lines with zero values beyond both ends (the deferred forms' local solve)"""
+        h = self.hip
+        b = ctypes.c_size_t(0)
+        self.check(self.lib.adi_source_workspace_bytes(ctypes.byref(src.as_c()), Li.nx, Li.ny, Li.nz, dx,
+                                                       ctypes.byref(b)))
+        work = None
+        if b.value:
+            work = getattr(self, '_src_work', None)
+            if work is None or work.numel() < b.value:
+                work = self._src_work = torch.empty(b.value, dtype=torch.uint8, device=self.device)
+        self.check(self.lib.adi_source_lines0_slab(h._p(self._src_block), ctypes.byref(src.as_c()), h._p(U), h._p(flags),
+                                                   h._p(pack[0]), h._p(pack[1]), Li.nx, Li.ny, Li.nz, Li.sx, int(i_org),
+                                                   1 | self.box_hint, dx, theta, gam, dt, rho, cp, self._fc(pack),
+                                                   h._p(work), 0 if work is None else work.numel(), self._sp()))
+
+    def source_add_r0(self, src, Li, R0, flags, dir_mask, i_org, i_begin, i_end, dx, dt, rho, cp):
+        """R0 += dt*q/(rho cp) on local planes [i_begin, i_end) of the slab (in-mask, non-Dirichlet cells)"""
+        h = self.hip
+        self.check(self.lib.adi_source_add_r0(h._p(self._src_block), ctypes.byref(src.as_c()), h._p(R0), h._p(flags),
+                                              h._p(dir_mask), Li.nx, Li.ny, Li.nz, Li.sx, int(i_org), int(i_begin), int(i_end),
+                                              dx, dt, rho, cp, self._sp()))
+
 
 def _interior(t_ext):
     """planes 1..n-2 of an extended array: same strides, pointer advanced by one plane"""
@@ -688,7 +719,7 @@ class SlabStepper:
     _comm_priority = -1           # the side stream is a high-priority one: a HSA queue of its own (see rccl_env_defaults)
 
     def __init__(self, mask_local, dx, mat, params, Tinf=0.0, dir_mask=None, dir_value=None, neumann=None,
-                 robin_h=None, comm=None, engine=None):
+                 robin_h=None, comm=None, engine=None, source=None):
         self.engine = engine or HipEngine()
         self.comm = comm or TorchDistComm()
         self.rank, self.world = self.comm.rank, self.comm.world
@@ -731,6 +762,8 @@ class SlabStepper:
         self._comm_stream, self._use_streams = None, False
         self._halo_ready, self._halo_event = None, None
         self._gam = 0.0
+        self.source, self._i_org = None, None
+        self.set_source(source)
         self.set_mask(mask_local)
 
     def _pad(self, a, fill=0):
@@ -806,6 +839,42 @@ class SlabStepper:
             return tuple(None if t is None else _interior(t) for t in (p.d_coeff, p.d_dir_mask, p.d_dir_val, p.d_qflux))
         self.packs_int = [interior_pack(p) for p in self.packs_ext]
         self.flags_int = _interior(self.flags_ext)
+
+    def set_source(self, src):
+        """Attach a moving heat source (an adi3d_hip_coeff.GoldakSource; its origin in global coordinates, cell centres at
+        ((i0 + i + 1/2) dx, (j + 1/2) dx, (k + 1/2) dx) for local plane i of the slab that starts at global plane i0) or detach
+        it (None).  Every rank attaches and detaches the same source at the same step: the plan depends on it (collective).
+        Then step() needs t, the step's start time; the source is evaluated at t + dt/2."""
+        if src is not None:
+            from .adi3d_hip_coeff import GoldakSource
+            if not isinstance(src, GoldakSource):
+                raise TypeError("SlabStepper: source must be a GoldakSource or None, not %s" % type(src).__name__)
+            if not all(hasattr(self.engine, m) for m in ('source_set', 'source_lines0', 'source_add_r0')):
+                raise NotImplementedError("SlabStepper: the engine %s has no heat-source kernels" % type(self.engine).__name__)
+            src.validate()
+        if (src is None) != (self.source is None):
+            self._plan_steps = None                # attaching / detaching is no mask event: the next plan is a full one
+        self.source = src
+
+    def _plane_origin(self):
+        """global plane of this rank's local plane 0 (collective the first time: the slab sizes of all ranks)"""
+        if self._i_org is None:
+            self._i_org = 0 if self.world == 1 else int(sum(self._slab_planes_of_all_ranks()[:self.rank]))
+        return self._i_org
+
+    def _source_meets(self, src, t, dt, i_org):
+        """whether the support can meet this rank's planes at t + dt/2: the kernels' extent along axis 0 (src_extent), widened by
+        one plane each side"""
+        from ._lib import SOURCE_E_CUT
+        R = np.sqrt(SOURCE_E_CUT / 3.0)
+        if src.travel_axis == 0:
+            lo, hi = (R * src.c_r, R * src.c_f) if src.travel_sign > 0 else (R * src.c_f, R * src.c_r)
+        else:
+            lo = hi = R * (src.b if src.depth_axis == 0 else src.a)
+        c0 = float(src.center(float(t) + 0.5 * float(dt))[0])
+        g_first = np.ceil((c0 - lo) / self.dx - 0.5) - 1.0
+        g_last = np.floor((c0 + hi) / self.dx - 0.5) + 1.0
+        return bool(g_last >= i_org and g_first <= i_org + self.nxl - 1)
 
     def _scalar_specs(self):
         """(h_mode, h_scalar, q_mode, q_scalar) ctypes arrays when every face specification is a scalar or absent, else None"""
@@ -970,7 +1039,8 @@ class SlabStepper:
         prm = self.params
         key = (float(prm.dt), float(prm.theta), self._mask_version, self._force_exact, self._no_overlap,
                self._allow_fused, self._allow_window, self._keep_r0, self._allow_dots, self._allow_deferred,
-               self._allow_deferred_exact, self._allow_deferred_lines, self._deferred_lines_cost_ratio, self._allow_quick_replan)
+               self._allow_deferred_exact, self._allow_deferred_lines, self._deferred_lines_cost_ratio, self._allow_quick_replan,
+               self.source is not None)
         if self._a0_key == key:
             self._plan_steps += 1
             return self._a0
@@ -982,8 +1052,9 @@ class SlabStepper:
         self._streams()
         nl, fl, pk = self.nlines, self.flags_int, self.packs_int[0]
         first, last = self.rank == 0, self.rank == self.world - 1
+        src_on = self.source is not None
         if short_lived and self._allow_quick_replan:
-            plan = self._quick_plan(gam)
+            plan = self._quick_plan(gam, src_on)
             if plan is not None:
                 self._a0_key, self._a0 = key, plan
                 self.axis0_mode = plan['mode']
@@ -1091,7 +1162,9 @@ class SlabStepper:
         allf = E.vec(self.world)
         if plan is None:
             plan = dict(mode='exact', K=self.nxl)
-        plan['fused'] = self._fused_supported(plan['K'])     # the same on every rank (it depends on sizes only...
+        # with a source these forms add it to R0 (step: `ex`), so every pass that reads R0 must read the stored one: no fused
+        # passes (they evaluate the explicit stage themselves) and no dot products (accumulated while R0 is written)
+        plan['fused'] = self._fused_supported(plan['K']) and not src_on     # the same on every rank (sizes only...
         if self.world > 1:                                   # ...but slabs may differ by two planes: make it collective)
             flag.fill_(1.0 if plan['fused'] else 0.0)
             self.comm.all_gather(allf, flag)
@@ -1101,7 +1174,7 @@ class SlabStepper:
         plan['keep_r0'] = bool(plan['fused'] and plan['mode'] != 'window' and self._keep_r0)
         # whole-slab pass A without a second read of the slab: the marching explicit kernel accumulates the dot products
         # pass A needs while it writes R0 (uniform lines; the others are condensed from R0); pass B is the plain sweep
-        dots = bool(self._allow_dots and plan['mode'] != 'window' and hasattr(E, 'dots_setup')
+        dots = bool(self._allow_dots and not src_on and plan['mode'] != 'window' and hasattr(E, 'dots_setup')
                     and E.dots_supported(self.nxl, self.ny, self.nz, self.Lint.sx))
         flag.fill_(1.0 if dots else 0.0)
         self.comm.all_gather(allf, flag)
@@ -1146,7 +1219,8 @@ class SlabStepper:
             bufs.append(b)
         plan['chunks'] = bufs
         if plan['mode'] != 'window':
-            self._dots_sticky = bool(plan['dots'])          # (a re-plan of a short-lived plan keeps this decision, _quick_plan)
+            # (with a source the dot products are off for another reason: a decision already made is kept for later plans)
+            self._dots_sticky = bool(plan['dots']) if not src_on or self._dots_sticky is None else self._dots_sticky          # (a re-plan of a short-lived plan keeps this decision, _quick_plan)
         self._a0_key, self._a0 = key, plan
         self.axis0_mode = plan['mode']
         return plan
@@ -1184,9 +1258,10 @@ class SlabStepper:
             self._fused_by_K[K] = bool(float(allf.min()) >= 1.0)
         return self._fused_by_K[K]
 
-    def _quick_plan(self, gam):
+    def _quick_plan(self, gam, src_on=False):
         """plan for the current (dt, theta, mask) without a host synchronisation, or None (no full plan has been made yet, or
-        the slab is an all-solid box: the deferred forms need the full planner)"""
+        the slab is an all-solid box: the deferred forms need the full planner).  src_on: a source is attached (no fused
+        passes, no dot products: see _plan_axis0)"""
         E, prm = self.engine, self.params
         if self._dots_sticky is None or getattr(self, '_solid_everywhere', False) or getattr(E, 'box_hint', 0) == 2:
             return None
@@ -1203,9 +1278,9 @@ class SlabStepper:
         plan = dict(mode=mode, K=K, quick=True)
         if mode != 'exact':
             plan.update(Lw=E.layout(K, self.ny, self.nz, self.Lint.sx), worst=None)
-        plan['fused'] = self._fused_collective(K)
+        plan['fused'] = self._fused_collective(K) and not src_on
         plan['keep_r0'] = bool(plan['fused'] and mode != 'window' and self._keep_r0)
-        plan['dots'] = bool(self._dots_sticky and self._allow_dots and mode != 'window' and hasattr(E, 'dots_setup')
+        plan['dots'] = bool(self._dots_sticky and self._allow_dots and not src_on and mode != 'window' and hasattr(E, 'dots_setup')
                             and E.dots_supported(self.nxl, self.ny, self.nz, self.Lint.sx))
         if plan['dots']:
             plan['dd'] = E.dots_setup(self.Lint, self.flags_int, self.packs_int[0][1], prm.theta, gam)
@@ -1431,22 +1506,25 @@ class SlabStepper:
             self._no_overlap, self._force_exact = keep[:2]
         return err, not self._no_overlap
 
-    def step(self, T, events=None, prefetch_halo=False):
+    def step(self, T, events=None, prefetch_halo=False, t=None):
         """One ADI step of the local slab.  prefetch_halo=True promises that the returned field is passed to the
         next step() unmodified (an nsub loop).  Used by the 'window' form, whose step starts with the planes next
         to the halos: the boundary planes of the result are then computed first and sent to the neighbours while
         the rest of the last sweep runs.  (The other forms start with the planes that need no halo, which hides
-        the exchange just as well.)"""
+        the exchange just as well.)
+        t: the step's start time, required with a source attached (set_source), which is evaluated at t + dt/2."""
+        if self.source is not None and t is None:
+            raise ValueError("SlabStepper.step: a heat source is attached, so the step's start time t is required")
         E = self.engine
         if hasattr(E, '_stream_ptr'):
             E._stream_ptr = E.hip._stream()        # every kernel of this step goes to the stream that is current now
         try:
-            return self._step(T, events, prefetch_halo)
+            return self._step(T, events, prefetch_halo, t)
         finally:
             if hasattr(E, '_stream_ptr'):
                 E._stream_ptr = None
 
-    def _step(self, T, events, prefetch_halo):
+    def _step(self, T, events, prefetch_halo, t=None):
         E, prm, mat = self.engine, self.params, self.mat
         kappa = self._kappa = mat.k / (mat.rho * mat.cp)         # adi3d_numba_coeff.py:292
         gam = self._gam = kappa * prm.dt / (self.dx * self.dx)
@@ -1465,11 +1543,28 @@ class SlabStepper:
                 events[ne].record()
             ne += 1
         mark()
+        # moving source: superposition after the local sweep 0 where that sweep solves with zero boundary values (one rank,
+        # the deferred forms), otherwise added to R0 by every explicit-stage call; a rank the support cannot meet skips both
+        src = self.source
+        i_org = self._plane_origin() if src is not None else 0
+        src_here = src is not None and self._source_meets(src, t, prm.dt, i_org)
         plan = self._plan_axis0(_interior(Text), gam) if self.world > 1 else None
         fused = plan['fused'] if plan is not None else self._fused_supported(nl)
         streams = self._streams() and self.world > 1
         main = torch.cuda.current_stream() if streams else None
-        ex = lambda b, e: E.explicit(self.Lext, Text, self.flags_ext, self.dx, prm.dt, kappa, prm.theta, A, b, e)
+        src_r0 = src_here and plan is not None and not plan['mode'].startswith('deferred')
+        src_lines = src_here and not src_r0
+        if src_here:
+            E.source_set(src, t, prm.dt)
+
+        def ex(b, e):
+            E.explicit(self.Lext, Text, self.flags_ext, self.dx, prm.dt, kappa, prm.theta, A, b, e)
+            if src_r0:                                  # (extended planes [b, e) = local planes [b - 1, e - 1))
+                E.source_add_r0(src, Li, Ai, fl, self.packs_int[0][1], i_org, b - 1, e - 1, self.dx, prm.dt, mat.rho, mat.cp)
+
+        def src_lines0():
+            if src_lines:
+                E.source_lines0(src, Li, Bi, fl, self.packs_int[0], self.dx, prm.theta, gam, prm.dt, mat.rho, mat.cp, i_org)
 
         # 1. state halos (zeros outside the global grid are never read: the flags carry no coupling there)
         halo_ev = None
@@ -1508,6 +1603,7 @@ class SlabStepper:
                     ex(1, nl + 1)
                 mark()
                 E.sweep(0, v, Li, Ai, fl, self.packs_int[0], prm.theta, gam, prm.dt, self.Tinf, Bi)
+            src_lines0()                                      # before planes 0 and n-1 of Bi travel
             mark()
             if plan['mode'] == 'deferred_exact':
                 # no decay: all-gather of (plane 0, plane n-1) of x0 -- the right-hand sides of the interface system, whose matrix
@@ -1553,6 +1649,7 @@ class SlabStepper:
             # so they must have landed; in an nsub loop they were sent while the previous step's last sweep ran)
             if self.world == 1:
                 E.sweep0_fused(v, Li, Text, 1, 0, fl, self.packs_int[0], self.dx, prm.dt, kappa, prm.theta, self.Tinf, Bi)
+                src_lines0()
             else:
                 if halo_ev is not None and streams:
                     main.wait_event(halo_ev)
@@ -1562,6 +1659,7 @@ class SlabStepper:
             ex(1, nl + 1)
             mark()
             E.sweep(0, v, Li, Ai, fl, self.packs_int[0], prm.theta, gam, prm.dt, self.Tinf, Bi)
+            src_lines0()
         elif plan['dots']:
             # one pass over the slab: R0 and, per line, the two dot products of pass A (halos must have landed)
             # (running the explicit stage chunk by chunk of LINES, so that a chunk's interface exchange travels behind

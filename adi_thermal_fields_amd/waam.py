@@ -325,7 +325,7 @@ def run_layer_birth_slab(comm, i0, i1, mask_full, dx, mat, params_cls, h, Tinf, 
 
 
 def run_single_track_slab(comm, i0, i1, plate_mask, track_box, dx, mat, params_cls, h, Tinf, T_track, theta, dt, t_step,
-                          engine=None):
+                          engine=None, heat_source=None):
     """The moving deposit of single_track_on_plate.py:150-177 on ONE RANK of a slab decomposition (planes [i0, i1) of
     memory axis 0; BASELINE.json configs[4]: "layer-birth + moving source, 4 GPUs").  The track box spans planes
     [x0, x1) of the SHARDED axis, so a new column lands on every rank whose slab meets that range: those ranks switch
@@ -333,6 +333,8 @@ def run_single_track_slab(comm, i0, i1, plate_mask, track_box, dx, mat, params_c
     flags and packs for its slab -- SlabStepper.set_mask: mask halo exchange (a column next to a slab boundary changes the
     neighbour's halo coupling bits), flags, packs (:163) -- and takes the n_sub sub-steps of the column (:168-176).
     Every rank keeps the full host mask for bookkeeping (1 bit of information per cell), as run_layer_birth_slab does.
+    heat_source (a GoldakSource): the arc / laser of run_single_track (track_source, global coordinates) during the sub-steps of
+    every column, sub-step i at t = i * dt_sub from the column's start.  None: the loop without it, unchanged.
     Returns the local field as NumPy."""
     from . import dist_slab
     x0, x1, z0, z1, ncol = track_box
@@ -365,7 +367,12 @@ def run_single_track_slab(comm, i0, i1, plate_mask, track_box, dx, mat, params_c
                 T = Tl
         n_sub = max(1, int(math.ceil(t_step / dt)))
         params.dt = t_step / n_sub
-        for s_ in range(n_sub):
-            T = st.step(T, prefetch_halo=(s_ + 1 < n_sub))
+        if heat_source is None:
+            for s_ in range(n_sub):
+                T = st.step(T, prefetch_halo=(s_ + 1 < n_sub))
+        else:
+            st.set_source(track_source(heat_source, track_box, dx, yi, t_step))
+            for s_ in range(n_sub):
+                T = st.step(T, prefetch_halo=(s_ + 1 < n_sub), t=s_ * params.dt)
         params.dt = dt
     return np.array(st.local_numpy(T))

@@ -527,6 +527,23 @@ int adi_source_lines0(const void *d_block, const adi_heat_source *h_src, double 
                       const double *d_coeff, const uint8_t *d_dir_mask, int nx, int ny, int nz, long plane_stride,
                       int sparse, double dx, double theta, double gam, double dt, double rho, double cp,
                       const double *h_face_consts, void *d_work, size_t work_bytes, void *stream);
+/* The same on one slab of a grid cut along axis 0: the box (nx, ny, nz) is the slab, whose local plane i lies at global plane
+ * i_org + i (cell centre (i_org + i + 1/2) dx; i_org = 0 is adi_source_lines0).  Every line is solved over the slab's rows
+ * only, with ZERO values beyond its ends: the coupling bits of rows 0 and nx-1 to the halo planes (d_flags of a slab) enter
+ * the diagonal as in adi_sweep(axis 0) without d_xlo / d_xhi, and their off-diagonal entries multiply zeros.  That is the
+ * local solve of the deferred forms of the sharded-axis sweep, whose interface step then carries w to the other slabs. */
+int adi_source_lines0_slab(const void *d_block, const adi_heat_source *h_src, double *d_U, const uint8_t *d_flags,
+                           const double *d_coeff, const uint8_t *d_dir_mask, int nx, int ny, int nz, long plane_stride,
+                           int i_org, int sparse, double dx, double theta, double gam, double dt, double rho, double cp,
+                           const double *h_face_consts, void *d_work, size_t work_bytes, void *stream);
+/* The source term itself, added to R0: d_R0 += dt*q(t_n + dt/2)/(rho*cp) on the in-mask cells of local planes
+ * [i_begin, i_end) of the box that are not Dirichlet cells (d_dir_mask may be NULL), q from the block's centre and the cell
+ * centres ((i_org + i + 1/2) dx, (j + 1/2) dx, (k + 1/2) dx).  One thread per cell of the support's launch box, placed on the
+ * device from the block; nothing else is touched.  0 <= i_begin <= i_end <= nx, i_org >= 0.  For the slab forms that need the
+ * whole right-hand side before the sweep (their condensation reads R0). */
+int adi_source_add_r0(const void *d_block, const adi_heat_source *h_src, double *d_R0, const uint8_t *d_flags,
+                      const uint8_t *d_dir_mask, int nx, int ny, int nz, long plane_stride, int i_org, int i_begin,
+                      int i_end, double dx, double dt, double rho, double cp, void *stream);
 /* adi_explicit_rhs with a source FIELD d_S [W/m^3] (box layout): R0 += dt*S/(rho*cp) on in-mask cells */
 int adi_explicit_rhs_src(const double *d_T, const double *d_S, const uint8_t *d_flags, int nx, int ny, int nz,
                          long plane_stride, double dx, double dt, double kappa, double theta, double rho, double cp,
