@@ -148,6 +148,11 @@ SIGNATURES = {
     'adi_source_workspace_bytes': (c_int, [c_void_p, c_int, c_int, c_int, c_double, ctypes.POINTER(c_size_t)]),
     'adi_explicit_rhs_src': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double,
                                      c_double, c_double, c_double, c_void_p, c_void_p]),
+    'adi_cyl_source_set': (c_int, [c_void_p, c_void_p, c_double, c_double, ctypes.c_longlong, c_void_p]),
+    'adi_cyl_source_sample': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double, c_double,
+                                      c_void_p, c_void_p, c_void_p]),
+    'adi_cyl_step_src': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p]),
+    'adi_cyl_sweep_src': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p]),
     'adi_ctx_create': (c_int, [c_int, c_int, c_int, c_double, c_int, c_void_pp]),
     'adi_ctx_destroy': (c_int, [c_void_p]),
     'adi_ctx_set_mask': (c_int, [c_void_p, c_void_p]),
@@ -170,6 +175,16 @@ class HeatSource(ctypes.Structure):
     _fields_ = [('power', c_double), ('eta', c_double), ('a', c_double), ('b', c_double), ('c_f', c_double),
                 ('c_r', c_double), ('f_f', c_double), ('origin', c_double * 3), ('velocity', c_double),
                 ('travel_axis', c_int), ('travel_sign', c_int), ('depth_axis', c_int), ('reserved', c_int)]
+
+
+CYL_DEPTHS = {'z': 0, 'r': 1}   # ADI_CYL_DEPTH_Z, ADI_CYL_DEPTH_R
+
+
+class CylHeatSource(ctypes.Structure):
+    """adi_cyl_heat_source (include/adi_hip.h)"""
+    _fields_ = [('power', c_double), ('eta', c_double), ('a', c_double), ('b', c_double), ('c_f', c_double),
+                ('c_r', c_double), ('f_f', c_double), ('r_c', c_double), ('phi0', c_double), ('omega', c_double),
+                ('z0', c_double), ('v_z', c_double), ('depth', c_int), ('reserved', c_int)]
 
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import lib, check
 from .adi3d_hip_coeff import DeviceField, Layout, to_device, _device, _stream, _p, _wrap
 
-__all__ = ['StagedCylStepper', 'GridCyl', 'Material', 'Params', 'RobinR', 'ZBC', 'adi_step', 'adi_step_masked', 'DeviceField', 'to_device']
+__all__ = ['StagedCylStepper', 'CylGoldakSource', 'GridCyl', 'Material', 'Params', 'RobinR', 'ZBC', 'adi_step', 'adi_step_masked', 'DeviceField', 'to_device']
 
 
 class GridCyl:  # adi3d_cyl_phi_v3.py:33-43
@@ -75,6 +75,109 @@ class ZBC:  # :60-68
         self.T_bot = float(T_bot); self.T_top = float(T_top)
 
 
+class CylGoldakSource:
+    """Goldak's double ellipsoid riding on the cylindrical grid, for the `S=` argument of adi_step / adi_step_masked and the
+    `source=` argument of StagedCylStepper (include/adi_hip.h, "Moving heat source of the cylindrical step").
+    power P [W], efficiency eta, a (transverse half-width), b (depth), c_f / c_r (front / rear length) [m], front fraction
+    f_f (f_r = 2 - f_f).  The centre at time t is at radius r_c, angle phi0 + omega t (omega signed, rad/s) and height
+    z0 + v_z t (from the bottom face; v_z = pitch |omega| / 2 pi: a helix, 0: a ring).  Offsets are Cartesian in the frame
+    (tangent, radial, axial) at the centre, with delta = phi - phi_c and s = sign(omega) (+1 for 0):
+        xi = s r sin(delta),  rho = r cos(delta) - r_c,  zeta = z - z_c
+    depth='z' (the arc on top of a wall): E = 3 xi^2/c^2 + 3 rho^2/a^2 + 3 zeta^2/b^2; depth='r' (cladding on a cylinder
+    face) swaps rho and zeta.  q = 6 sqrt(3) f eta P / (a b c pi^1.5) exp(-E) with (f, c) = (f_f, c_f) where xi >= 0, else
+    (f_r, c_r); q = 0 where E > E_CUT = 40.  The ellipsoid is rigid: q integrates to 2 eta P over all space, to eta P over
+    the half-space on one side of the centre plane normal to the depth axis.
+    power, eta, f_f, r_c, phi0, omega, z0 and v_z may change between the runs of a StagedCylStepper without a new graph."""
+    E_CUT = _lib.SOURCE_E_CUT
+
+    def __init__(self, power, eta, a, b, c_f, c_r, f_f=0.6, *, r_c, phi0=0.0, omega=0.0, z0, v_z=0.0, depth='z'):
+        self.power, self.eta, self.a, self.b, self.c_f, self.c_r, self.f_f = power, eta, a, b, c_f, c_r, f_f
+        self.r_c, self.phi0, self.omega, self.z0, self.v_z, self.depth = r_c, phi0, omega, z0, v_z, depth
+        self.validate()
+
+    def validate(self):
+        """ValueError for any parameter adi_cyl_heat_source rejects (include/adi_hip.h); returns the twelve numbers"""
+        try:
+            vals = [float(v) for v in (self.power, self.eta, self.a, self.b, self.c_f, self.c_r, self.f_f, self.r_c,
+                                       self.phi0, self.omega, self.z0, self.v_z)]
+        except (TypeError, ValueError):
+            raise ValueError("CylGoldakSource: parameters must be real numbers")
+        if not all(np.isfinite(v) for v in vals):
+            raise ValueError("CylGoldakSource: non-finite source parameter")
+        P, eta, a, b, cf, cr, ff, rc = vals[:8]
+        if P < 0:
+            raise ValueError("CylGoldakSource: power < 0")
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError("CylGoldakSource: eta outside [0, 1]")
+        if min(a, b, cf, cr) <= 0:
+            raise ValueError("CylGoldakSource: non-positive length")
+        if not 0.0 < ff < 2.0:
+            raise ValueError("CylGoldakSource: f_f outside (0, 2)")
+        if rc < 0:
+            raise ValueError("CylGoldakSource: r_c < 0")
+        if not isinstance(self.depth, str) or self.depth not in _lib.CYL_DEPTHS:
+            raise ValueError("CylGoldakSource: depth must be 'z' (0) or 'r' (1)")
+        return vals
+
+    def as_c(self):
+        v = self.validate()
+        return _lib.CylHeatSource(*v, _lib.CYL_DEPTHS[self.depth], 0)
+
+    def shape_key(self):
+        """the support's shape (a change recaptures a stepper's graph)"""
+        return (float(self.a), float(self.b), float(self.c_f), float(self.c_r), self.depth)
+
+    def center(self, t):
+        """(r_c, phi_c, z_c) at time t"""
+        return (float(self.r_c), float(self.phi0) + float(self.omega) * float(t), float(self.z0) + float(self.v_z) * float(t))
+
+    def q(self, r, phi, z, t):
+        """q [W/m^3] at points (broadcast NumPy arrays: radius, angle, height) -- the host evaluator, the kernels' expression"""
+        P, eta, a, b, cf, cr, ff, rc = self.validate()[:8]
+        _, phic, zc = self.center(t)
+        r, phi, z = (np.asarray(v, dtype=np.float64) for v in (r, phi, z))
+        delta = phi - phic
+        sgn = -1.0 if float(self.omega) < 0.0 else 1.0
+        xi = sgn * (r * np.sin(delta))
+        rho = r * np.cos(delta) - rc
+        zeta = z - zc
+        lrad, lax = (a, b) if self.depth == 'z' else (b, a)
+        front = xi >= 0.0
+        f = np.where(front, ff, 2.0 - ff)
+        cl = np.where(front, cf, cr)
+        E = (3.0 * (xi * xi) / (cl * cl) + 3.0 * (rho * rho) / (lrad * lrad)) + 3.0 * (zeta * zeta) / (lax * lax)
+        amp = (6.0 * np.sqrt(3.0) * f * eta * P) / (a * b * cl * np.pi ** 1.5)
+        with np.errstate(under='ignore'):
+            return np.where(E <= self.E_CUT, amp * np.exp(-np.minimum(E, 745.0)), 0.0)
+
+    def sample(self, grid, t, active=None):
+        """q at the cell centres (r_i, (j+1/2) dphi, (k+1/2) dz) at time t: float64 array (nr, nphi, nz), 0 where `active`
+        is False (NumPy: the ground truth the tests hold the kernels to)"""
+        phi = (np.arange(grid.nphi, dtype=np.float64) + 0.5) * grid.dphi
+        z = (np.arange(grid.nz, dtype=np.float64) + 0.5) * grid.dz
+        q = np.broadcast_to(self.q(np.asarray(grid.r)[:, None, None], phi[None, :, None], z[None, None, :], t), grid.shape)
+        return np.array(q) if active is None else np.where(np.asarray(active, dtype=bool), q, 0.0)
+
+    def sample_device(self, grid, t, active=None):
+        """the same on the device (adi_cyl_source_sample): a DeviceField"""
+        out = grid.layout.empty(zero=True)
+        d_act = None if active is None else grid.layout.to_layout(active, torch.uint8)
+        check(lib.adi_cyl_source_sample(ctypes.byref(self.as_c()), grid.nr, grid.nphi, grid.nz, grid.layout.sx,
+                                        grid.R_in, grid.dr, grid.dphi, grid.dz, float(t), _p(d_act), _p(out), _stream()))
+        return DeviceField(out)
+
+    def set_block(self, blk, t0, dt, n=0):
+        check(lib.adi_cyl_source_set(_p(blk), ctypes.byref(self.as_c()), float(t0), float(dt), int(n), _stream()))
+
+
+def _source_block(owner):
+    """the device parameter block of a moving source (ADI_SOURCE_BLOCK_BYTES), one per grid / stepper"""
+    blk = getattr(owner, '_src_block', None)
+    if blk is None or blk.device != _device():
+        blk = owner._src_block = torch.zeros(_lib.SOURCE_BLOCK_BYTES, dtype=torch.uint8, device=_device())
+    return blk
+
+
 class _Plan:
     def __init__(self, handle):
         self.handle = handle
@@ -117,18 +220,26 @@ def _state(Tn, grid):
     return grid.layout.to_layout(Tn, torch.float64), kind
 
 
-def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner):
+def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None):
     # adi3d_cyl_phi_v3.py:335: `scheme = prm.scheme if prm.scheme in ('be', 'douglas') else 'be'` -- every string but
     # 'douglas' is backward Euler in the reference, and so it is here
     if prm.scheme == "douglas":
         raise NotImplementedError("adi3d_hip_cyl does not serve scheme='douglas': the reference's branch is numerically "
                                   "broken (reads uninitialised memory, omits alpha), so it has no valid oracle")
-    t, kind = _state(Tn, grid)
+    src = S if isinstance(S, CylGoldakSource) else None
+    if src is not None and t is None:
+        raise ValueError("t (the step's start time) is required when S is a CylGoldakSource")
+    x, kind = _state(Tn, grid)
     pl = _plan(grid, mat, prm.dt, robin_r, zbc)
     out = grid.layout.empty()
-    d_S = None if S is None else grid.layout.to_layout(S, torch.float64)
     d_act = None if active is None else grid.layout.to_layout(active, torch.uint8)
-    check(lib.adi_cyl_step(pl.handle, _p(t), _p(out), None, None, _p(d_S), _p(d_act),
+    if src is not None:           # q(t + dt/2) evaluated in the r sweep's load (adi_cyl_step_src)
+        blk = _source_block(grid)
+        src.set_block(blk, t, prm.dt)
+        check(lib.adi_cyl_step_src(pl.handle, _p(blk), _p(x), _p(out), _p(d_act), float(T_void), float(T_inner), _stream()))
+        return _wrap(out, kind)
+    d_S = None if S is None else grid.layout.to_layout(S, torch.float64)
+    check(lib.adi_cyl_step(pl.handle, _p(x), _p(out), None, None, _p(d_S), _p(d_act),
                            float(T_void), float(T_inner), _stream()))
     return _wrap(out, kind)
 
@@ -136,27 +247,47 @@ def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner):
 class StagedCylStepper:
     """adi_step (BE) with its arguments resolved once, for loops over a device-resident field and per-sweep timing:
     `events`: optional list of 4 torch.cuda.Event recorded on the launch stream before / between / after the r, phi
-    and z sweeps (adi_cyl_sweep of the C ABI)."""
+    and z sweeps (adi_cyl_sweep of the C ABI).
+    source: a CylGoldakSource, evaluated in the r sweep's load at each step's mid-time from a device block (adi_cyl_sweep_src)
+    whose step counter the z sweep advances; None issues the launches of a plain step."""
     stage_names = ['sweep_r', 'sweep_phi', 'sweep_z_contig']
     stage_bytes_per_cell = [16.0, 16.0, 16.0]          # SURVEY.md 8(d): field in + field out per sweep
 
-    def __init__(self, grid, mat, prm, robin_r, zbc):
+    def __init__(self, grid, mat, prm, robin_r, zbc, source=None):
         if prm.scheme == "douglas":
             raise NotImplementedError("scheme='douglas' has no valid oracle (see adi_step)")
+        if source is not None and not isinstance(source, CylGoldakSource):
+            raise TypeError("StagedCylStepper: source must be a CylGoldakSource (pass a source field to adi_step)")
         self.grid = grid
+        self.dt = float(prm.dt)
         self.plan = _plan(grid, mat, prm.dt, robin_r, zbc)
+        self.source = source
+        self.captures = 0
+        if source is not None:
+            source.validate()
+            _source_block(self)                        # exists before any capture
 
-    def step(self, T, events=None):
+    def _sweep(self, ax, a, b):
+        if self.source is None:
+            check(lib.adi_cyl_sweep(self.plan.handle, ax, _p(a), _p(b), None, None, 0.0, 0.0, _stream()))
+        else:
+            check(lib.adi_cyl_sweep_src(self.plan.handle, ax, _p(_source_block(self)), _p(a), _p(b), None, 0.0, 0.0,
+                                        _stream()))
+
+    def step(self, T, events=None, t=0.0):
         """r sweep T -> out, then the phi and z sweeps IN PLACE on out (every sweep kernel reads only the rows it writes):
-        the input is untouched, as in the reference, and two of the three sweeps work on one field instead of two"""
+        the input is untouched, as in the reference, and two of the three sweeps work on one field instead of two.
+        t: the step's start time (the source, if any, at t + dt/2)"""
         g = self.grid
+        if self.source is not None:
+            self.source.set_block(_source_block(self), t, self.dt)
         t = g.layout.to_layout(T, torch.float64)
         out = g.layout.empty()
         seq = ((0, t, out), (1, out, out), (2, out, out)) if g.nphi > 1 else ((0, t, out), (2, out, out))
         if events is not None:
             events[0].record()
         for ax, a, b in seq:
-            check(lib.adi_cyl_sweep(self.plan.handle, ax, _p(a), _p(b), None, None, 0.0, 0.0, _stream()))
+            self._sweep(ax, a, b)
             if events is not None:
                 events[ax + 1].record()
                 if ax == 0 and g.nphi == 1:
@@ -169,26 +300,31 @@ class StagedCylStepper:
         if events is not None:
             events[0].record()
         for ax in ((0, 1, 2) if self.grid.nphi > 1 else (0, 2)):
-            check(lib.adi_cyl_sweep(self.plan.handle, ax, _p(x), _p(x), None, None, 0.0, 0.0, _stream()))
+            self._sweep(ax, x, x)
             if events is not None:
                 events[ax + 1].record()
                 if ax == 0 and self.grid.nphi == 1:
                     events[2].record()
 
-    def run(self, T, nsteps, graph=True):
+    def run(self, T, nsteps, graph=True, t0=0.0):
         """`nsteps` BE steps with the same plan on a device-resident field (the drivers' inner loops,
         quick_compare_layer_birth_robin_cyl_v3.py), returned as a new DeviceField.  The loop owns its field, so all three
         sweeps run IN PLACE: the working set is one field (134 MB at 128 x 256 x 512, inside the 256 MB Infinity Cache)
         instead of two -- 0.160 -> 0.144 ms per step.  The step is three kernels of ~45 us, at the edge of launch-bound: the
         launches of one step are captured once into a HIP graph and replayed.  Bit-identical to calling step() nsteps
-        times.  graph=False: plain launches."""
+        times.  graph=False: plain launches.
+        t0: time at the start of the first step (a source's step i runs at t0 + i*dt + dt/2).  The source's block is written
+        here, so its parameters as they are now hold for this run; a change of its support's shape recaptures."""
         g = self.grid
         nsteps = int(nsteps)
         st = getattr(self, '_graph', None)
-        if st is None:
-            st = self._graph = dict(X=g.layout.empty(), g=None)
+        key = None if self.source is None else self.source.shape_key()
+        if st is None or st.get('key') != key:
+            st = self._graph = dict(X=g.layout.empty(), g=None, key=key)
         X = st['X']
         X.copy_(g.layout.to_layout(T, torch.float64))
+        if self.source is not None:
+            self.source.set_block(_source_block(self), t0, self.dt)
         if graph and nsteps >= 2 and st['g'] is None:
             self._step_inplace(X)                          # warm-up outside the capture (lazy module loads)
             X.copy_(g.layout.to_layout(T, torch.float64))
@@ -197,6 +333,9 @@ class StagedCylStepper:
             with torch.cuda.graph(cg):
                 self._step_inplace(X)
             st['g'] = cg
+            self.captures += 1
+            if self.source is not None:
+                self.source.set_block(_source_block(self), t0, self.dt)   # (after the warm-up: the counter starts at 0)
         for _ in range(nsteps):
             if graph and st['g'] is not None:
                 st['g'].replay()
@@ -207,15 +346,19 @@ class StagedCylStepper:
         return DeviceField(out)
 
 
-def adi_step(Tn, grid, mat, prm, robin_r, zbc, S=None, theta=None):
-    """adi3d_cyl_phi_v3.py:332-350 (BE branch: r -> phi -> z with theta = 1; `theta` is unused there too)."""
-    return _run(Tn, grid, mat, prm, robin_r, zbc, S, None, 0.0, 0.0)
+def adi_step(Tn, grid, mat, prm, robin_r, zbc, S=None, theta=None, t=None):
+    """adi3d_cyl_phi_v3.py:332-350 (BE branch: r -> phi -> z with theta = 1; `theta` is unused there too).
+    S: a source field [W/m^3] of the grid's shape (the reference's argument), or a CylGoldakSource evaluated at t + dt/2 in
+    the r sweep's load -- then `t`, the step's start time, is required."""
+    return _run(Tn, grid, mat, prm, robin_r, zbc, S, None, 0.0, 0.0, t)
 
 
-def adi_step_masked(Tn, grid, mat, prm, robin_outer, zbc, active, robin_inner=None, robin_void=None):
+def adi_step_masked(Tn, grid, mat, prm, robin_outer, zbc, active, robin_inner=None, robin_void=None, S=None, t=None):
     """quick_spiral_deposition_gif_v5.py:31-70: void cells clamped to robin_void.T_inf before and after
     the step, inactive axis-row cells to robin_inner.T_inf; the clamps are fused into the r-sweep load
-    and the z-sweep store."""
+    and the z-sweep store.
+    S: a CylGoldakSource (q(t + dt/2) added on active cells only; `t` required), or a source field added to the clamped
+    field as adi_step(T_work, S=S) adds it."""
     robin_inner = robin_inner or robin_outer
     robin_void = robin_void or robin_outer
-    return _run(Tn, grid, mat, prm, robin_outer, zbc, None, active, robin_void.T_inf, robin_inner.T_inf)
+    return _run(Tn, grid, mat, prm, robin_outer, zbc, S, active, robin_void.T_inf, robin_inner.T_inf, t)

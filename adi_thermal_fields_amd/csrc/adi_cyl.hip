@@ -15,7 +15,9 @@
 //   z sweep   contiguous axis 2 (build_coeff_z, :255-298): constant coefficients, the two end rows
 //             carry the neumann0 / dirichlet / robin closure; the void post-clamp is fused into the store.
 //
-// Algorithmic HBM traffic: 16 B/cell/sweep (+8 with a source, +1 per masked pass).
+// Moving heat source (the *_src / *_tick instantiations): q evaluated in the r sweep's load from a device block, the block's
+// step counter advanced by the z sweep; no source field, so no extra traffic.
+// Algorithmic HBM traffic: 16 B/cell/sweep (+8 with a source field, +1 per masked pass).
 // Cache policy of this translation unit: PLAIN loads and stores (the Cartesian kernels stream their outputs with nt stores).
 // The cylindrical sweeps run in place on a field of 134 MB at BASELINE configs[3] -- inside the 256 MB Infinity Cache -- and a
 // streaming store evicts exactly the lines the next sweep is about to read: 0.145 -> 0.133 ms per step in the loop, 0.154 ->
@@ -23,6 +25,7 @@
 #define ADI_STORE_AUX 0
 #define ADI_LOAD_NT_CONTIG 0
 #define ADI_CYL_NT 0
+#include <cstddef>
 #include <cstdlib>
 #include <math.h>
 #include <string.h>
@@ -55,6 +58,7 @@ struct adi_cyl_plan {
     double zadd0, zaddN;         // RHS increments (robin)
     int zdir0, zdirN;            // dirichlet flags
     double zT0, zTN;             // dirichlet values
+    double r_in, dr, dphi, dz;   // geometry (cell centres of the moving source)
 };
 
 #ifndef ADI_CYL_NT
@@ -68,15 +72,121 @@ struct CylZ {
     int dir0, dirN;
 };
 
+// ---- moving heat source (include/adi_hip.h, "Moving heat source of the cylindrical step") -----------------------
+// The r sweep's load adds dt*q/(rho cp) to R0, q evaluated in registers: no source field, the step's traffic is unchanged.
+struct CylSrcBlock {
+    adi_cyl_heat_source s;
+    double t0, dt;
+    unsigned long long n;
+};
+static_assert(sizeof(CylSrcBlock) == ADI_SOURCE_BLOCK_BYTES, "cylindrical source block layout");
+static_assert(offsetof(CylSrcBlock, n) == 120, "the counter sits where the Cartesian block keeps it (adi_source_tick)");
+
+struct CylGeo {
+    double r_in, dr, dphi, dz;
+    int nz;
+};
+
+constexpr double kCylECut = ADI_SOURCE_E_CUT;
+constexpr double kCylTwoPi = 6.283185307179586;
+
+__host__ __device__ inline double cyl_eterm(double o, double len)
+{
+#pragma clang fp contract(off)
+    return 3.0 * (o * o) / (len * len);
+}
+
+// what one launch needs of the source at time t (uniform over the grid), and per line the angle's sin / cos and the axial term
+struct CylSrcEval {
+    double rc, phic, zc, sgn, amp_f, amp_r, cf, cr, lrad, lax;
+    double sn, cs, ez;
+};
+
+__device__ inline void cyl_src_init(const adi_cyl_heat_source &s, double t, CylSrcEval &e)
+{
+#pragma clang fp contract(off)
+    e.rc = s.r_c;
+    e.phic = s.phi0 + s.omega * t;
+    e.zc = s.z0 + s.v_z * t;
+    e.sgn = s.omega < 0.0 ? -1.0 : 1.0;
+    const double den = pow(M_PI, 1.5);
+    e.amp_f = (6.0 * sqrt(3.0) * s.f_f * s.eta * s.power) / (s.a * s.b * s.c_f * den);
+    e.amp_r = (6.0 * sqrt(3.0) * (2.0 - s.f_f) * s.eta * s.power) / (s.a * s.b * s.c_r * den);
+    e.cf = s.c_f; e.cr = s.c_r;
+    e.lrad = s.depth == ADI_CYL_DEPTH_Z ? s.a : s.b;   // length of the radial offset rho
+    e.lax = s.depth == ADI_CYL_DEPTH_Z ? s.b : s.a;    // length of the axial offset zeta
+}
+
+// t_n + dt/2 of the block, t_n = t0 + n*dt without contraction (src_tmid of adi_source.hip)
+__device__ inline double cyl_src_tmid(const CylSrcBlock &B)
+{
+#pragma clang fp contract(off)
+    const double tn = B.t0 + (double)B.n * B.dt;
+    return tn + 0.5 * B.dt;
+}
+
+// Whether the cells of the lines [l0, l1] of one radius plane (line = j*nz + k) can meet the support; uniform over a tile.
+// Axially: the z range of the lines (all of it when they cross a phi boundary) against z_c +- R*lax.  In the plane: the
+// support lies in the disc of radius reach = R*max(c_f, c_r, lrad) about (r_c, phi_c), whose points all lie within
+// asin(reach/r_c) of phi_c (every angle when reach >= r_c).  R = sqrt(E_CUT/3); a relative slack of 1e-6 keeps rounding on
+// the safe side.
+__device__ inline bool cyl_src_tile(const CylSrcEval &e, long l0, long l1, const CylGeo &G)
+{
+    const double R = sqrt(kCylECut / 3.0) * (1.0 + 1e-6);
+    const unsigned nz = (unsigned)G.nz, j0 = (unsigned)l0 / nz, j1 = (unsigned)l1 / nz;   // (a plane is < 2^31 lines)
+    const double zlo = j0 == j1 ? ((double)((unsigned)l0 - j0 * nz) + 0.5) * G.dz : 0.5 * G.dz;
+    const double zhi = j0 == j1 ? ((double)((unsigned)l1 - j1 * nz) + 0.5) * G.dz : ((double)nz - 0.5) * G.dz;
+    const double hz = R * e.lax;
+    if (zhi < e.zc - hz || zlo > e.zc + hz) return false;
+    const double reach = R * fmax(fmax(e.cf, e.cr), e.lrad);
+    if (reach >= e.rc) return true;
+    const double half = asin(reach / e.rc) * (1.0 + 1e-6) + 1e-12;
+    const double plo = ((double)j0 + 0.5) * G.dphi, span = (double)(j1 - j0) * G.dphi;
+    const double x = e.phic - plo;
+    const double u = x - kCylTwoPi * floor(x * (1.0 / kCylTwoPi));   // phi_c - phi_lo in [0, 2 pi) (up to rounding)
+    if (u <= span) return true;
+    return fmin(u - span, kCylTwoPi - u) <= half;   // (u rounded past 2 pi or below 0 only shrinks a distance)
+}
+
+// per line (j, k): false when the axial term alone puts every cell of the line outside the support
+__device__ inline bool cyl_src_line(CylSrcEval &e, long line, const CylGeo &G)
+{
+#pragma clang fp contract(off)
+    const unsigned j = (unsigned)line / (unsigned)G.nz, k = (unsigned)line - j * (unsigned)G.nz;
+    e.ez = cyl_eterm(((double)k + 0.5) * G.dz - e.zc, e.lax);
+    if (!(e.ez <= kCylECut)) return false;
+    sincos(((double)j + 0.5) * G.dphi - e.phic, &e.sn, &e.cs);
+    return true;
+}
+
+// q at radius r of the current line; exp only where the exponent passes the cut
+__device__ inline double cyl_src_q(const CylSrcEval &e, double r)
+{
+#pragma clang fp contract(off)
+    const double xi = e.sgn * (r * e.sn);
+    const double rho = r * e.cs - e.rc;
+    const bool front = xi >= 0.0;
+    const double E = (cyl_eterm(xi, front ? e.cf : e.cr) + cyl_eterm(rho, e.lrad)) + e.ez;
+    if (!(E <= kCylECut)) return 0.0;
+    return (front ? e.amp_f : e.amp_r) * exp(-E);
+}
+__device__ inline double cyl_src_row(const CylSrcEval &e, const CylGeo &G, int i)
+{
+#pragma clang fp contract(off)
+    return cyl_src_q(e, G.r_in + ((double)i + 0.5) * G.dr);   // GridCyl.r
+}
+
 // ---- r sweep / phi sweep: strided kernel with table-driven rows ---------------------------------
 // MODE 0: r sweep (axis 0).  MODE 1: phi sweep (axis 1, periodic, Sherman-Morrison).
-template <int M, int MODE>
-__global__ __launch_bounds__(M <= 8 ? 1024 : 512) void k_cyl_strided(
+// SRC (MODE 0 only): the moving source of the block blk added in the load (k_cyl_strided_src)
+template <int M, int MODE, bool SRC>
+__device__ __forceinline__ void cyl_strided_body(
     const double *in, double *out, int n, long stride, int n_inner, long outer_stride,
     int Lp, int LINES, int tiles_inner, long ntiles,
     const double *__restrict__ ta, const double *__restrict__ tb, const double *__restrict__ tc, double add_last,
     const double *__restrict__ S, double s_scale, const uint8_t *__restrict__ active_mask, double T_void,
-    const double *__restrict__ fac, const double *__restrict__ zt, const double *__restrict__ smden)
+    const double *__restrict__ fac, const double *__restrict__ zt, const double *__restrict__ smden,
+    const CylSrcBlock *__restrict__ blk, const CylGeo &G)
 {
     extern __shared__ __align__(16) double sm[];
     const int tid = threadIdx.x;
@@ -90,6 +200,13 @@ __global__ __launch_bounds__(M <= 8 ? 1024 : 512) void k_cyl_strided(
     const int r0 = sg * M;
 
     double a[M], b[M], c[M], d[M];
+    CylSrcEval E;
+    bool src_on = false;
+    if constexpr (SRC) {   // (tile-uniform test first: a tile the support cannot reach evaluates nothing)
+        cyl_src_init(blk->s, cyl_src_tmid(*blk), E);
+        const long l0 = (long)ti * LINES, l1 = min(l0 + LINES, (long)n_inner) - 1;
+        src_on = cyl_src_tile(E, l0, l1, G) && active && cyl_src_line(E, kcol, G);
+    }
     double f = 0.0, b0 = 1.0;
     if (MODE == 1) {
         f = fac[to];
@@ -103,6 +220,8 @@ __global__ __launch_bounds__(M <= 8 ? 1024 : 512) void k_cyl_strided(
         double v = ok ? in[p] : 0.0;
         if (MODE == 0) {
             if (active_mask != nullptr && ok && active_mask[p] == 0) v = T_void;  // T_work[void] = ambient, :56-57
+            if constexpr (SRC)                                                  // R0 = Tn + dt*q/(rho cp), active cells
+                if (src_on && ok && !(active_mask != nullptr && active_mask[p] == 0)) v = v + s_scale * cyl_src_row(E, G, row);
             if (S != nullptr && ok) v = v + s_scale * S[p];                    // R0 = Tn + dt*(S/(rho cp)), :339
             a[r] = (row < n) ? ta[row] : 0.0;
             b[r] = (row < n) ? tb[row] : 1.0;
@@ -188,13 +307,40 @@ __global__ __launch_bounds__(M <= 8 ? 1024 : 512) void k_cyl_strided(
         }
 }
 
-// ---- z sweep: contiguous kernel, constant coefficients with end closures -----------------------
-template <int M, bool VEC>
-__global__ __launch_bounds__(256) void k_cyl_contig(const double *in, double *out,
-                                                   long nlines, int n, int Lp, CylZ z,
-                                                   const uint8_t *__restrict__ active_mask, double T_void,
-                                                   double T_inner, long lines_per_r0, long sx)
+template <int M, int MODE>
+__global__ __launch_bounds__(M <= 8 ? 1024 : 512) void k_cyl_strided(
+    const double *in, double *out, int n, long stride, int n_inner, long outer_stride,
+    int Lp, int LINES, int tiles_inner, long ntiles,
+    const double *__restrict__ ta, const double *__restrict__ tb, const double *__restrict__ tc, double add_last,
+    const double *__restrict__ S, double s_scale, const uint8_t *__restrict__ active_mask, double T_void,
+    const double *__restrict__ fac, const double *__restrict__ zt, const double *__restrict__ smden)
 {
+    cyl_strided_body<M, MODE, false>(in, out, n, stride, n_inner, outer_stride, Lp, LINES, tiles_inner, ntiles, ta, tb, tc,
+                                     add_last, S, s_scale, active_mask, T_void, fac, zt, smden, nullptr, CylGeo{});
+}
+
+// the r sweep (MODE 0) with the moving source of the block
+template <int M>
+__global__ __launch_bounds__(M <= 8 ? 1024 : 512) void k_cyl_strided_src(
+    const double *in, double *out, int n, long stride, int n_inner, int Lp, int LINES, int tiles_inner, long ntiles,
+    const double *__restrict__ ta, const double *__restrict__ tb, const double *__restrict__ tc, double add_last,
+    double s_scale, const uint8_t *__restrict__ active_mask, double T_void, const CylSrcBlock *__restrict__ blk, CylGeo G)
+{
+    cyl_strided_body<M, 0, true>(in, out, n, stride, n_inner, 0, Lp, LINES, tiles_inner, ntiles, ta, tb, tc, add_last,
+                                 nullptr, s_scale, active_mask, T_void, nullptr, nullptr, nullptr, blk, G);
+}
+
+// ---- z sweep: contiguous kernel, constant coefficients with end closures -----------------------
+// TICK: the first thread of block 0 advances the source block's counter (k_cyl_contig_tick: the step's last kernel; every
+// reader of the counter -- the r sweep -- has finished before it starts)
+template <int M, bool VEC, bool TICK>
+__device__ __forceinline__ void cyl_contig_body(const double *in, double *out,
+                                                long nlines, int n, int Lp, CylZ z,
+                                                const uint8_t *__restrict__ active_mask, double T_void,
+                                                double T_inner, long lines_per_r0, long sx, unsigned long long *tick)
+{
+    if constexpr (TICK)
+        if (blockIdx.x == 0 && threadIdx.x == 0) *tick = *tick + 1ull;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lw = 64 >> (__ffs(Lp) - 1);
     const int li = lane & (Lp - 1);
@@ -268,6 +414,23 @@ __global__ __launch_bounds__(256) void k_cyl_contig(const double *in, double *ou
     }
 }
 
+template <int M, bool VEC>
+__global__ __launch_bounds__(256) void k_cyl_contig(const double *in, double *out,
+                                                   long nlines, int n, int Lp, CylZ z,
+                                                   const uint8_t *__restrict__ active_mask, double T_void,
+                                                   double T_inner, long lines_per_r0, long sx)
+{
+    cyl_contig_body<M, VEC, false>(in, out, nlines, n, Lp, z, active_mask, T_void, T_inner, lines_per_r0, sx, nullptr);
+}
+template <int M, bool VEC>
+__global__ __launch_bounds__(256) void k_cyl_contig_tick(const double *in, double *out,
+                                                        long nlines, int n, int Lp, CylZ z,
+                                                        const uint8_t *__restrict__ active_mask, double T_void,
+                                                        double T_inner, long lines_per_r0, long sx, unsigned long long *tick)
+{
+    cyl_contig_body<M, VEC, true>(in, out, nlines, n, Lp, z, active_mask, T_void, T_inner, lines_per_r0, sx, tick);
+}
+
 // ---- FAST forms ------------------------------------------------------------------------------------------------
 // The three operators of the BE step have coefficients that do not depend on the data and hardly on the position:
 //   phi  (-f_i, 1+2f_i, -f_i) along the line, f_i by radius      -> the uniform-interior model of adi_core.hpp with one
@@ -338,12 +501,14 @@ __global__ __launch_bounds__(1024) void k_cyl_phi_fast(
 // z sweep: one wave = 64/Lp lines, lane li owns rows [li*M, li*M+M); coalesced loads / stores through a wave-private
 // LDS strip (adi_cart_dev.hpp, coal_load).  Closures without a Dirichlet end (neumann0 / robin): row 0 and row n-1
 // differ from the uniform row in their diagonal and right-hand side only.
-template <int M>
-__global__ __launch_bounds__(256) void k_cyl_z_fast(const double *in, double *out, long nlines,
-                                                   int n, int Lp, CylZ z, UniC<M> U,
-                                                   const uint8_t *__restrict__ active_mask, double T_void, double T_inner,
-                                                   long lines_per_r0, long sx)
+template <int M, bool TICK>
+__device__ __forceinline__ void cyl_z_fast_body(const double *in, double *out, long nlines,
+                                                int n, int Lp, CylZ z, UniC<M> U,
+                                                const uint8_t *__restrict__ active_mask, double T_void, double T_inner,
+                                                long lines_per_r0, long sx, unsigned long long *tick)
 {
+    if constexpr (TICK)    // (cyl_contig_body)
+        if (blockIdx.x == 0 && threadIdx.x == 0) *tick = *tick + 1ull;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __shared__ __align__(16) double strips[4 * 32 * (M + 2)];
     double *strip = strips + wave * 32 * (M + 2);
@@ -388,6 +553,23 @@ __global__ __launch_bounds__(256) void k_cyl_z_fast(const double *in, double *ou
     coal_store<M>(out + wbase, strip, lane, d);
 }
 
+template <int M>
+__global__ __launch_bounds__(256) void k_cyl_z_fast(const double *in, double *out, long nlines,
+                                                   int n, int Lp, CylZ z, UniC<M> U,
+                                                   const uint8_t *__restrict__ active_mask, double T_void, double T_inner,
+                                                   long lines_per_r0, long sx)
+{
+    cyl_z_fast_body<M, false>(in, out, nlines, n, Lp, z, U, active_mask, T_void, T_inner, lines_per_r0, sx, nullptr);
+}
+template <int M>
+__global__ __launch_bounds__(256) void k_cyl_z_fast_tick(const double *in, double *out, long nlines,
+                                                        int n, int Lp, CylZ z, UniC<M> U,
+                                                        const uint8_t *__restrict__ active_mask, double T_void,
+                                                        double T_inner, long lines_per_r0, long sx, unsigned long long *tick)
+{
+    cyl_z_fast_body<M, true>(in, out, nlines, n, Lp, z, U, active_mask, T_void, T_inner, lines_per_r0, sx, tick);
+}
+
 // r sweep.  Per segment (M rows, row M-1 = separator) the host stores, RF_STRIDE doubles each:
 //   wf[M-1]  forward multipliers  a_r * ip_{r-1}  (wf[0] unused)      wb[M-1] backward multipliers c_r * jp_{r+1}
 //   ip[M-1]  inverse pivots of the top-down factorisation             cr[M-1] the c_r of the interior rows
@@ -408,11 +590,12 @@ struct CylRSegView {
 
 // tile = 64 adjacent lines (one wave = one segment of 64 lines: the tables are wave-uniform -> scalar loads) x all
 // segments; 512-byte row pieces
-template <int M>
-__global__ __launch_bounds__(1024) void k_cyl_r_fast(
+// SRC: the moving source of the block blk added in the load (k_cyl_r_fast_src)
+template <int M, bool SRC>
+__device__ __forceinline__ void cyl_r_fast_body(
     const double *in, double *out, int n, long stride, int n_inner, int nseg, int Lp,
     long ntiles, const double *__restrict__ rfac, double add_last, const double *__restrict__ S, double s_scale,
-    const uint8_t *__restrict__ active_mask, double T_void)
+    const uint8_t *__restrict__ active_mask, double T_void, const CylSrcBlock *__restrict__ blk, const CylGeo &G)
 {
     extern __shared__ __align__(16) double sm[];          // 2 x [Lp][64] separator right-hand sides + [Lp][64] first-row data
     constexpr int MI = M - 1;
@@ -425,6 +608,12 @@ __global__ __launch_bounds__(1024) void k_cyl_r_fast(
     CylRSegView T;
     T.p = rfac + (size_t)sg * RF_STRIDE;
     double d[M];
+    CylSrcEval E;
+    bool src_on = false;
+    if constexpr (SRC) {   // (the tile's 64 lines first: a tile the support cannot reach evaluates nothing)
+        cyl_src_init(blk->s, cyl_src_tmid(*blk), E);
+        src_on = cyl_src_tile(E, tile * 64, tile * 64 + 63, G) && cyl_src_line(E, base, G);
+    }
 #if ADI_LOAD_PRIO
     __builtin_amdgcn_s_setprio(ADI_LOAD_PRIO);
 #endif
@@ -433,6 +622,8 @@ __global__ __launch_bounds__(1024) void k_cyl_r_fast(
         const long p = base + (long)(r0 + r) * stride;
         double v = in[p];
         if (active_mask != nullptr && active_mask[p] == 0) v = T_void;        // T_work[void] = ambient, :56-57
+        if constexpr (SRC)                                                    // R0 = Tn + dt*q/(rho cp), active cells
+            if (src_on && !(active_mask != nullptr && active_mask[p] == 0)) v = v + s_scale * cyl_src_row(E, G, r0 + r);
         if (S != nullptr) v = v + s_scale * S[p];                            // R0 = Tn + dt*(S/(rho cp)), :339
         d[r] = v;
     }
@@ -486,6 +677,25 @@ __global__ __launch_bounds__(1024) void k_cyl_r_fast(
     }
 }
 
+template <int M>
+__global__ __launch_bounds__(1024) void k_cyl_r_fast(
+    const double *in, double *out, int n, long stride, int n_inner, int nseg, int Lp,
+    long ntiles, const double *__restrict__ rfac, double add_last, const double *__restrict__ S, double s_scale,
+    const uint8_t *__restrict__ active_mask, double T_void)
+{
+    cyl_r_fast_body<M, false>(in, out, n, stride, n_inner, nseg, Lp, ntiles, rfac, add_last, S, s_scale, active_mask, T_void,
+                              nullptr, CylGeo{});
+}
+template <int M>
+__global__ __launch_bounds__(1024) void k_cyl_r_fast_src(
+    const double *in, double *out, int n, long stride, int n_inner, int nseg, int Lp,
+    long ntiles, const double *__restrict__ rfac, double add_last, double s_scale,
+    const uint8_t *__restrict__ active_mask, double T_void, const CylSrcBlock *__restrict__ blk, CylGeo G)
+{
+    cyl_r_fast_body<M, true>(in, out, n, stride, n_inner, nseg, Lp, ntiles, rfac, add_last, nullptr, s_scale, active_mask,
+                             T_void, blk, G);
+}
+
 // elementwise pass used when a sweep degenerates (nphi == 1) or the grid is too long for the fast path
 __global__ __launch_bounds__(256) void k_copy(const double *in, double *out, size_t n)
 {
@@ -502,7 +712,7 @@ static int contig_rows(int n) { return n <= 128 ? 2 : (n <= 256 ? 4 : (n <= 512 
 template <int M, int MODE>
 static void launch_cyl_strided(const double *in, double *out, int n, long stride, int n_inner, long n_outer,
                                long outer_stride, const adi_cyl_plan *pl, const double *S, double s_scale,
-                               const uint8_t *act, double T_void, hipStream_t st)
+                               const uint8_t *act, double T_void, hipStream_t st, const CylSrcBlock *blk, const CylGeo &G)
 {
     const int Lp = next_pow2((n + M - 1) / M);
     const int min_lines = 16, min_threads = 512;
@@ -514,6 +724,13 @@ static void launch_cyl_strided(const double *in, double *out, int n, long stride
     const int tiles_inner = (n_inner + lines - 1) / lines;
     const long ntiles = (long)tiles_inner * n_outer;
     const size_t lds = (size_t)8 * lines * (Lp + 1) * sizeof(double);
+    if constexpr (MODE == 0)
+        if (blk != nullptr) {     // (the r sweep: n_outer == 1)
+            hipLaunchKernelGGL((k_cyl_strided_src<M>), dim3((unsigned)ntiles), dim3(lines * Lp), lds, st, in, out, n, stride,
+                               n_inner, Lp, lines, tiles_inner, ntiles, pl->d_ar, pl->d_br, pl->d_cr, pl->r_add_last, s_scale,
+                               act, T_void, blk, G);
+            return;
+        }
     hipLaunchKernelGGL((k_cyl_strided<M, MODE>), dim3((unsigned)ntiles), dim3(lines * Lp), lds, st, in, out, n, stride,
                        n_inner, outer_stride, Lp, lines, tiles_inner, ntiles, pl->d_ar, pl->d_br, pl->d_cr,
                        pl->r_add_last, S, s_scale, act, T_void, pl->d_fac, pl->d_zt, pl->d_smden);
@@ -522,29 +739,70 @@ static void launch_cyl_strided(const double *in, double *out, int n, long stride
 template <int MODE>
 static void dispatch_cyl_strided(const double *in, double *out, int n, long stride, int n_inner, long n_outer,
                                  long outer_stride, const adi_cyl_plan *pl, const double *S, double s_scale,
-                                 const uint8_t *act, double T_void, hipStream_t st)
+                                 const uint8_t *act, double T_void, hipStream_t st, const CylSrcBlock *blk = nullptr,
+                                 const CylGeo &G = CylGeo{})
 {
     switch (strided_rows(n)) {
-        case 2: launch_cyl_strided<2, MODE>(in, out, n, stride, n_inner, n_outer, outer_stride, pl, S, s_scale, act, T_void, st); break;
-        case 4: launch_cyl_strided<4, MODE>(in, out, n, stride, n_inner, n_outer, outer_stride, pl, S, s_scale, act, T_void, st); break;
-        case 8: launch_cyl_strided<8, MODE>(in, out, n, stride, n_inner, n_outer, outer_stride, pl, S, s_scale, act, T_void, st); break;
-        default: launch_cyl_strided<16, MODE>(in, out, n, stride, n_inner, n_outer, outer_stride, pl, S, s_scale, act, T_void, st); break;
+        case 2: launch_cyl_strided<2, MODE>(in, out, n, stride, n_inner, n_outer, outer_stride, pl, S, s_scale, act, T_void, st, blk, G); break;
+        case 4: launch_cyl_strided<4, MODE>(in, out, n, stride, n_inner, n_outer, outer_stride, pl, S, s_scale, act, T_void, st, blk, G); break;
+        case 8: launch_cyl_strided<8, MODE>(in, out, n, stride, n_inner, n_outer, outer_stride, pl, S, s_scale, act, T_void, st, blk, G); break;
+        default: launch_cyl_strided<16, MODE>(in, out, n, stride, n_inner, n_outer, outer_stride, pl, S, s_scale, act, T_void, st, blk, G); break;
     }
 }
 
 template <int M>
 static void launch_cyl_contig(const double *in, double *out, long nlines, int n, const CylZ &z, const uint8_t *act,
-                              double T_void, double T_inner, long lines_per_r0, long sx, hipStream_t st)
+                              double T_void, double T_inner, long lines_per_r0, long sx, hipStream_t st,
+                              unsigned long long *tick)
 {
     const int Lp = next_pow2((n + M - 1) / M);
     const int lw = 64 / Lp;
     const long waves = (nlines + lw - 1) / lw;
     const unsigned grid = (unsigned)((waves + 3) / 4);
     const bool vec = ((((uintptr_t)in | (uintptr_t)out) & 15) == 0) && (n % M == 0) && (sx % 2 == 0);
-    if (vec)
+    if (tick != nullptr) {
+        if (vec)
+            hipLaunchKernelGGL((k_cyl_contig_tick<M, true>), dim3(grid), dim3(256), 0, st, in, out, nlines, n, Lp, z, act, T_void,
+                               T_inner, lines_per_r0, sx, tick);
+        else
+            hipLaunchKernelGGL((k_cyl_contig_tick<M, false>), dim3(grid), dim3(256), 0, st, in, out, nlines, n, Lp, z, act, T_void,
+                               T_inner, lines_per_r0, sx, tick);
+    } else if (vec)
         hipLaunchKernelGGL((k_cyl_contig<M, true>), dim3(grid), dim3(256), 0, st, in, out, nlines, n, Lp, z, act, T_void, T_inner, lines_per_r0, sx);
     else
         hipLaunchKernelGGL((k_cyl_contig<M, false>), dim3(grid), dim3(256), 0, st, in, out, nlines, n, Lp, z, act, T_void, T_inner, lines_per_r0, sx);
+}
+
+// q at every cell centre at time t (0 on inactive cells): the field form of the source, and what the tests compare with
+__global__ __launch_bounds__(256) void k_cyl_source_sample(adi_cyl_heat_source s, CylGeo G, int nr, int nphi, long sx,
+                                                           double t, const uint8_t *__restrict__ active, double *__restrict__ out)
+{
+    const long plane = (long)nphi * G.nz;
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= plane * nr) return;
+    const int i = (int)(q / plane);
+    const long line = q - (long)i * plane;
+    const long p = (long)i * sx + line;
+    CylSrcEval e;
+    cyl_src_init(s, t, e);
+    const bool on = (active == nullptr || active[p] != 0) && cyl_src_line(e, line, G);
+    out[p] = on ? cyl_src_row(e, G, i) : 0.0;
+}
+
+__global__ void k_cyl_source_set(CylSrcBlock *blk, CylSrcBlock v) { *blk = v; }
+
+static int check_cyl_source(const adi_cyl_heat_source *h, const char *fn)
+{
+    ADI_REQUIRE(h != nullptr, "%s: null source", fn);
+    const double v[] = {h->power, h->eta, h->a, h->b, h->c_f, h->c_r, h->f_f, h->r_c, h->phi0, h->omega, h->z0, h->v_z};
+    for (double x : v) ADI_REQUIRE(std::isfinite(x), "%s: non-finite source parameter", fn);
+    ADI_REQUIRE(h->power >= 0.0, "%s: power < 0", fn);
+    ADI_REQUIRE(h->eta >= 0.0 && h->eta <= 1.0, "%s: eta outside [0, 1]", fn);
+    ADI_REQUIRE(h->a > 0.0 && h->b > 0.0 && h->c_f > 0.0 && h->c_r > 0.0, "%s: non-positive length", fn);
+    ADI_REQUIRE(h->f_f > 0.0 && h->f_f < 2.0, "%s: f_f outside (0, 2)", fn);
+    ADI_REQUIRE(h->r_c >= 0.0, "%s: r_c < 0", fn);
+    ADI_REQUIRE(h->depth == ADI_CYL_DEPTH_Z || h->depth == ADI_CYL_DEPTH_R, "%s: depth must be 'z' (0) or 'r' (1)", fn);
+    return ADI_OK;
 }
 
 }  // namespace adi
@@ -591,6 +849,7 @@ int adi_cyl_plan_create_annular(int nr, int nphi, int nz, long plane_stride, dou
     memset(p, 0, sizeof(*p));
     ADI_HIP_TRY(hipGetDevice(&p->device));
     p->nr = nr; p->nphi = nphi; p->nz = nz; p->rho = rho; p->cp = cp; p->dt = dt;
+    p->r_in = r_in; p->dr = dr; p->dphi = dphi; p->dz = dz;
     p->sx = plane_stride ? plane_stride : (long)nphi * nz;
     if (p->sx < (long)nphi * nz) { delete p; return set_err(ADI_ERR_ARG, "adi_cyl_plan_create: plane_stride < nphi*nz"); }
     const double alpha = k / (rho * cp);  // Material.alpha, :48-50
@@ -770,9 +1029,12 @@ int adi_cyl_plan_destroy(adi_cyl_plan *plan)
     return ADI_OK;
 }
 
+// blk != nullptr: the moving source of the block (k_cyl_r_fast_src / k_cyl_strided_src) instead of d_S
 static int cyl_sweep_r(const adi_cyl_plan *pl, const double *in, double *out, const double *d_S, const uint8_t *d_active,
-                       double T_void, hipStream_t st)
+                       double T_void, hipStream_t st, const CylSrcBlock *blk = nullptr)
 {
+    CylGeo G;
+    G.r_in = pl->r_in; G.dr = pl->dr; G.dphi = pl->dphi; G.dz = pl->dz; G.nz = pl->nz;
     const int nr = pl->nr;
     const long plane = (long)pl->nphi * pl->nz;
     const double s_scale = pl->dt * (1.0 / (pl->rho * pl->cp));
@@ -780,14 +1042,20 @@ static int cyl_sweep_r(const adi_cyl_plan *pl, const double *in, double *out, co
         const int Lp = pl->r_nseg;
         const long ntiles = plane / 64;
         const size_t lds = (size_t)3 * Lp * 64 * sizeof(double);
-        if (pl->r_M == 8)
+        if (blk != nullptr && pl->r_M == 8)
+            hipLaunchKernelGGL((k_cyl_r_fast_src<8>), dim3((unsigned)ntiles), dim3(64 * Lp), lds, st, in, out, nr, pl->sx,
+                               (int)plane, pl->r_nseg, Lp, ntiles, pl->d_rfac, pl->r_add_last, s_scale, d_active, T_void, blk, G);
+        else if (blk != nullptr)
+            hipLaunchKernelGGL((k_cyl_r_fast_src<16>), dim3((unsigned)ntiles), dim3(64 * Lp), lds, st, in, out, nr, pl->sx,
+                               (int)plane, pl->r_nseg, Lp, ntiles, pl->d_rfac, pl->r_add_last, s_scale, d_active, T_void, blk, G);
+        else if (pl->r_M == 8)
             hipLaunchKernelGGL((k_cyl_r_fast<8>), dim3((unsigned)ntiles), dim3(64 * Lp), lds, st, in, out, nr, pl->sx, (int)plane,
                                pl->r_nseg, Lp, ntiles, pl->d_rfac, pl->r_add_last, d_S, s_scale, d_active, T_void);
         else
             hipLaunchKernelGGL((k_cyl_r_fast<16>), dim3((unsigned)ntiles), dim3(64 * Lp), lds, st, in, out, nr, pl->sx, (int)plane,
                                pl->r_nseg, Lp, ntiles, pl->d_rfac, pl->r_add_last, d_S, s_scale, d_active, T_void);
     } else {
-        dispatch_cyl_strided<0>(in, out, nr, pl->sx, (int)plane, 1, 0, pl, d_S, s_scale, d_active, T_void, st);
+        dispatch_cyl_strided<0>(in, out, nr, pl->sx, (int)plane, 1, 0, pl, d_S, s_scale, d_active, T_void, st, blk, G);
     }
     ADI_CHECK_LAUNCH();
     return ADI_OK;
@@ -816,8 +1084,9 @@ static int cyl_sweep_phi(const adi_cyl_plan *pl, const double *in, double *out, 
     return ADI_OK;
 }
 
+// tick != nullptr: the same sweep, whose first thread also advances the source block's counter (k_*_tick)
 static int cyl_sweep_z(const adi_cyl_plan *pl, const double *in, double *out, const uint8_t *d_active, double T_void,
-                       double T_inner, hipStream_t st)
+                       double T_inner, hipStream_t st, unsigned long long *tick = nullptr)
 {
     const int nr = pl->nr, nphi = pl->nphi, nz = pl->nz;
     CylZ z;
@@ -829,14 +1098,18 @@ static int cyl_sweep_z(const adi_cyl_plan *pl, const double *in, double *out, co
                       nphi % lwf == 0 && ((((uintptr_t)in | (uintptr_t)out) & 15) == 0) && pl->sx % 2 == 0;
     if (fast) {
         const long waves = nlines / lwf;
-        hipLaunchKernelGGL((k_cyl_z_fast<16>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, in, out, nlines, nz, Lpf, z,
-                           make_unic<16>(z.f), d_active, T_void, T_inner, (long)nphi, pl->sx);
+        if (tick != nullptr)
+            hipLaunchKernelGGL((k_cyl_z_fast_tick<16>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, in, out, nlines, nz,
+                               Lpf, z, make_unic<16>(z.f), d_active, T_void, T_inner, (long)nphi, pl->sx, tick);
+        else
+            hipLaunchKernelGGL((k_cyl_z_fast<16>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, in, out, nlines, nz,
+                               Lpf, z, make_unic<16>(z.f), d_active, T_void, T_inner, (long)nphi, pl->sx);
     } else {
         switch (contig_rows(nz)) {
-            case 2: launch_cyl_contig<2>(in, out, nlines, nz, z, d_active, T_void, T_inner, nphi, pl->sx, st); break;
-            case 4: launch_cyl_contig<4>(in, out, nlines, nz, z, d_active, T_void, T_inner, nphi, pl->sx, st); break;
-            case 8: launch_cyl_contig<8>(in, out, nlines, nz, z, d_active, T_void, T_inner, nphi, pl->sx, st); break;
-            default: launch_cyl_contig<16>(in, out, nlines, nz, z, d_active, T_void, T_inner, nphi, pl->sx, st); break;
+            case 2: launch_cyl_contig<2>(in, out, nlines, nz, z, d_active, T_void, T_inner, nphi, pl->sx, st, tick); break;
+            case 4: launch_cyl_contig<4>(in, out, nlines, nz, z, d_active, T_void, T_inner, nphi, pl->sx, st, tick); break;
+            case 8: launch_cyl_contig<8>(in, out, nlines, nz, z, d_active, T_void, T_inner, nphi, pl->sx, st, tick); break;
+            default: launch_cyl_contig<16>(in, out, nlines, nz, z, d_active, T_void, T_inner, nphi, pl->sx, st, tick); break;
         }
     }
     ADI_CHECK_LAUNCH();
@@ -881,6 +1154,68 @@ int adi_cyl_step(const adi_cyl_plan *pl, const double *d_T_in, double *d_T_out, 
         if (int rc = cyl_sweep_phi(pl, d_T_out, d_T_out, st)) return rc;
     // z sweep (void post-clamp fused)
     return cyl_sweep_z(pl, d_T_out, d_T_out, d_active, T_void, T_inner, st);
+}
+
+int adi_cyl_source_set(void *d_block, const adi_cyl_heat_source *h_src, double t0, double dt, long long n, void *stream)
+{
+    if (int rc = check_cyl_source(h_src, "adi_cyl_source_set")) return rc;
+    ADI_REQUIRE(d_block, "adi_cyl_source_set: null block");
+    ADI_REQUIRE(std::isfinite(t0) && std::isfinite(dt) && dt > 0.0 && n >= 0, "adi_cyl_source_set: bad t0 / dt / n");
+    CylSrcBlock v;
+    memset(&v, 0, sizeof(v));
+    v.s = *h_src;
+    v.t0 = t0; v.dt = dt; v.n = (unsigned long long)n;
+    hipLaunchKernelGGL(k_cyl_source_set, dim3(1), dim3(1), 0, as_stream(stream), (CylSrcBlock *)d_block, v);
+    ADI_CHECK_LAUNCH();
+    return ADI_OK;
+}
+
+int adi_cyl_source_sample(const adi_cyl_heat_source *h_src, int nr, int nphi, int nz, long plane_stride, double r_in,
+                          double dr, double dphi, double dz, double t, const uint8_t *d_active, double *d_out, void *stream)
+{
+    if (int rc = check_cyl_source(h_src, "adi_cyl_source_sample")) return rc;
+    ADI_REQUIRE(d_out, "adi_cyl_source_sample: null output");
+    ADI_REQUIRE(nr > 0 && nphi > 0 && nz > 0, "adi_cyl_source_sample: bad grid");
+    const double g[] = {r_in, dr, dphi, dz, t};
+    for (double x : g) ADI_REQUIRE(std::isfinite(x), "adi_cyl_source_sample: non-finite geometry / t");
+    ADI_REQUIRE(r_in >= 0.0 && dr > 0.0 && dphi > 0.0 && dz > 0.0, "adi_cyl_source_sample: bad r_in / dr / dphi / dz");
+    const long sx = plane_stride ? plane_stride : (long)nphi * nz;
+    ADI_REQUIRE(sx >= (long)nphi * nz, "adi_cyl_source_sample: plane_stride < nphi*nz");
+    CylGeo G;
+    G.r_in = r_in; G.dr = dr; G.dphi = dphi; G.dz = dz; G.nz = nz;
+    const long cells = (long)nr * nphi * nz;
+    hipLaunchKernelGGL(k_cyl_source_sample, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, as_stream(stream), *h_src, G,
+                       nr, nphi, sx, t, d_active, d_out);
+    ADI_CHECK_LAUNCH();
+    return ADI_OK;
+}
+
+int adi_cyl_sweep_src(const adi_cyl_plan *pl, int axis, void *d_block, const double *d_in, double *d_out,
+                      const uint8_t *d_active, double T_void, double T_inner, void *stream)
+{
+    ADI_REQUIRE(pl && d_block && d_in && d_out, "adi_cyl_sweep_src: bad argument");
+    ADI_REQUIRE(axis >= 0 && axis < 3, "adi_cyl_sweep_src: bad axis %d", axis);
+    ADI_REQUIRE((long)pl->nphi * pl->nz <= 0x7fffffffL, "adi_cyl_sweep_src: (nphi, nz) plane too large");
+    hipStream_t st = as_stream(stream);
+    CylSrcBlock *blk = (CylSrcBlock *)d_block;
+    if (axis == 0) return cyl_sweep_r(pl, d_in, d_out, nullptr, d_active, T_void, st, blk);
+    if (axis == 2) return cyl_sweep_z(pl, d_in, d_out, d_active, T_void, T_inner, st, &blk->n);
+    return adi_cyl_sweep(pl, 1, d_in, d_out, nullptr, nullptr, 0.0, 0.0, stream);
+}
+
+int adi_cyl_step_src(const adi_cyl_plan *pl, void *d_block, const double *d_T_in, double *d_T_out,
+                     const uint8_t *d_active, double T_void, double T_inner, void *stream)
+{
+    ADI_REQUIRE(pl && d_block && d_T_in && d_T_out, "adi_cyl_step_src: null argument");
+    ADI_REQUIRE(d_T_out != d_T_in, "adi_cyl_step_src: T_out aliases T_in");
+    ADI_REQUIRE((long)pl->nphi * pl->nz <= 0x7fffffffL, "adi_cyl_step_src: (nphi, nz) plane too large");
+    hipStream_t st = as_stream(stream);
+    CylSrcBlock *blk = (CylSrcBlock *)d_block;
+    // adi_cyl_step with the source evaluated in the r sweep's load and the counter advanced by the z sweep
+    if (int rc = cyl_sweep_r(pl, d_T_in, d_T_out, nullptr, d_active, T_void, st, blk)) return rc;
+    if (pl->nphi > 1)
+        if (int rc = cyl_sweep_phi(pl, d_T_out, d_T_out, st)) return rc;
+    return cyl_sweep_z(pl, d_T_out, d_T_out, d_active, T_void, T_inner, st, &blk->n);
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@ import math
 import numpy as np
 
 __all__ = ['synthetic_head_mask', 'plan_layers', 'birth_times', 'layer_birth_schedule', 'run_layer_birth', 'run_single_track',
-           'run_layer_birth_slab', 'run_single_track_slab']
+           'run_layer_birth_slab', 'run_single_track_slab', 'ring_source', 'run_spiral_deposition']
 
 
 def synthetic_head_mask(nx, ny, nz):
@@ -242,6 +242,87 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
                 T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=src, t=i * params.dt)
         params.dt = dt_orig
     return np.asarray(T)
+
+
+def ring_source(heat_source, R_in, wall, z_top, tau):
+    """the heat source of one ring of run_spiral_deposition: `heat_source`'s power, efficiency and shape, its centre on the
+    nozzle -- mid-wall radius R_in + wall/2, angle 0 at t = 0 turning at 2 pi / tau, height z_top (the top of the ring being
+    deposited), no axial travel"""
+    s = heat_source
+    return type(s)(s.power, s.eta, s.a, s.b, s.c_f, s.c_r, f_f=s.f_f, r_c=R_in + 0.5 * wall, phi0=0.0,
+                   omega=2.0 * math.pi / tau, z0=z_top, v_z=0.0, depth=s.depth)
+
+
+def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_side, h_end, z_back, layer_h, n_layers, tau,
+                          nr, nphi, heat_source=None, device_resident=True):
+    """The ring-by-ring deposition loop of quick_spiral_deposition_gif_v5.py on an annular wall (R_in, R_in + wall): one
+    z-cell per layer, nphi cells per turn, dt = tau / nphi, BE.  Before each step the arc swept during it is activated at Tdep
+    in whole radial columns, then adi_step_masked advances the field (Robin h_side on the outer wall, neumann0 below, Robin
+    h_end on top; voids and the inner row clamped to Tinf).  mat_args = dict(rho=, cp=, k=).
+    heat_source (a CylGoldakSource of the backend): the arc as a moving volumetric source on the ring being deposited
+    (ring_source; the ring's top z, a new one when a layer completes), on active cells, during the steps that deposit; None:
+    the reference's loop.  With a device backend and device_resident, T and the active mask stay in HBM and an arc's
+    activation is two slice assignments.  Returns (grid, fields, masks): NumPy (nr, nphi, nz) fields and masks at `times`."""
+    dr = wall / nr
+    nz = int(round((z_back + layer_h * n_layers) / layer_h))
+    grid = backend.GridCyl(nr, nphi, nz, dr, 2.0 * math.pi / nphi, layer_h, R_in + wall, R_in=R_in)
+    m = backend.Material(mat_args['rho'], mat_args['cp'], mat_args['k'])
+    wall_bc = backend.RobinR(h_side, Tinf)
+    zbc = backend.ZBC(kind_bot='neumann0', kind_top='robin', h_top=h_end, T_inf_top=Tinf)
+    iz0 = int(round(z_back / layer_h))
+    T = np.full((nr, nphi, nz), float(Tinf))
+    active = np.zeros((nr, nphi, nz), bool)
+    active[:, :, :iz0] = True
+    dev = device_resident and _is_device_backend(backend)
+    if dev:                                       # T and the mask in HBM: an activation is two slice assignments
+        import torch
+        T = grid.layout.to_layout(T, torch.float64)           # (a native-layout tensor in, a tensor out of every step)
+        active = grid.layout.to_layout(active, torch.uint8)
+    dt, omega = tau / nphi, 2.0 * math.pi / tau
+    prm = backend.Params(dt, 1.0, "be")
+    layer, angle, t = 0, 0.0, 0.0
+    fields, masks = [], []
+    for t_goal in times:
+        while t < t_goal - 1e-12:
+            t_next = min(t + dt, t_goal)
+            left = omega * (t_next - t)
+            src = None
+            if heat_source is not None and layer < n_layers and 0 <= iz0 + layer < nz:
+                src = ring_source(heat_source, R_in, wall, (iz0 + layer + 1) * layer_h, tau)
+            while left > 0.0 and layer < n_layers:
+                seg = min(left, 2.0 * math.pi - angle)
+                if seg > 0.0:
+                    iz = iz0 + layer
+                    if 0 <= iz < nz:
+                        first = int(math.floor(angle / grid.dphi))
+                        last = max(first, int(math.floor((angle + seg - 1e-12) / grid.dphi)))
+                        for c in range(first, last + 1):
+                            if not active[0, c % nphi, iz]:
+                                active[:, c % nphi, iz] = True
+                                T[:, c % nphi, iz] = Tdep
+                    angle += seg
+                    left -= seg
+                if angle >= 2.0 * math.pi - 1e-15:
+                    angle = 0.0
+                    layer += 1
+                    if iz0 + layer > nz - 1:
+                        layer = n_layers
+            prm.dt = t_next - t
+            if src is None:
+                T = backend.adi_step_masked(T, grid, m, prm, wall_bc, zbc, active, robin_inner=wall_bc, robin_void=wall_bc)
+            else:
+                T = backend.adi_step_masked(T, grid, m, prm, wall_bc, zbc, active, robin_inner=wall_bc, robin_void=wall_bc,
+                                            S=src, t=t)
+            if not dev:
+                T = np.asarray(T).copy()
+            t = t_next
+        if dev:
+            fields.append(T.cpu().numpy().copy())
+            masks.append(active.cpu().numpy().astype(bool))
+        else:
+            fields.append(T.copy())
+            masks.append(active.copy())
+    return grid, fields, masks
 
 
 def run_layer_birth_slab(comm, i0, i1, mask_full, dx, mat, params_cls, h, Tinf, Ts, theta, cfl, layers, times_birth,

@@ -550,6 +550,57 @@ int adi_explicit_rhs_src(const double *d_T, const double *d_S, const uint8_t *d_
                          double *d_R0, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Moving heat source of the cylindrical step.  For a step t_n -> t_n + dt:
+ *     R0 = Tn + dt * q(x_c, t_n + dt/2) / (rho*cp)
+ * and the three sweeps run unchanged.  Cell centres r_i = r_in + (i+1/2) dr, phi_j = (j+1/2) dphi, z_k = (k+1/2) dz (z from
+ * the bottom face).  With `d_active` (the adi_step_masked form) q is added on active cells only; void cells keep the clamps.
+ *
+ * adi_cyl_heat_source: Goldak's double ellipsoid riding on the wall.  Centre at time t: radius r_c, angle
+ * phi_c = phi0 + omega t (omega signed), height z_c = z0 + v_z t (v_z = pitch |omega| / 2 pi: a helix; 0: a ring).  Offsets
+ * in the Cartesian frame (tangent, radial, axial) at the centre, with delta = phi - phi_c and s = sign(omega) (+1 for 0):
+ *     xi = s r sin(delta),  rho = r cos(delta) - r_c,  zeta = z - z_c
+ * depth = ADI_CYL_DEPTH_Z (the arc on top of a wall):      E = 3 xi^2/c^2 + 3 rho^2/a^2 + 3 zeta^2/b^2
+ * depth = ADI_CYL_DEPTH_R (cladding on a cylinder face):   E = 3 xi^2/c^2 + 3 zeta^2/a^2 + 3 rho^2/b^2
+ *     q = 6 sqrt(3) f eta P / (a b c pi^1.5) exp(-E),  (f, c) = (f_f, c_f) where xi >= 0, else (2 - f_f, c_r);
+ *     q = 0 exactly where E > ADI_SOURCE_E_CUT.
+ * The ellipsoid is rigid, so Goldak's normalisation holds: 2 eta P over all space, eta P over the half-space on one side of
+ * the centre plane normal to the depth axis.  Valid: finite values, power >= 0, 0 <= eta <= 1, a, b, c_f, c_r > 0,
+ * 0 < f_f < 2, r_c >= 0, depth 0 or 1.  Everything else is ADI_ERR_ARG, checked before any HIP call.
+ * The parameter block (ADI_SOURCE_BLOCK_BYTES) holds the source, t0, dt and the step counter n at the offsets of the
+ * Cartesian block (adi_source_tick advances either); t_n = t0 + n*dt.  The step kernels read it through the pointer, so a
+ * captured graph follows every parameter as the block changes.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADI_CYL_DEPTH_Z 0
+#define ADI_CYL_DEPTH_R 1
+typedef struct adi_cyl_heat_source {
+    double power;        /* P [W] */
+    double eta;          /* efficiency */
+    double a, b;         /* transverse half-width, depth [m] */
+    double c_f, c_r;     /* front / rear length [m] */
+    double f_f;          /* front fraction; f_r = 2 - f_f */
+    double r_c;          /* radius of the centre [m] */
+    double phi0, omega;  /* angle of the centre at t = 0 [rad], angular velocity [rad/s] */
+    double z0, v_z;      /* height of the centre at t = 0 [m], axial velocity [m/s] */
+    int depth;           /* ADI_CYL_DEPTH_Z or ADI_CYL_DEPTH_R */
+    int reserved;
+} adi_cyl_heat_source;
+
+/* writes the parameter block d_block (device, ADI_SOURCE_BLOCK_BYTES) on `stream`: the source, t0, dt and the counter n */
+int adi_cyl_source_set(void *d_block, const adi_cyl_heat_source *h_src, double t0, double dt, long long n, void *stream);
+/* q [W/m^3] at the cell centres of an (nr, nphi, nz) grid at time t into d_out (plane stride plane_stride, 0: nphi*nz);
+ * d_active (optional): 0 on inactive cells */
+int adi_cyl_source_sample(const adi_cyl_heat_source *h_src, int nr, int nphi, int nz, long plane_stride, double r_in,
+                          double dr, double dphi, double dz, double t, const uint8_t *d_active, double *d_out,
+                          void *stream);
+/* adi_cyl_step with the source of d_block at t_n + dt/2 (plan's dt) evaluated in the r sweep's load; the z sweep advances
+ * the block's counter by one (a loop of these needs no separate tick) */
+int adi_cyl_step_src(const adi_cyl_plan *plan, void *d_block, const double *d_T_in, double *d_T_out,
+                     const uint8_t *d_active, double T_void, double T_inner, void *stream);
+/* adi_cyl_sweep with the block: axis 0 adds the source, axis 1 is the plain phi sweep, axis 2 advances the counter */
+int adi_cyl_sweep_src(const adi_cyl_plan *plan, int axis, void *d_block, const double *d_in, double *d_out,
+                      const uint8_t *d_active, double T_void, double T_inner, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Context API: the library owns the device memory; callers hand over HOST arrays.
  * One context per GPU and thread; no hidden global state.
  * ---------------------------------------------------------------------------------------------- */
