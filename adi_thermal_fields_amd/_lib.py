@@ -118,6 +118,13 @@ SIGNATURES = {
     'adi_morph6': (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'adi_flood_outside': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int_p, c_void_p]),
     'adi_pack_frame_f32be': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
+    'adi_stlcorr_count': (c_int, [c_void_p, c_void_p, c_long, c_double, c_int, c_double, c_void_p, c_void_p]),
+    'adi_stlcorr_bin': (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_int, c_long, c_long,
+                                c_double_p, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'adi_stlcorr_accumulate': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_double, c_double_p,
+                                       c_void_pp, c_void_pp, c_void_pp, c_void_p]),
+    'adi_stlcorr_fallback': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_long, c_int, c_double, c_void_p, c_void_p,
+                                     c_void_p]),
     'adi_count_exposed_faces': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p]),
     'adi_birth_planes': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_int, c_double, c_void_p,
                                  c_void_p]),
@@ -168,6 +175,8 @@ SIGNATURES = {
 MAX_BOX_CELLS = 1 << 32       # ADI_MAX_BOX_CELLS: nx * plane_stride of a Cartesian box stays below it
 SOURCE_BLOCK_BYTES = 128     # ADI_SOURCE_BLOCK_BYTES
 SOURCE_E_CUT = 40.0          # ADI_SOURCE_E_CUT
+STLCORR_DROPPED = (1 << 63) - 1   # ADI_STLCORR_DROPPED
+STLCORR_MAX_SUBDIV = 4096    # ADI_STLCORR_MAX_SUBDIV
 
 
 class HeatSource(ctypes.Structure):

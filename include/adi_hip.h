@@ -427,6 +427,41 @@ int adi_flood_outside(const uint8_t *d_solid, uint8_t *d_outside, int nx, int ny
                       void *stream);
 int adi_pack_frame_f32be(const double *d_T, int nx, int ny, int nz, long plane_stride, uint32_t *d_out, void *stream);
 
+/*
+ * Projection of a triangle mesh onto the faces of a voxel mask: voxel_bc_correction.py:53-167 (STLBoundaryCorrector), the
+ * stage that produces the per-voxel robin_h fields of a curved part.  Every sub-triangle of the reference's subdivision is a
+ * "slot"; the caller owns the workspaces and does the two pieces of plumbing between the calls (an exclusive scan of the
+ * counts, a STABLE sort of the keys).  Masks and fields share one layout: element (i, j, k) at i*stride_x + j*stride_y + k.
+ *
+ * adi_stlcorr_count: d_tri (ntri, 3, 3) vertices, d_area (ntri); d_count[t] = n*n, the sub-triangles of triangle t
+ *   (n = ceil of its largest bounding-box extent in voxels, clamped to [1, max_subdiv]), or 0 when area <= area_epsilon.
+ * adi_stlcorr_bin: d_offset (ntri + 1) = exclusive scan of d_count, d_offset[ntri] == nslot.  Slot s of triangle t is
+ *   sub-triangle s - d_offset[t] in the order of _subdivide_triangle (i, then j, lower before upper).  Writes d_key[s] = the
+ *   element offset of the voxel that holds the sub-triangle's centroid, or ADI_STLCORR_DROPPED when the centroid is outside
+ *   the grid or off-mask; d_sub_area[s]; d_slot_tri[s] = t.  The centroid is rounded operation by operation, as NumPy does.
+ * adi_stlcorr_accumulate: d_key_sorted / d_order = the keys sorted stably and the slot each sorted entry came from.  One
+ *   thread per voxel sums its entries IN SLOT ORDER -- the reference's order of addition -- per face: area * |normal
+ *   component| where the component passes 1e-12.  For every face that received a contribution it writes the sum to
+ *   h_area[face] (where not NULL) and, where h_robin[face] / h_scale[face] are not NULL, sum / dx^2 to the scale field and
+ *   h_base[face] * that to the Robin field.  The three tables are HOST arrays of six device pointers (face order of this
+ *   header); untouched cells keep what the caller put there (zeros).  No atomics: two runs give the same bits.
+ * adi_stlcorr_fallback: build_corrected_fields(fallback_to_base=True), :155-165 -- in-mask cells whose `face` neighbour is
+ *   off-mask or outside the box and whose Robin value is <= 0 get `base` and scale 1.
+ * None of the four synchronises.  Counts, offsets, keys and slot numbers are 64-bit.
+ */
+#define ADI_STLCORR_DROPPED    0x7fffffffffffffffLL
+#define ADI_STLCORR_MAX_SUBDIV 4096
+int adi_stlcorr_count(const double *d_tri, const double *d_area, long ntri, double dx, int max_subdiv,
+                      double area_epsilon, long *d_count, void *stream);
+int adi_stlcorr_bin(const double *d_tri, const double *d_area, const long *d_offset, long ntri, long nslot,
+                    const uint8_t *d_mask, int nx, int ny, int nz, long stride_x, long stride_y, const double *h_origin,
+                    double dx, int max_subdiv, long *d_key, double *d_sub_area, long *d_slot_tri, void *stream);
+int adi_stlcorr_accumulate(const long *d_key_sorted, const long *d_order, const double *d_sub_area, const long *d_slot_tri,
+                           const double *d_normal, long nslot, double dx, const double *h_base, double *const *h_area,
+                           double *const *h_robin, double *const *h_scale, void *stream);
+int adi_stlcorr_fallback(const uint8_t *d_mask, int nx, int ny, int nz, long stride_x, long stride_y, int face, double base,
+                         double *d_robin, double *d_scale, void *stream);
+
 /* T[sel != 0] = value   (layer birth: waam_from_stl_v7_mm.py:487-495 `T[newborn] = Ts`); flat over n elements */
 int adi_masked_fill(double *d_T, const uint8_t *d_sel, size_t n, double value, void *stream);
 /* dst = a | b  (birth bookkeeping: mask_act |= newborn) */
