@@ -151,13 +151,14 @@ __global__ __launch_bounds__(256) void k_stl_accumulate(const long *__restrict__
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) {
             const double comp = nrm[ax];
-            // _accumulate_face_projection: tol = 1e-12; add_projected_area drops a product that is not positive
+            // _accumulate_face_projection: tol = 1e-12; add_projected_area returns on `area <= 0.0`, so a product that
+            // is NaN (a NaN area passes `area <= area_epsilon` too) is added, as the reference adds it
             if (comp > 1e-12) {
                 const double w = a * comp;
-                if (w > 0.0) { acc[2 * ax + 1] += w; seen |= 1u << (2 * ax + 1); }
+                if (!(w <= 0.0)) { acc[2 * ax + 1] += w; seen |= 1u << (2 * ax + 1); }
             } else if (comp < -1e-12) {
                 const double w = a * (-comp);
-                if (w > 0.0) { acc[2 * ax] += w; seen |= 1u << (2 * ax); }
+                if (!(w <= 0.0)) { acc[2 * ax] += w; seen |= 1u << (2 * ax); }
             }
         }
     }

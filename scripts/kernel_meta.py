@@ -67,6 +67,25 @@ def object_kernels(obj):
     return kernels
 
 
+def object_mnemonics(obj):
+    """{mangled kernel name: [mnemonic of every instruction]} of the gfx950 code object of one .o (llvm-objdump -d)"""
+    with tempfile.TemporaryDirectory() as tmp:
+        fat, co = os.path.join(tmp, 'fat.bin'), os.path.join(tmp, 'dev.co')
+        subprocess.run([os.path.join(LLVM, 'llvm-objcopy'), '--dump-section=.hip_fatbin=' + fat, obj, os.path.join(tmp, 'x.o')],
+                       check=True, capture_output=True)
+        subprocess.run([os.path.join(LLVM, 'clang-offload-bundler'), '--unbundle', '--type=o', '--input=' + fat,
+                        '--targets=' + TARGET, '--output=' + co], check=True, capture_output=True)
+        text = subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '-d', co], capture_output=True, text=True, check=True).stdout
+    out, cur = {}, None
+    for line in text.splitlines():
+        m = re.match(r'^[0-9a-f]+ <([^>]+)>:', line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif cur is not None and re.match(r'^\s+[a-z]', line):
+            cur.append(line.split()[0])
+    return out
+
+
 def all_kernels(csrc=CSRC):
     out = []
     for f in sorted(os.listdir(csrc)):

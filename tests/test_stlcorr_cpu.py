@@ -12,9 +12,11 @@ import numpy as np
 import pytest
 
 from helpers import GOLDEN
+from stlcorr_meshes import BOUNDARY_CASES, HAND_SET_CASES, MARGIN_CASES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CASES = ['cyl64', 'cyl700', 'frustum', 'offgrid_sub1', 'offgrid_sub3', 'empty', 'small']
+
+CASES = MARGIN_CASES + BOUNDARY_CASES
 
 
 def test_every_fixture_is_there():
@@ -30,7 +32,7 @@ def _ulps(got, want):
     return np.abs(np.asarray(got) - want) / np.spacing(np.maximum(np.abs(want), np.finfo(np.float64).tiny))
 
 
-@pytest.mark.parametrize('name', CASES)
+@pytest.mark.parametrize('name', [c for c in CASES if c not in HAND_SET_CASES])
 def test_triangle_mesh_reproduces_the_stored_normals_and_areas(name):
     from adi_thermal_fields_amd.voxel_bc_correction import TriangleMesh
     g = np.load(os.path.join(GOLDEN, 'stlcorr_%s.npz' % name))
@@ -149,3 +151,37 @@ def test_no_scratch_in_the_stlcorr_kernels():
     for name, k in ks.items():
         assert k['scratch'] == 0 and k.get('vgpr_spill_count', 0) == 0, (name, k)
         assert k['max_flat_workgroup_size'] == 256, (name, k)
+
+
+def test_only_divisions_and_the_square_root_fuse_in_the_stlcorr_kernels():
+    """A tripwire for the rounding claim of csrc/adi_stlcorr.hip (`#pragma clang fp contract(off)`: every product and sum
+    of the binning rounds on its own, as NumPy's do).  The only fused multiply-adds left in the ISA are those of the fp64
+    division and square-root expansions: 5 per division (one v_div_fmas_f64 each) and 11 per square root (one v_rsq_f64
+    each).  Measured with hipcc of HIP 7.2.26015 (AMD clang 22.0.0git, roc-7.2.0), before this test existed and with it:
+    k_stl_count 15 = 5 * 3, k_stl_bin 96 = 5 * 17 + 11 * 1, k_stl_accumulate 30 = 5 * 6, k_stl_fallback 0.
+    Not a proof -- the fixtures with centroids on voxel boundaries are (test_stlcorr_gpu.py)."""
+    sys.path.insert(0, os.path.join(ROOT, 'scripts'))
+    import kernel_meta
+    obj = os.path.join(kernel_meta.CSRC, 'adi_stlcorr.o')
+    if not os.path.exists(os.path.join(kernel_meta.LLVM, 'llvm-objdump')):
+        pytest.skip('no llvm-objdump at %s' % kernel_meta.LLVM)
+    assert os.path.exists(obj), 'no adi_stlcorr.o under csrc/: run `python -m adi_thermal_fields_amd.build` first'
+    seen = {}
+    for name, ops in kernel_meta.object_mnemonics(obj).items():
+        if 'k_stl_' not in name:
+            continue
+        count = lambda *stems: sum(1 for op in ops if op.split('_e32')[0].split('_e64')[0] in stems)
+        fused = count('v_fma_f64', 'v_fmac_f64', 'v_pk_fma_f64')
+        div, sqrt = count('v_div_fmas_f64'), count('v_rsq_f64')
+        short = name[name.index('k_stl_'):].split('E')[0]
+        seen[short] = (fused, div, sqrt)
+        assert fused == 5 * div + 11 * sqrt, (
+            '%s: %d fused fp64 multiply-adds for %d divisions and %d square roots (expected 5 and 11 each).  Either the '
+            'compiler expands division / square root differently now -- disassemble the object (llvm-objdump -d on its '
+            'gfx950 code object), check that every v_fma_f64 / v_fmac_f64 sits between a v_div_scale_f64 or v_rsq_f64 and '
+            'its v_div_fixup_f64 / final v_cndmask, and record the new figures here with the compiler version -- or a '
+            'product and a sum of the binning were contracted: then the centroids no longer round as NumPy rounds them'
+            % (short, fused, div, sqrt))
+    print(seen)
+    assert sorted(seen) == ['k_stl_accumulate', 'k_stl_bin', 'k_stl_count', 'k_stl_fallback'], sorted(seen)
+    assert seen['k_stl_bin'][1:] == (17, 1) and seen['k_stl_count'][1:] == (3, 0), seen

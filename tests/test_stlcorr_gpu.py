@@ -1,8 +1,13 @@
 """GPU: the STL correction of voxel Robin coefficients (adi_thermal_fields_amd.voxel_bc_correction, csrc/adi_stlcorr.hip)
 against the reference's fields (tests/golden/stlcorr_*.npz, written by tests/golden/make_golden_stlcorr.py).
 
-Bounds.  The set of non-zero cells of every field must be the reference's exactly: that is the binning, and the fixtures
-keep every centroid at least 1e-9 dx away from a voxel boundary.  A value may differ by n_max * 2^-52 relative, the bound
+Bounds.  The set of non-zero cells of every field must be the reference's exactly: that is the binning.  Seven fixtures
+keep every centroid at least 1e-9 dx away from a voxel boundary; eight more do the opposite (planar faces on voxel planes,
+whole-voxel spans, normals at the 1e-12 tolerance, NaN / huge / subnormal inputs: stlcorr_meshes.BOUNDARY_CASES), so the
+voxel of a sub-triangle hangs on the last bit of a rounding and the device has to round as NumPy does.  Beyond the
+fixtures the reference is oracle/stlcorr_oracle.py, pinned to them bit for bit on the CPU
+(test_oracle_stlcorr_golden.py): a seeded fuzz over meshes, shapes, masks and depths, the slot decode down to
+max_subdiv = 4096 on the C ABI, special values.  A value may differ by n_max * 2^-52 relative, the bound
 for sums of n_max positive terms taken in another order, n_max read from the fixture; the device adds in the
 reference's order, so the differences measured so far are zero.  At scale there is no reference: for an
 all-true mask that contains the mesh every sub-triangle lands, so each projected-area field sums to
@@ -16,12 +21,13 @@ import pytest
 
 import cases
 from helpers import GOLDEN, rel_linf
+import stlcorr_meshes as sm
 from stlcorr_meshes import subdivisions, tube_triangles
 
 pytestmark = pytest.mark.gpu
 
 FACES = ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')
-CASES = ['cyl64', 'cyl700', 'frustum', 'offgrid_sub1', 'offgrid_sub3', 'empty', 'small']
+CASES = sm.MARGIN_CASES + sm.BOUNDARY_CASES
 EPS = 2.0 ** -52
 
 
@@ -50,7 +56,9 @@ def _compare(what, got, want, n_max):
     assert isinstance(got, np.ndarray) and got.dtype == np.float64 and got.shape == want.shape, what
     assert np.array_equal(got != 0.0, want != 0.0), '%s: %d cells differ in being zero' % (
         what, int(np.count_nonzero((got != 0.0) != (want != 0.0))))
-    nz = want != 0.0
+    odd = ~np.isfinite(want)                       # a NaN or an infinite area in the mesh: the same NaN / infinity
+    assert np.array_equal(got[odd], want[odd], equal_nan=True), what
+    nz = (want != 0.0) & ~odd
     worst = float(np.max(np.abs(got[nz] - want[nz]) / np.abs(want[nz]))) if nz.any() else 0.0
     assert worst <= n_max * EPS, '%s: relative difference %.3e above %d * 2^-52' % (what, worst, n_max)
     return worst
@@ -225,3 +233,158 @@ def test_keys_past_32_bits(shape):
     print('STLCORR far corner %s: first cell %d, relative difference of the scale sum %.3e (bound %.3e)'
           % (shape, first, rel, N * EPS))
     assert rel <= N * EPS, (got, want, rel)
+
+
+# ---- against the oracle -----------------------------------------------------------------------------------------------
+def _oracle(c):
+    from oracle import stlcorr_oracle as orc
+    return orc.STLBoundaryCorrector(c.mesh, c.mask, c.origin, c.dx, max_subdiv=c.max_subdiv, area_epsilon=c.area_epsilon)
+
+
+def _device(c, mask):
+    from adi_thermal_fields_amd.voxel_bc_correction import STLBoundaryCorrector
+    return STLBoundaryCorrector(c.mesh, mask, c.origin, c.dx, max_subdiv=c.max_subdiv, area_epsilon=c.area_epsilon)
+
+
+def _whole_storage(t):
+    """every element of the tensor's allocation: the logical box, the padding of the physical box and of the planes"""
+    import torch
+    return torch.empty(0, dtype=t.dtype, device=t.device).set_(t.untyped_storage())
+
+
+def _check_against_oracle(c, tag):
+    """fields of the NumPy-mask path within n_max * 2^-52 of the oracle's on the same non-zero cells; the device-mask
+    path (the padded layout of Grid3D) bit-equal to the NumPy-mask path; nothing off-mask or in the padding"""
+    import adi_thermal_fields_amd.adi3d_hip_coeff as hip
+    want = _oracle(c)
+    n_max = int(want.contribution_counts().max()) if want.contribution_counts().size else 0
+    w_area = want.projected_area_fields()
+    host, off = _device(c, c.mask), ~c.mask
+    d_mask = hip.Grid3D(*c.mask.shape, c.dx, c.mask).d_mask
+    dev = _device(c, d_mask)
+    worst = 0.0
+
+    area, d_area = host.projected_area_fields(), dev.projected_area_fields()
+    for f in FACES:
+        worst = max(worst, _compare('%s area %s' % (tag, f), area[f], w_area[f], n_max))
+        assert not area[f][off].any(), f
+        assert np.array_equal(d_area[f].cpu().numpy(), area[f], equal_nan=True), f
+        assert int((_whole_storage(d_area[f]) != 0).sum()) == int(np.count_nonzero(area[f])), f     # padding untouched
+    for fallback in (True, False):
+        w_robin, w_scale = want.build_corrected_fields(c.base_h, fallback_to_base=fallback)
+        robin, scale = host.build_corrected_fields(c.base_h, fallback_to_base=fallback)
+        d_robin, d_scale = dev.build_corrected_fields(c.base_h, fallback_to_base=fallback)
+        assert list(robin) == list(c.base_h) and list(d_robin) == list(c.base_h)
+        for f in c.base_h:
+            worst = max(worst, _compare('%s robin %s' % (tag, f), robin[f], w_robin[f], n_max),
+                        _compare('%s scale %s' % (tag, f), scale[f], w_scale[f], n_max))
+            assert not robin[f][off].any() and not scale[f][off].any(), f
+            for d, h in ((d_robin[f], robin[f]), (d_scale[f], scale[f])):
+                assert np.array_equal(d.cpu().numpy(), h, equal_nan=True), f
+                assert int((_whole_storage(d) != 0).sum()) == int(np.count_nonzero(h)), f
+            if c.base_h[f] == 0.0:
+                assert not robin[f].any() and not scale[f].any(), f
+    return worst, n_max, int(want.slots().offset[-1])
+
+
+@pytest.mark.parametrize('seed', range(sm.FUZZ_SEEDS))
+def test_fuzz_against_the_oracle(seed):
+    """stlcorr_meshes.fuzz_case: boxes and plates on voxel planes, lattice-snapped soups, tilted and axis-aligned tubes;
+    extents from 1 to 100 and ragged ones the layout pads; all-true, solid, holed and thin-walled masks; max_subdiv up to
+    64.  test_oracle_stlcorr_golden.py::test_the_fuzz_stays_on_the_hard_cases asserts on the CPU how many of these cases
+    have centroids exactly on voxel boundaries and how many are cut 16 deep or more."""
+    c = sm.fuzz_case(seed)
+    worst, n_max, nsub = _check_against_oracle(c, 'seed %d' % seed)
+    print('STLCORR fuzz %2d: %s mesh, %s mask %s, max_subdiv %d, %d sub-triangles, n_max %d, largest relative difference '
+          '%.3e (bound %.3e)' % (seed, c.mesh_kind, c.mask_kind, c.mask.shape, c.max_subdiv, nsub, n_max, worst, n_max * EPS))
+
+
+def test_special_values_against_the_oracle():
+    """the special_values mesh of the fixtures (NaN vertex, NaN and infinite area, area at area_epsilon, +-1e300 m, zero
+    normal, a product that underflows to zero) on a holed mask and a negative origin, and a mesh whose bounding box is
+    infinite (n clamps to max_subdiv; the reference raises there, the oracle states the device's rule).  Ordinary inputs
+    with defined results: a cell is NaN only where the oracle's is, nothing lands off-mask."""
+    import types
+    g, base_h = _load('special_values')
+    mask = g['mask'].copy()
+    mask[2:4, 2:5, 2:4] = np.random.default_rng(5).random((2, 3, 2)) < 0.5
+    tri = g['triangles'] - 2e-3
+    inf = np.array([[[np.inf, 1e-3, 1e-3], [2e-3, 3e-3, 1e-3], [1e-3, 2e-3, 4e-3]],
+                    [[1e-3, 1e-3, 1e-3], [2e-3, -np.inf, 1e-3], [1e-3, 2e-3, 4e-3]]])
+    for name, mesh in (('fixture mesh', sm.mesh_of(tri, normals=g['normals'], areas=g['areas'])),
+                       ('infinite span', sm.mesh_of(np.concatenate([tri[:1], inf, tri[8:]]),
+                                                    normals=[[0.36, -0.48, 0.8]] * 4, areas=[2.1e-6, 1e-6, 1e-6, 4e-8]))):
+        c = types.SimpleNamespace(mesh=mesh, mask=mask, origin=np.array([-2e-3, -2e-3, -2e-3]), dx=float(g['dx']),
+                                  max_subdiv=int(g['max_subdiv']), area_epsilon=float(g['area_epsilon']), base_h=base_h)
+        worst, n_max, nsub = _check_against_oracle(c, name)
+        print('STLCORR special values, %s: %d sub-triangles, largest relative difference %.3e' % (name, nsub, worst))
+
+
+def _abi_bin(tri, area, shape, origin, dx, max_subdiv, area_epsilon):
+    """adi_stlcorr_count -> scan -> adi_stlcorr_bin on an all-true dense mask, straight on the C ABI;
+    -> (offset, key, sub_area, slot_tri) as NumPy arrays"""
+    import ctypes
+    import torch
+    from adi_thermal_fields_amd._lib import check, lib
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    d_tri = torch.from_numpy(np.ascontiguousarray(tri, dtype=np.float64)).cuda()
+    d_area = torch.from_numpy(np.ascontiguousarray(area, dtype=np.float64)).cuda()
+    ntri = len(area)
+    offset = torch.zeros(ntri + 1, dtype=torch.int64, device='cuda')
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    check(lib.adi_stlcorr_count(p(d_tri), p(d_area), ntri, dx, max_subdiv, area_epsilon,
+                                ctypes.c_void_p(offset.data_ptr() + 8), stream))
+    offset.cumsum_(0)
+    nslot = int(offset[-1].item())
+    nx, ny, nz = shape
+    mask = torch.ones(nx * ny * nz, dtype=torch.uint8, device='cuda')
+    key = torch.full((nslot,), -7, dtype=torch.int64, device='cuda')
+    sub_area = torch.full((nslot,), -7.0, dtype=torch.float64, device='cuda')
+    slot_tri = torch.full((nslot,), -7, dtype=torch.int64, device='cuda')
+    check(lib.adi_stlcorr_bin(p(d_tri), p(d_area), p(offset), ntri, nslot, p(mask), nx, ny, nz, ny * nz, nz,
+                              (ctypes.c_double * 3)(*[float(v) for v in origin]), dx, max_subdiv, p(key), p(sub_area),
+                              p(slot_tri), stream))
+    torch.cuda.synchronize()
+    return offset.cpu().numpy(), key.cpu().numpy(), sub_area.cpu().numpy(), slot_tri.cpu().numpy()
+
+
+# a sliver 4099 voxels long inside a 4100 x 2 x 2 grid: cut as deep as max_subdiv allows, every centroid in the grid
+_SLIVER = np.array([[0.5, 0.3, 0.3], [4099.5, 0.6, 0.4], [2000.2, 1.7, 1.6]])
+_SLIVER_GRID = (4100, 2, 2)
+
+
+def _decode_case(tri, area, max_subdiv, area_epsilon=1e-16):
+    import types
+    from oracle import stlcorr_oracle as orc
+    dx = 2.0 ** -10
+    tri = np.asarray(tri, dtype=np.float64) * dx
+    mesh = types.SimpleNamespace(triangles=tri, face_normals=np.zeros((len(tri), 3)), area_faces=np.asarray(area, float))
+    want = orc.STLBoundaryCorrector(mesh, np.ones(_SLIVER_GRID, bool), (0.0, 0.0, 0.0), dx, max_subdiv=max_subdiv,
+                                    area_epsilon=area_epsilon).slots(keep_centroids=False)
+    offset, key, sub_area, slot_tri = _abi_bin(tri, area, _SLIVER_GRID, (0.0, 0.0, 0.0), dx, max_subdiv, area_epsilon)
+    assert np.array_equal(offset, want.offset)
+    assert np.all(want.cell >= 0)                                  # every centroid lands: every slot has a real key
+    assert np.array_equal(slot_tri, want.tri)
+    assert np.array_equal(sub_area, want.sub_area)
+    wrong = np.nonzero(key != want.cell)[0]
+    assert len(wrong) == 0, 'max_subdiv %d: %d of %d keys differ, the first at slot %d (device %d, oracle %d)' % (
+        max_subdiv, len(wrong), len(key), wrong[0], key[wrong[0]], want.cell[wrong[0]])
+    return len(key)
+
+
+@pytest.mark.parametrize('max_subdiv', [2, 3, 7, 31, 64, 1000, 4096])
+def test_slot_decode_at_depth(max_subdiv):
+    """k_stl_bin's closed-form decode of (i, j, lower / upper) from the slot number, for EVERY slot of one triangle cut
+    max_subdiv x max_subdiv, against the oracle's table written down by the loops (no square root)"""
+    n = _decode_case([_SLIVER], [3.7e-3], max_subdiv)
+    assert n == max_subdiv * max_subdiv
+
+
+def test_slot_decode_steps_over_triangles_without_slots():
+    """the binary search over repeated offsets: triangles at or below area_epsilon first, last, between two others and two
+    in a row"""
+    shifted = _SLIVER + [0.0, 0.05, -0.1]
+    tri = [_SLIVER, _SLIVER, shifted, _SLIVER, _SLIVER, _SLIVER, shifted[[1, 2, 0]], _SLIVER]
+    area = [0.0, 3.7e-3, 2.9e-3, 1e-9, 1e-9, 5.1e-3, 4.4e-3, 1e-9]
+    assert _decode_case(tri, area, 7, area_epsilon=1e-9) == 4 * 49
+    assert _decode_case(tri[:1] + tri[5:], area[:1] + area[5:], 33, area_epsilon=1e-9) == 2 * 33 * 33
