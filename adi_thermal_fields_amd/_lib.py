@@ -125,6 +125,12 @@ SIGNATURES = {
                                        c_void_pp, c_void_pp, c_void_pp, c_void_p]),
     'adi_stlcorr_fallback': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_long, c_int, c_double, c_void_p, c_void_p,
                                      c_void_p]),
+    'adi_voxelize_words': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_long)]),
+    'adi_voxelize_count': (c_int, [c_void_p, c_long, c_double_p, c_double, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'adi_voxelize_toggle': (c_int, [c_void_p, c_void_p, c_long, c_long, c_double_p, c_double, c_int, c_int, c_int, c_int,
+                                    c_void_p, c_void_p]),
+    'adi_voxelize_scan': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'adi_voxelize_majority': (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     'adi_count_exposed_faces': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p]),
     'adi_birth_planes': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_int, c_double, c_void_p,
                                  c_void_p]),

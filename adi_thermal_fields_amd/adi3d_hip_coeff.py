@@ -287,7 +287,10 @@ class Grid3D:
         self._all_solid = None
         self._scratch = None
         self.mask_version = next(_MASK_VERSIONS)
-        self.mask = np.asarray(mask).astype(np.bool_, copy=True, order='C')
+        if isinstance(mask, (torch.Tensor, DeviceField)):          # e.g. voxelize_solid(as_tensor=True): the setter downloads it
+            self.mask = mask
+        else:
+            self.mask = np.asarray(mask).astype(np.bool_, copy=True, order='C')
 
     @property
     def shape(self):

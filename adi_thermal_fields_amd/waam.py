@@ -4,8 +4,9 @@ The loops are restated from waam_from_stl_v7_mm.py (layers :436-456, birth times
 :487-495, event loop :515-550) and single_track_on_plate.py:150-177 (column-by-column deposit).  They drive ANY
 module with the reference's operator surface (`Grid3D`, `Material`, `Params`,
 `precompute_coeff_packs_unified`, `adi_step_numba_coeff`): the HIP backend in production, the CPU oracle in
-the parity tests.  STL loading / voxelisation (trimesh) is out of scope; `synthetic_head_mask` supplies the
-formula-generated stand-in for the missing `11091_FemaleHead_v4.stl`.
+the parity tests.  The mask of a part comes from `voxelize.load_voxel_from_stl_mm` (STL -> solid mask on the device, no
+trimesh); `synthetic_head_mask` supplies the formula-generated stand-in for the missing `11091_FemaleHead_v4.stl`
+(SURVEY.md 8(d) config 5).
 
 With the HIP backend the temperature stays in HBM for the whole run: births are a masked fill on the
 device, the mask/pack rebuild is one upload (1 B/cell) plus two kernels, frames download only at output times.

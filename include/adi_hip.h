@@ -462,6 +462,37 @@ int adi_stlcorr_accumulate(const long *d_key_sorted, const long *d_order, const 
 int adi_stlcorr_fallback(const uint8_t *d_mask, int nx, int ny, int nz, long stride_x, long stride_y, int face, double base,
                          double *d_robin, double *d_scale, void *stream);
 
+/*
+ * Solid voxelisation of a closed triangle mesh: voxel (i, j, k) of the dense uint8 mask (nx, ny, nz),
+ * C order, is 1 exactly when its centre h_origin[m] + (index + 0.5) * dx lies inside the surface.  Rays run along `axis`
+ * (0, 1 or 2) through every column of centres; with b = (axis + 1) % 3 and c = (axis + 2) % 3 a triangle covers a column
+ * when the three edge functions of its projection onto (b, c) have one strict sign (edges in lexicographic order, a zero
+ * broken as if the centre were nudged by (+eps, +eps^2)), its depth there is d0 + (l1 (d1 - d0) + l2 (d2 - d0)), and the
+ * crossing toggles every voxel of the column whose centre is >= depth.  Solid = an odd number of toggles.  No operation
+ * is contracted to an FMA: the result is the bit-for-bit value of the same arithmetic in IEEE doubles.
+ *
+ * The toggle grid is caller-owned, adi_voxelize_words() 32-bit words, zeroed by the caller before adi_voxelize_toggle:
+ * one bit per voxel along the ray and one more per column for crossings behind the last voxel.
+ *
+ * adi_voxelize_count: d_tri (ntri, 3, 3) vertices; d_count[t] = the 4 x 4 column tiles of triangle t's bounding box
+ *   clipped to the grid, 0 for zero projected area or a triangle outside.
+ * adi_voxelize_toggle: d_offset (ntri + 1) = exclusive scan of d_count, d_offset[ntri] == nitem.  Sixteen lanes per tile,
+ *   one integer atomic XOR of one bit per crossing: the grid does not depend on the order of arrival.
+ * adi_voxelize_scan: prefix XOR along every column (in place: d_words then holds the solid bits), the dense mask written
+ *   to d_mask, and the number of columns with an odd number of crossings ("leaks": the surface is not closed there)
+ *   ADDED to *d_leaks, a device int the caller zeroed.  d_words and d_mask 16-byte aligned.
+ * adi_voxelize_majority: d_out[q] = 1 where at least two of the three masks are non-zero (the three ray axes of a mesh
+ *   with small gaps); d_out may be one of the inputs.
+ * None of them synchronises.  Counts and offsets are 64-bit.
+ */
+int adi_voxelize_words(int nx, int ny, int nz, int axis, long *words);
+int adi_voxelize_count(const double *d_tri, long ntri, const double *h_origin, double dx, int nx, int ny, int nz, int axis,
+                       long *d_count, void *stream);
+int adi_voxelize_toggle(const double *d_tri, const long *d_offset, long ntri, long nitem, const double *h_origin, double dx,
+                        int nx, int ny, int nz, int axis, uint32_t *d_words, void *stream);
+int adi_voxelize_scan(uint32_t *d_words, int nx, int ny, int nz, int axis, uint8_t *d_mask, int *d_leaks, void *stream);
+int adi_voxelize_majority(const uint8_t *d_m0, const uint8_t *d_m1, const uint8_t *d_m2, size_t n, uint8_t *d_out, void *stream);
+
 /* T[sel != 0] = value   (layer birth: waam_from_stl_v7_mm.py:487-495 `T[newborn] = Ts`); flat over n elements */
 int adi_masked_fill(double *d_T, const uint8_t *d_sel, size_t n, double value, void *stream);
 /* dst = a | b  (birth bookkeeping: mask_act |= newborn) */
