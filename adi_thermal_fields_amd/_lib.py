@@ -178,6 +178,7 @@ SIGNATURES = {
     'adi_ctx_last_step_ms': (c_int, [c_void_p, ctypes.POINTER(ctypes.c_float)]),
 }
 
+MIXED_MIN_TG = 1e-9           # kMixedMinTg (csrc/adi_core.hpp): below this theta * gamma a sweep runs no FAST kernel
 MAX_BOX_CELLS = 1 << 32       # ADI_MAX_BOX_CELLS: nx * plane_stride of a Cartesian box stays below it
 SOURCE_BLOCK_BYTES = 128     # ADI_SOURCE_BLOCK_BYTES
 SOURCE_E_CUT = 40.0          # ADI_SOURCE_E_CUT
@@ -212,6 +213,10 @@ class AdiError(RuntimeError):
     pass
 
 
+class AdiArgError(AdiError, ValueError):
+    """ADI_ERR_ARG: the ValueError the reference would have raised, and -- like every status of the library -- an AdiError"""
+
+
 def last_error():
     msg = lib.adi_last_error()
     return msg.decode('utf-8', 'replace') if msg else ''
@@ -223,7 +228,7 @@ def check(rc):
         return
     msg = last_error()
     if rc == ADI_ERR_ARG:
-        raise ValueError(msg)          # e.g. ValueError("bad face"), adi3d_numba_coeff.py:54
+        raise AdiArgError(msg)         # e.g. ValueError("bad face"), adi3d_numba_coeff.py:54
     raise AdiError('libadi_hip error %d: %s' % (rc, msg))
 
 

@@ -658,15 +658,21 @@ class _NoFallback:
     number of queued units is read back from the first word of the workspace (one 4-byte copy, once per mask / pack
     version), and later sweeps of the same configuration carry the bit when that number was zero.  The read-back is a
     host synchronisation, so it waits for the third sweep of a configuration: a layer-birth loop that changes the mask every
-    two or three steps (waam.run_layer_birth) never pays it."""
+    two or three steps (waam.run_layer_birth) never pays it.
+
+    WHETHER a FAST kernel runs at all also depends on the call: below theta * gamma = _lib.MIXED_MIN_TG the library sends
+    the whole sweep to the GENERAL kernels, and an axis-2 sweep with interface values (xlo / xhi) takes the thread-per-line
+    kernel.  Neither touches the queue word, so what is read back then is whatever the workspace held, and dt and theta are
+    per-call arguments under one pack set.  Such a sweep neither learns nor carries the bit (`tg`, `plain`)."""
     LEARN_AFTER = 3
 
-    def __init__(self, grid, pack, entry, axis, v, sp, work):
+    def __init__(self, grid, pack, entry, axis, v, sp, work, tg, plain=True):
         self.cache = pack.__dict__.setdefault('_nofb', {})
         self.key = (entry, axis, v, sp, grid.mask_version, getattr(pack, 'mask_version', None), grid.shape, grid.sx,
                     None if pack.d_dir_mask is None else pack.d_dir_mask.data_ptr())
         self.work = work
-        self.state = self.cache.get(self.key, 0) if ((sp & 1) and work is not None and work.numel() >= 4) else False
+        fast = (sp & 1) and work is not None and work.numel() >= 4 and tg >= _lib.MIXED_MIN_TG and plain
+        self.state = self.cache.get(self.key, 0) if fast else False
 
     @property
     def bit(self):
@@ -691,7 +697,8 @@ def _sweep_into(axis, t_in, t_out, grid, mat, params, pack, Tinf, variant=None, 
     _, work, wb = grid.scratch(2)
     v = pack.variant if variant is None else variant
     sp = _sparse_arg(grid, pack, dense)
-    nf = _NoFallback(grid, pack, 'sweep', axis, v, sp, work)
+    nf = _NoFallback(grid, pack, 'sweep', axis, v, sp, work, params.theta * gam,
+                     plain=not (axis == 2 and (xlo is not None or xhi is not None)))
     check(lib.adi_sweep_bricks(axis, v, _p(t_in), _p(grid.d_flags), _p(grid.d_bricks), _p(pack.d_coeff), _p(pack.d_dir_mask),
                         _p(pack.d_dir_val), _p(pack.d_qflux), *grid.layout.pd,
                         sp | nf.bit, params.theta,
@@ -716,12 +723,12 @@ def valid_range(t):
 def _explicit_sweep0_into(t, t_out, grid, mat, params, pack, Tinf, variant=None, dense=False):
     """stages 1+2 of adi_step_numba_coeff (adi3d_numba_coeff.py:292-299) in one pass: R0 is evaluated inside the
     loads of the axis-0 sweep.  Neighbours are read anywhere inside t's storage."""
-    kappa, _ = _gam(grid, mat, params)
+    kappa, gam = _gam(grid, mat, params)
     _, work, wb = grid.scratch(2)
     v = pack.variant if variant is None else variant
     vlo, vhi = valid_range(t)
     sp = _sparse_arg(grid, pack, dense)
-    nf = _NoFallback(grid, pack, 'fused', 0, v, sp, work)
+    nf = _NoFallback(grid, pack, 'fused', 0, v, sp, work, params.theta * gam)
     check(lib.adi_explicit_sweep0_bricks(v, _p(t), vlo, vhi, _p(grid.d_flags), _p(grid.d_bricks), _p(pack.d_coeff),
                                          _p(pack.d_dir_mask),
                                   _p(pack.d_dir_val), _p(pack.d_qflux), *grid.layout.pd,

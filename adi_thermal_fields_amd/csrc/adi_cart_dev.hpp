@@ -74,8 +74,9 @@ struct SweepScal {
     int sparse;   // 1: coeff / qflux are non-zero only on cells exposed along the sweep axis (packs built by
                   //    adi_build_coeffs), so they are loaded only there; dir_val only where dir_mask is set
     int nofb = 0; // promise (bit 2 of `sparse`): the FAST kernel takes every unit of this sweep -- the caller has seen the
-                  //    unit queue of the same (mask, packs, variant, shape) come back empty; the queue reset and the GENERAL
-                  //    launch behind the FAST kernel are skipped (3 + 3 launches of ~4.5 us and their gaps per step)
+                  //    unit queue of the same (mask, packs, variant, shape) come back empty AFTER A FAST KERNEL RAN (tg >=
+                  //    kMixedMinTg: below it no FAST kernel is launched and the queue word is nobody's); the queue reset and the
+                  //    GENERAL launch behind the FAST kernel are skipped (3 + 3 launches of ~4.5 us and their gaps per step)
     // Deferred interface correction of a slab decomposition (adi_sweep_corrected, strided axis 1 only): the value this
     // sweep reads at (plane i, row j, column k) is  in + c_w[i] * c_lo[j*nz + k] + c_w[c_n - 1 - i] * c_hi[j*nz + k]
     // -- the axis-0 sweep before it solved every line with zero boundary values, and by linearity the true solution

@@ -5,6 +5,7 @@
 #include <new>
 
 #include "adi_common.hpp"
+#include "adi_core.hpp"   // kMixedMinTg
 
 namespace adi {
 
@@ -279,12 +280,15 @@ int adi_ctx_step(adi_ctx *c, double rho, double cp, double k, double dt, double 
         return set_err(ADI_ERR_STATE, "adi_ctx_step: needs mask, packs (rebuilt after every mask change) and a field");
     ADI_HIP_TRY(hipSetDevice(c->device));
     ADI_HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    // dt and theta are per-call: below the gate (theta * gam as adi_step forms it) the sweeps run no FAST kernel, their queue
+    // counts read 0 whatever the mask, and a promise is neither learnt from such a step nor passed to it
+    const bool fast = theta * ((k / (rho * cp)) * dt / (c->dx * c->dx)) >= kMixedMinTg;
     for (int s = 0; s < nsteps; ++s) {
         const int nxt = c->cur ^ 1;
         const int sp = 1 | (c->all_solid ? 2 : 0);
         int rc;
-        if (c->promise < 0 && c->work != nullptr && c->work_bytes >= sizeof(unsigned)) {
-            // first step after a mask / pack change: count the units each sweep's FAST kernel queues (a function of the mask
+        if (fast && c->promise < 0 && c->work != nullptr && c->work_bytes >= sizeof(unsigned)) {
+            // first such step after a mask / pack change: count the units each sweep's FAST kernel queues (a function of the mask
             // and the packs, not of the field); if there are none, the later steps skip the queue reset and the fallback launch
             unsigned q[3];
             rc = adi_step_queued_bricks(c->T[c->cur], c->T[nxt], c->tmp[0], c->tmp[1], c->flags, c->bricks, c->coeff, c->dir_mask, c->dir_val,
@@ -295,7 +299,7 @@ int adi_ctx_step(adi_ctx *c, double rho, double cp, double k, double dt, double 
             c->promise = (q[0] == 0 && q[1] == 0 && q[2] == 0) ? 1 : 0;
         } else {
             rc = adi_step_bricks(c->T[c->cur], c->T[nxt], c->tmp[0], c->tmp[1], c->flags, c->bricks, c->coeff, c->dir_mask, c->dir_val, c->qflux,
-                          c->variant, sp | (c->promise == 1 ? 4 : 0), c->nx, c->ny, c->nz, c->sx, c->dx, rho, cp, k, dt, theta, Tinf,
+                          c->variant, sp | (fast && c->promise == 1 ? 4 : 0), c->nx, c->ny, c->nz, c->sx, c->dx, rho, cp, k, dt, theta, Tinf,
                           c->fconsts_ok ? c->fconsts : nullptr, c->work, c->work_bytes, c->stream);
             if (rc != ADI_OK) return rc;
         }

@@ -461,14 +461,20 @@ class HipEngine:
             self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._work
 
-    def _promise(self, entry, axis, variant, Li, flags, pack):
+    def _promise(self, entry, axis, variant, Li, flags, pack, tg):
         """(key, bit): which units the FAST kernels queue depends on the flags, the Dirichlet mask, the variant and the shape
-        only; a configuration seen to queue nothing skips the queue reset and the GENERAL launch from then on"""
+        only; a configuration seen to queue nothing skips the queue reset and the GENERAL launch from then on.  Below
+        tg = theta * gamma = MIXED_MIN_TG the library runs no FAST kernel and nobody writes the queue word: such a sweep
+        neither learns nor carries the bit (key None)"""
+        if not tg >= self._lib.MIXED_MIN_TG:
+            return None, 0
         key = (entry, axis, variant, Li.nx, Li.ny, Li.nz, Li.sx, flags.data_ptr(), pack[0].data_ptr(),
                None if pack[1] is None else pack[1].data_ptr(), self.box_hint, self.mask_epoch)
         return key, (4 if self._nofb.get(key) is True else 0)
 
     def _learn(self, key, w):
+        if key is None:
+            return
         st = self._nofb.get(key, 0)
         if st is True or st is False:
             return
@@ -480,7 +486,7 @@ class HipEngine:
     def sweep(self, axis, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf, t_out, xlo=None, xhi=None):
         h = self.hip
         w = self._workspace(Li)
-        key, bit = self._promise('sweep', axis, variant, Li, flags, pack)
+        key, bit = self._promise('sweep', axis, variant, Li, flags, pack, theta * gam)
         a = list(self._args(axis, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf))
         a[12] |= bit
         self.check(self.lib.adi_sweep(*a, h._p(t_out), h._p(xlo), h._p(xhi), self._fc(pack), h._p(w), w.numel(), self._sp()))
@@ -507,7 +513,7 @@ class HipEngine:
     def sweep0_fused(self, variant, L, T_ext, i0, j0, flags, pack, dx, dt, kappa, theta, Tinf, t_out, xlo=None, xhi=None):
         h = self.hip
         w = self._workspace(L)
-        key, bit = self._promise('fused', 0, variant, L, flags, pack)
+        key, bit = self._promise('fused', 0, variant, L, flags, pack, theta * (kappa * dt / (dx * dx)))
         a = list(self._fused_args(variant, L, T_ext, i0, j0, flags, pack, dx, dt, kappa, theta, Tinf))
         a[13] |= bit
         self.check(self.lib.adi_explicit_sweep0(*a, h._p(t_out), h._p(xlo), h._p(xhi), self._fc(pack), h._p(w), w.numel(),
@@ -569,7 +575,7 @@ class HipEngine:
         """axis-1 sweep of t_in + w[i] * ulo + w[n-1-i] * uhi (the correction is added to what the sweep loads)"""
         h = self.hip
         w = self._workspace(Li)
-        key, bit = self._promise('sweep', 1, variant, Li, flags, pack)
+        key, bit = self._promise('sweep', 1, variant, Li, flags, pack, theta * gam)
         a = list(self._args(1, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf))
         a[12] |= bit
         self.check(self.lib.adi_sweep_corrected(*a[1:], h._p(t_out), h._p(ulo), h._p(uhi), h._p(w_corr), self._fc(pack),

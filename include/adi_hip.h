@@ -180,6 +180,9 @@ int adi_explicit_rhs_planes(const double *d_T, const uint8_t *d_flags, int nx, i
  * depends on the flags, the Dirichlet mask, the variant, `sparse` and the shape only -- never on the field -- so a caller
  * may set the bit after it has seen the queue of an identical call come back empty: after a sweep without the bit the first
  * 32-bit word of d_work is the number of queued units (adi3d_hip_coeff.py does exactly that, once per mask / pack version).
+ * That word is written only by a sweep that launched a FAST kernel: not with theta * gam < 1e-9 (a vanishing time step: the
+ * GENERAL kernels take the whole sweep), not on axis 2 with d_xlo / d_xhi, not where the line length has no FAST kernel.
+ * What it holds after such a sweep says nothing about an identical call at another dt, theta or interface argument.
  * d_work/work_bytes (adi_sweep_workspace_bytes): c'/d' scratch for lines longer than the in-register limit,
  * otherwise the unit queue that lets a sparse sweep run as a FAST kernel (solid interior) followed by the
  * GENERAL kernel on the queued surface units; with NULL/0 the GENERAL kernel processes everything.
@@ -391,8 +394,11 @@ int adi_step(const double *d_T_in, double *d_T_out, double *d_tmp_a, double *d_t
              void *d_work, size_t work_bytes, void *stream);
 /* The same step, reporting in h_queued[axis] (three HOST words, valid once the stream is synchronised) how many units the
  * FAST kernel of each sweep handed to the GENERAL kernel.  That number depends on the flags, the Dirichlet mask, the
- * variant, `sparse` and the shape only, so three zeros license bit 2 of `sparse` (the no-fallback promise, see adi_sweep) on
- * every later step of the same configuration; adi_ctx_step does this on the first step after a mask / pack change. */
+ * variant, `sparse` and the shape -- not on the field -- so three zeros license bit 2 of `sparse` (the no-fallback promise,
+ * see adi_sweep) on every later step of the same configuration.  One exception: a step with theta * k dt / (rho cp dx^2)
+ * < 1e-9 runs no FAST kernel at all (a vanishing time step; theta = 0 included) and reports three zeros whatever the mask:
+ * zeros from such a step license nothing.  adi_ctx_step learns on the first step at or above that bound after a mask / pack
+ * change and passes the bit to such steps only. */
 int adi_step_queued(const double *d_T_in, double *d_T_out, double *d_tmp_a, double *d_tmp_b,
              const uint8_t *d_flags, const double *const *d_coeff, const uint8_t *d_dir_mask,
              const double *d_dir_val, const double *const *d_qflux, int variant, int sparse,

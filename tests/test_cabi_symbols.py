@@ -82,3 +82,12 @@ def test_face_constants_are_the_pack_values_bit_for_bit():
     hm2 = I6(1, 2, 1, 1, 1, 1)
     _lib.check(_lib.lib.adi_face_constants(dx, rho, cp, hm2, hs, qm, qs, consts, valid))
     assert list(valid) == [0, 1, 1]
+
+
+def test_mixed_min_tg_is_the_library_gate():
+    """_lib.MIXED_MIN_TG decides on the host which sweeps may learn or carry the no-fallback promise; it must be the very
+    gate below which the library runs no FAST kernel (kMixedMinTg, csrc/adi_core.hpp)"""
+    from adi_thermal_fields_amd import _lib
+    src = open(os.path.join(ROOT, 'adi_thermal_fields_amd', 'csrc', 'adi_core.hpp')).read()
+    m = re.findall(r'constexpr\s+double\s+kMixedMinTg\s*=\s*([0-9.eE+-]+)\s*;', src)
+    assert len(m) == 1 and float(m[0]) == _lib.MIXED_MIN_TG
