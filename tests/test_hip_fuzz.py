@@ -113,14 +113,17 @@ def test_random_case_device_resident_and_staged(seed):
 
 
 # ---- cylindrical BE step -------------------------------------------------------------------------------------------------
-# shapes on both sides of every condition of the FAST kernels (adi_cyl.hip: r -- the (phi, z) plane a multiple of 64 lines;
-# phi -- nz a multiple of 32, nphi a multiple of the segment length; z -- no Dirichlet closure, nz a multiple of 16 with a
-# power-of-two segment count), all nine z closures, source term, masked step, annular grids
+# shapes on both sides of every condition of the FAST kernels (adi_cyl.hip: r -- nr >= 64 with a power-of-two count of at
+# most 16 segments of 8 or 16 rows, and the (phi, z) plane a multiple of 64 lines; phi -- nphi >= 64 with a power-of-two count
+# of at most 32 segments of 8 (16 from nphi = 128) rows, and nz a multiple of 32; z -- no Dirichlet closure, nz >= 128 a multiple
+# of 16 with a power-of-two segment count, and nphi % (64 / (nz / 16)) == 0: a wave's lines lie in one radius plane), up to the
+# longest line the plan takes (1024; the deterministic cases of every switch are in test_cyl_switches_gpu.py), all nine z
+# closures, source term, masked step, annular grids
 def _cyl_case(seed):
     rng = np.random.default_rng(5000 + seed)
-    nr = int(rng.choice([1, 2, 5, 8, 16, 24, 64, 128]))
-    nphi = int(rng.choice([1, 2, 3, 8, 16, 36, 64, 128, 256]))
-    nz = int(rng.choice([3, 12, 16, 32, 40, 64, 128, 130, 256, 512]))
+    nr = int(rng.choice([1, 2, 5, 8, 16, 24, 64, 128, 256, 512]))
+    nphi = int(rng.choice([1, 2, 3, 8, 16, 36, 64, 128, 256, 512]))
+    nz = int(rng.choice([3, 12, 16, 32, 40, 64, 128, 130, 256, 512, 1024]))
     while nr * nphi * nz > 300000:
         if nphi >= nz and nphi > 8:
             nphi //= 2
