@@ -34,6 +34,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, check, ptr_array, FACES
+from ._ledger import PromiseLedger
 
 __all__ = ['Grid3D', 'Material', 'Params', 'AxisCoeffPack', 'exposed_mask', 'precompute_coeff_packs_unified',
            'adi_step_hip_coeff', 'adi_step_numba_coeff', 'adi_step_gpu_coeff', 'DeviceField', 'to_device',
@@ -61,6 +62,16 @@ def _stream():
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def _sweep_workspace_bytes(nx, ny, nz, sx):
+    """bytes of workspace that serve a sweep of the box along any axis (adi_sweep_workspace_bytes)"""
+    wb = 0
+    for ax in range(3):
+        b = ctypes.c_size_t(0)
+        check(lib.adi_sweep_workspace_bytes(ax, nx, ny, nz, sx, ctypes.byref(b)))
+        wb = max(wb, b.value)
+    return wb
 
 
 def recommended_dims(nx, ny, nz):
@@ -401,11 +412,7 @@ class Grid3D:
                 skew = 256 * (i + 1)
                 raw = torch.empty(L.numel_padded + skew, dtype=torch.float64, device=_device())
                 fields.append(raw[skew:skew + L.numel_padded].as_strided(L.shape, L.strides))
-            wb = 0
-            for ax in range(3):
-                b = ctypes.c_size_t(0)
-                check(lib.adi_sweep_workspace_bytes(ax, *self.layout.pd, ctypes.byref(b)))
-                wb = max(wb, b.value)
+            wb = _sweep_workspace_bytes(*L.pd)
             work = torch.empty(wb, dtype=torch.uint8, device=_device()) if wb else None
             self._scratch = (fields, work, wb)
         return self._scratch
@@ -651,45 +658,15 @@ def _sparse_arg(grid, pack, dense):
     return int(pack.sparse_ok and fresh and not dense) | (2 if getattr(grid, 'all_solid', False) else 0)
 
 
-class _NoFallback:
-    """Bit 2 of `sparse` (include/adi_hip.h): skip the queue reset and the GENERAL launch behind a FAST kernel that is known
-    to take every unit.  Which units a FAST kernel queues depends on the flags, the Dirichlet mask, the variant, the
-    `sparse` bits and the shape -- not on the field -- so the first sweep of a configuration runs without the bit, the
-    number of queued units is read back from the first word of the workspace (one 4-byte copy, once per mask / pack
-    version), and later sweeps of the same configuration carry the bit when that number was zero.  The read-back is a
-    host synchronisation, so it waits for the third sweep of a configuration: a layer-birth loop that changes the mask every
-    two or three steps (waam.run_layer_birth) never pays it.
-
-    WHETHER a FAST kernel runs at all also depends on the call: below theta * gamma = _lib.MIXED_MIN_TG the library sends
-    the whole sweep to the GENERAL kernels, and an axis-2 sweep with interface values (xlo / xhi) takes the thread-per-line
-    kernel.  Neither touches the queue word, so what is read back then is whatever the workspace held, and dt and theta are
-    per-call arguments under one pack set.  Such a sweep neither learns nor carries the bit (`tg`, `plain`)."""
-    LEARN_AFTER = 3
-
-    def __init__(self, grid, pack, entry, axis, v, sp, work, tg, plain=True):
-        self.cache = pack.__dict__.setdefault('_nofb', {})
-        self.key = (entry, axis, v, sp, grid.mask_version, getattr(pack, 'mask_version', None), grid.shape, grid.sx,
-                    None if pack.d_dir_mask is None else pack.d_dir_mask.data_ptr())
-        self.work = work
-        fast = (sp & 1) and work is not None and work.numel() >= 4 and tg >= _lib.MIXED_MIN_TG and plain
-        self.state = self.cache.get(self.key, 0) if fast else False
-
-    @property
-    def bit(self):
-        return 4 if self.state is True else 0
-
-    def learn(self):
-        st = self.state
-        if st is True or st is False:
-            return
-        st += 1                                   # uses of this configuration so far
-        if st >= self.LEARN_AFTER and not torch.cuda.is_current_stream_capturing():
-            st = int(self.work[:4].view(torch.int32)[0].item()) == 0
-        if self.key not in self.cache:            # a new configuration: entries of older mask versions are dead (a
-            cur = self.key[4]                     # layer-birth run would otherwise add three keys per birth for good)
-            for k in [k for k in self.cache if k[4] != cur]:
-                del self.cache[k]
-        self.cache[self.key] = st
+def _ledger_key(grid, pack, entry, axis, v, sp, work, tg, plain=True):
+    """-> (the PromiseLedger kept on the PACK: every stepper on it shares it; this call's key, None when not eligible)"""
+    nf = pack.__dict__.get('_nofb')
+    if nf is None:
+        nf = pack._nofb = PromiseLedger()
+    if not nf.eligible(sp, work, tg, plain):
+        return nf, None
+    return nf, (entry, axis, v, sp, grid.mask_version, getattr(pack, 'mask_version', None), grid.shape, grid.sx,
+                None if pack.d_dir_mask is None else pack.d_dir_mask.data_ptr())
 
 
 def _sweep_into(axis, t_in, t_out, grid, mat, params, pack, Tinf, variant=None, xlo=None, xhi=None, dense=False):
@@ -697,15 +674,15 @@ def _sweep_into(axis, t_in, t_out, grid, mat, params, pack, Tinf, variant=None, 
     _, work, wb = grid.scratch(2)
     v = pack.variant if variant is None else variant
     sp = _sparse_arg(grid, pack, dense)
-    nf = _NoFallback(grid, pack, 'sweep', axis, v, sp, work, params.theta * gam,
-                     plain=not (axis == 2 and (xlo is not None or xhi is not None)))
+    nf, key = _ledger_key(grid, pack, 'sweep', axis, v, sp, work, params.theta * gam,
+                          plain=not (axis == 2 and (xlo is not None or xhi is not None)))
     check(lib.adi_sweep_bricks(axis, v, _p(t_in), _p(grid.d_flags), _p(grid.d_bricks), _p(pack.d_coeff), _p(pack.d_dir_mask),
                         _p(pack.d_dir_val), _p(pack.d_qflux), *grid.layout.pd,
-                        sp | nf.bit, params.theta,
+                        sp | nf.bit(key), params.theta,
                         gam, params.dt, float(Tinf), _p(t_out),
                         _p(xlo), _p(xhi), _fc_arg(grid, pack, sp),
                         _p(work), wb, _stream()))
-    nf.learn()
+    nf.learn(key, work, grid.mask_version)
 
 
 def fused_supported(grid, cond_pass=False):
@@ -728,13 +705,13 @@ def _explicit_sweep0_into(t, t_out, grid, mat, params, pack, Tinf, variant=None,
     v = pack.variant if variant is None else variant
     vlo, vhi = valid_range(t)
     sp = _sparse_arg(grid, pack, dense)
-    nf = _NoFallback(grid, pack, 'fused', 0, v, sp, work, params.theta * gam)
+    nf, key = _ledger_key(grid, pack, 'fused', 0, v, sp, work, params.theta * gam)
     check(lib.adi_explicit_sweep0_bricks(v, _p(t), vlo, vhi, _p(grid.d_flags), _p(grid.d_bricks), _p(pack.d_coeff),
                                          _p(pack.d_dir_mask),
                                   _p(pack.d_dir_val), _p(pack.d_qflux), *grid.layout.pd,
-                                  sp | nf.bit, grid.dx, params.dt, kappa, params.theta,
+                                  sp | nf.bit(key), grid.dx, params.dt, kappa, params.theta,
                                   float(Tinf), _p(t_out), None, None, _fc_arg(grid, pack, sp), _p(work), wb, _stream()))
-    nf.learn()
+    nf.learn(key, work, grid.mask_version)
 
 
 def adi_explicit_sweep_axis0(Tn, grid, mat, params, pack, Tinf=0.0, variant=None, dense=False):
@@ -824,18 +801,18 @@ def _step_field_source(Tn, grid, mat, params, packs, Tinf, S):
 
 
 def _source_block(owner):
-    """the device parameter block of a moving source (ADI_SOURCE_BLOCK_BYTES), one per grid / stepper"""
+    """the device parameter block of a moving source (ADI_SOURCE_BLOCK_BYTES), one per grid / stepper / engine"""
     blk = getattr(owner, '_src_block', None)
     if blk is None or blk.device != _device():
         blk = owner._src_block = torch.zeros(_lib.SOURCE_BLOCK_BYTES, dtype=torch.uint8, device=_device())
     return blk
 
 
-def _source_work(owner, grid, src):
-    """workspace of adi_source_lines0 (lines longer than the in-register limit only; None otherwise), one per grid /
-    stepper, grown when a larger support needs more"""
+def _source_work(owner, dims, dx, src):
+    """workspace of adi_source_lines0 on a box of `dims` = (nx, ny, nz) (lines longer than the in-register limit only; None
+    otherwise), one per grid / stepper / engine, grown when a larger support needs more"""
     b = ctypes.c_size_t(0)
-    check(lib.adi_source_workspace_bytes(ctypes.byref(src.as_c()), *grid.layout.pd[:3], grid.dx, ctypes.byref(b)))
+    check(lib.adi_source_workspace_bytes(ctypes.byref(src.as_c()), *dims, dx, ctypes.byref(b)))
     if b.value == 0:
         return None
     w = getattr(owner, '_src_work', None)
@@ -849,7 +826,7 @@ def _source_lines0_into(U, grid, mat, params, pack, src, owner):
     are `owner`'s"""
     _, gam = _gam(grid, mat, params)
     sp = _sparse_arg(grid, pack, False)
-    work = _source_work(owner, grid, src)
+    work = _source_work(owner, grid.layout.pd[:3], grid.dx, src)
     check(lib.adi_source_lines0(_p(_source_block(owner)), ctypes.byref(src.as_c()), _p(U), _p(grid.d_flags),
                                 _p(pack.d_coeff), _p(pack.d_dir_mask if pack.has_dir else None), *grid.layout.pd, sp,
                                 grid.dx, params.theta, gam, params.dt, mat.rho, mat.cp, _fc_arg(grid, pack, sp),

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
-from .adi3d_hip_coeff import DeviceField, Layout, to_device, _device, _stream, _p, _wrap
+from .adi3d_hip_coeff import DeviceField, Layout, to_device, _device, _stream, _p, _wrap, _source_block
 
 __all__ = ['StagedCylStepper', 'CylGoldakSource', 'GridCyl', 'Material', 'Params', 'RobinR', 'ZBC', 'adi_step', 'adi_step_masked', 'DeviceField', 'to_device']
 
@@ -168,14 +168,6 @@ class CylGoldakSource:
 
     def set_block(self, blk, t0, dt, n=0):
         check(lib.adi_cyl_source_set(_p(blk), ctypes.byref(self.as_c()), float(t0), float(dt), int(n), _stream()))
-
-
-def _source_block(owner):
-    """the device parameter block of a moving source (ADI_SOURCE_BLOCK_BYTES), one per grid / stepper"""
-    blk = getattr(owner, '_src_block', None)
-    if blk is None or blk.device != _device():
-        blk = owner._src_block = torch.zeros(_lib.SOURCE_BLOCK_BYTES, dtype=torch.uint8, device=_device())
-    return blk
 
 
 class _Plan:

@@ -362,11 +362,12 @@ class HipEngine:
     def __init__(self):
         from . import adi3d_hip_coeff as hip
         from . import _lib
+        from ._ledger import PromiseLedger
         self.hip, self._lib, self.lib, self.check = hip, _lib, _lib.lib, _lib.check
         self.device = hip._device()
         self.box_hint = 0          # 2: every cell of every slab is in the mask (SlabStepper.set_mask decides, collectively)
         self.mask_epoch = 0        # bumped by SlabStepper.set_mask: the flags / packs are rebuilt in place
-        self._nofb = {}            # no-fallback promise per sweep configuration (bit 2 of `sparse`, include/adi_hip.h)
+        self._nofb = PromiseLedger()   # no-fallback promise per sweep configuration (bit 2 of `sparse`); set_mask clears it
         self._fconsts = {}         # coefficient storage -> per-face scalars of the pack built on it (h_face_consts)
         self._stream_ptr = None    # launch stream of the step in progress (SlabStepper.step pins it: one lookup per step)
         self._wb = {}              # workspace bytes per box shape
@@ -441,61 +442,44 @@ class HipEngine:
         self.check(self.lib.adi_explicit_rhs_planes(h._p(T_ext), h._p(flags_ext), L.nx, L.ny, L.nz, L.sx, dx, dt, kappa,
                                                     theta, h._p(out_ext), i_begin, i_end, self._sp()))
 
-    def _args(self, axis, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf):
+    def _args(self, variant, Li, t_in, flags, pack, sparse, theta, gam, dt, Tinf):
         h = self.hip
-        return (axis, variant, h._p(t_in), h._p(flags), h._p(pack[0]), h._p(pack[1]), h._p(pack[2]), h._p(pack[3]),
-                Li.nx, Li.ny, Li.nz, Li.sx, 1 | self.box_hint, theta, gam, dt, float(Tinf))   # packs from adi_build_coeffs: sparse
+        return (variant, h._p(t_in), h._p(flags), h._p(pack[0]), h._p(pack[1]), h._p(pack[2]), h._p(pack[3]),
+                Li.nx, Li.ny, Li.nz, Li.sx, sparse, theta, gam, dt, float(Tinf))
 
     def _workspace(self, Li):
         """unit queue of the FAST/GENERAL kernel pair (sized for the largest box seen)"""
         key = (Li.nx, Li.ny, Li.nz, Li.sx)
         need = self._wb.get(key)
         if need is None:
-            need = 0
-            for ax in range(3):
-                b = ctypes.c_size_t(0)
-                self.check(self.lib.adi_sweep_workspace_bytes(ax, Li.nx, Li.ny, Li.nz, Li.sx, ctypes.byref(b)))
-                need = max(need, b.value)
-            self._wb[key] = need
+            need = self._wb[key] = self.hip._sweep_workspace_bytes(*key)
         if getattr(self, '_work', None) is None or self._work.numel() < need:
             self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._work
 
-    def _promise(self, entry, axis, variant, Li, flags, pack, tg):
-        """(key, bit): which units the FAST kernels queue depends on the flags, the Dirichlet mask, the variant and the shape
-        only; a configuration seen to queue nothing skips the queue reset and the GENERAL launch from then on.  Below
-        tg = theta * gamma = MIXED_MIN_TG the library runs no FAST kernel and nobody writes the queue word: such a sweep
-        neither learns nor carries the bit (key None)"""
-        if not tg >= self._lib.MIXED_MIN_TG:
-            return None, 0
-        key = (entry, axis, variant, Li.nx, Li.ny, Li.nz, Li.sx, flags.data_ptr(), pack[0].data_ptr(),
-               None if pack[1] is None else pack[1].data_ptr(), self.box_hint, self.mask_epoch)
-        return key, (4 if self._nofb.get(key) is True else 0)
-
-    def _learn(self, key, w):
-        if key is None:
-            return
-        st = self._nofb.get(key, 0)
-        if st is True or st is False:
-            return
-        st += 1                    # the read-back synchronises the host: wait for the third sweep of a configuration
-        if st >= 3 and not torch.cuda.is_current_stream_capturing():
-            st = int(w[:4].view(torch.int32)[0].item()) == 0
-        self._nofb[key] = st
+    def _nofb_begin(self, entry, axis, variant, Li, flags, pack, tg, plain=True):
+        """first half of a sweep under the no-fallback promise (_ledger.PromiseLedger) -> (workspace, key, `sparse` with the
+        bit); the caller launches with them and ends with self._nofb.learn(key, workspace)"""
+        w = self._workspace(Li)
+        sp, key = 1 | self.box_hint, None         # packs from adi_build_coeffs: sparse
+        if self._nofb.eligible(sp, w, tg, plain):
+            key = (entry, axis, variant, Li.nx, Li.ny, Li.nz, Li.sx, flags.data_ptr(), pack[0].data_ptr(),
+                   None if pack[1] is None else pack[1].data_ptr(), self.box_hint, self.mask_epoch)
+        return w, key, sp | self._nofb.bit(key)
 
     def sweep(self, axis, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf, t_out, xlo=None, xhi=None):
         h = self.hip
-        w = self._workspace(Li)
-        key, bit = self._promise('sweep', axis, variant, Li, flags, pack, theta * gam)
-        a = list(self._args(axis, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf))
-        a[12] |= bit
-        self.check(self.lib.adi_sweep(*a, h._p(t_out), h._p(xlo), h._p(xhi), self._fc(pack), h._p(w), w.numel(), self._sp()))
-        self._learn(key, w)
+        w, key, sp = self._nofb_begin('sweep', axis, variant, Li, flags, pack, theta * gam,
+                                      plain=not (axis == 2 and (xlo is not None or xhi is not None)))
+        self.check(self.lib.adi_sweep(axis, *self._args(variant, Li, t_in, flags, pack, sp, theta, gam, dt, Tinf), h._p(t_out),
+                                      h._p(xlo), h._p(xhi), self._fc(pack), h._p(w), w.numel(), self._sp()))
+        self._nofb.learn(key, w)
 
     def condense(self, axis, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf, cond):
         h = self.hip
         w = self._workspace(Li)
-        self.check(self.lib.adi_sweep_condense(*self._args(axis, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf),
+        self.check(self.lib.adi_sweep_condense(axis, *self._args(variant, Li, t_in, flags, pack, 1 | self.box_hint, theta,
+                                                                 gam, dt, Tinf),
                                                h._p(cond), self._fc(pack), h._p(w), w.numel(), self._sp()))
 
     # explicit stage folded into the axis-0 sweep / condensation (ABI v7).  The box (L.nx, L.ny, L.nz) starts at plane
@@ -503,22 +487,21 @@ class HipEngine:
     def fused_supported(self, nx, ny, nz, sx, cond_pass):
         return bool(self.lib.adi_explicit_fused_supported(nx, ny, nz, sx, 1 if cond_pass else 0))
 
-    def _fused_args(self, variant, L, T_ext, i0, j0, flags, pack, dx, dt, kappa, theta, Tinf):
+    def _fused_args(self, variant, L, T_ext, i0, j0, flags, pack, sparse, dx, dt, kappa, theta, Tinf):
         h = self.hip
         tv = T_ext[i0:i0 + L.nx, j0:j0 + L.ny, :]
         vlo, vhi = h.valid_range(tv)
         return (variant, h._p(tv), vlo, vhi, h._p(flags), h._p(pack[0]), h._p(pack[1]), h._p(pack[2]), h._p(pack[3]),
-                L.nx, L.ny, L.nz, L.sx, 1 | self.box_hint, dx, dt, kappa, theta, float(Tinf))
+                L.nx, L.ny, L.nz, L.sx, sparse, dx, dt, kappa, theta, float(Tinf))
 
     def sweep0_fused(self, variant, L, T_ext, i0, j0, flags, pack, dx, dt, kappa, theta, Tinf, t_out, xlo=None, xhi=None):
         h = self.hip
-        w = self._workspace(L)
-        key, bit = self._promise('fused', 0, variant, L, flags, pack, theta * (kappa * dt / (dx * dx)))
-        a = list(self._fused_args(variant, L, T_ext, i0, j0, flags, pack, dx, dt, kappa, theta, Tinf))
-        a[13] |= bit
-        self.check(self.lib.adi_explicit_sweep0(*a, h._p(t_out), h._p(xlo), h._p(xhi), self._fc(pack), h._p(w), w.numel(),
+        w, key, sp = self._nofb_begin('fused', 0, variant, L, flags, pack, theta * (kappa * dt / (dx * dx)))
+        self.check(self.lib.adi_explicit_sweep0(*self._fused_args(variant, L, T_ext, i0, j0, flags, pack, sp, dx, dt, kappa,
+                                                                  theta, Tinf),
+                                                h._p(t_out), h._p(xlo), h._p(xhi), self._fc(pack), h._p(w), w.numel(),
                                                 self._sp()))
-        self._learn(key, w)
+        self._nofb.learn(key, w)
 
     # deferred form of the sharded-axis sweep (include/adi_hip.h, ABI v12): every line solved with zero boundary values by
     # the single-domain kernel, one plane to each neighbour, 2 x 2 interface systems, and the rank-two correction added by
@@ -574,13 +557,11 @@ class HipEngine:
     def sweep_corrected(self, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf, t_out, ulo, uhi, w_corr):
         """axis-1 sweep of t_in + w[i] * ulo + w[n-1-i] * uhi (the correction is added to what the sweep loads)"""
         h = self.hip
-        w = self._workspace(Li)
-        key, bit = self._promise('sweep', 1, variant, Li, flags, pack, theta * gam)
-        a = list(self._args(1, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf))
-        a[12] |= bit
-        self.check(self.lib.adi_sweep_corrected(*a[1:], h._p(t_out), h._p(ulo), h._p(uhi), h._p(w_corr), self._fc(pack),
+        w, key, sp = self._nofb_begin('sweep', 1, variant, Li, flags, pack, theta * gam)
+        self.check(self.lib.adi_sweep_corrected(*self._args(variant, Li, t_in, flags, pack, sp, theta, gam, dt, Tinf),
+                                                h._p(t_out), h._p(ulo), h._p(uhi), h._p(w_corr), self._fc(pack),
                                                 h._p(w), w.numel(), self._sp()))
-        self._learn(key, w)
+        self._nofb.learn(key, w)
 
     # the deferred form for lines that are not uniform (ABI v17): per-line homogeneous solutions
     def homogeneous_solution(self, variant, Li, flags, pack, theta, gam, dt, lower):
@@ -597,9 +578,8 @@ class HipEngine:
         # (dense reads, no face constants: the coefficient arrays as they are; a one-off per plan)
         h = self.hip
         w = self._workspace(Li)
-        a = list(self._args(0, v, Li, zero, flags, pk, theta, gam, dt, 0.0))
-        a[12] = 0
-        self.check(self.lib.adi_sweep(*a, h._p(out), h._p(one if lower else None), h._p(None if lower else one), None,
+        self.check(self.lib.adi_sweep(0, *self._args(v, Li, zero, flags, pk, 0, theta, gam, dt, 0.0), h._p(out),
+                                      h._p(one if lower else None), h._p(None if lower else one), None,
                                       h._p(w), w.numel(), self._sp()))
         return out
 
@@ -627,8 +607,8 @@ class HipEngine:
         """r0_out (optional, a view of the box in an array laid out like T_ext): also receives R0"""
         h = self.hip
         w = self._workspace(L)
-        self.check(self.lib.adi_explicit_condense0(*self._fused_args(variant, L, T_ext, i0, j0, flags, pack, dx, dt,
-                                                                     kappa, theta, Tinf),
+        self.check(self.lib.adi_explicit_condense0(*self._fused_args(variant, L, T_ext, i0, j0, flags, pack, 1 | self.box_hint,
+                                                                     dx, dt, kappa, theta, Tinf),
                                                    h._p(cond), h._p(r0_out), self._fc(pack), h._p(w), w.numel(), self._sp()))
 
     # pass A folded into the marching explicit kernel: dot products of R0 with fixed weights (uniform lines), the rest
@@ -684,22 +664,14 @@ class HipEngine:
     # moving heat source (include/adi_hip.h, "Volumetric heat source"): one device block and one workspace per rank
     def source_set(self, src, t, dt):
         """the block of this rank: `src` (a GoldakSource) for the step that starts at t"""
-        if getattr(self, '_src_block', None) is None:
-            self._src_block = torch.zeros(self._lib.SOURCE_BLOCK_BYTES, dtype=torch.uint8, device=self.device)
-        self.check(self.lib.adi_source_set(self.hip._p(self._src_block), ctypes.byref(src.as_c()), float(t), float(dt), 0,
+        h = self.hip
+        self.check(self.lib.adi_source_set(h._p(h._source_block(self)), ctypes.byref(src.as_c()), float(t), float(dt), 0,
                                            self._sp()))
 
     def source_lines0(self, src, Li, U, flags, pack, dx, theta, gam, dt, rho, cp, i_org):
         """U += A0^-1 s on the slab's axis-0 lines with zero values beyond both ends (the deferred forms' local solve)"""
         h = self.hip
-        b = ctypes.c_size_t(0)
-        self.check(self.lib.adi_source_workspace_bytes(ctypes.byref(src.as_c()), Li.nx, Li.ny, Li.nz, dx,
-                                                       ctypes.byref(b)))
-        work = None
-        if b.value:
-            work = getattr(self, '_src_work', None)
-            if work is None or work.numel() < b.value:
-                work = self._src_work = torch.empty(b.value, dtype=torch.uint8, device=self.device)
+        work = h._source_work(self, (Li.nx, Li.ny, Li.nz), dx, src)
         self.check(self.lib.adi_source_lines0_slab(h._p(self._src_block), ctypes.byref(src.as_c()), h._p(U), h._p(flags),
                                                    h._p(pack[0]), h._p(pack[1]), Li.nx, Li.ny, Li.nz, Li.sx, int(i_org),
                                                    1 | self.box_hint, dx, theta, gam, dt, rho, cp, self._fc(pack),

@@ -1,6 +1,6 @@
 """GPU: the stateful layers above the Cartesian kernels driven through SEQUENCES of calls -- the context half of the C ABI
-(adi_ctx_*, raw ctypes as a non-Python consumer of include/adi_hip.h would drive it), and _NoFallback / StagedStepper of the
-Python host -- with dt and theta changing under one pack set.  Every number is compared with oracle.adi_oracle stepped
+(adi_ctx_*, raw ctypes as a non-Python consumer of include/adi_hip.h would drive it), and PromiseLedger / StagedStepper /
+HipEngine of the Python hosts -- with dt and theta changing under one pack set.  Every number is compared with oracle.adi_oracle stepped
 through the same sequence, at the project's bar rel_linf <= 1e-10.
 
 Why: the no-fallback promise (bit 2 of `sparse`) is learnt from the unit queue of a sweep, and a sweep with
@@ -198,7 +198,7 @@ def _py_sequence(api, step, T, grid, packs, calls):
 
 
 def test_python_host_promise_is_not_carried_across_the_time_step_gate():
-    """The same defect one layer up: _NoFallback keeps what it learnt on the PACK, so every stepper on those packs shares it.
+    """The same defect one layer up: the single-domain host keeps its PromiseLedger on the PACK, so every stepper on those packs shares it.
     One Grid3D, a Dirichlet plane (queues at an ordinary step), the queue word of the workspace at 0 as after any sweep that
     queued nothing.  (1) adi_step_hip_coeff: LEARN_AFTER steps at gam = 1e-10, then 3 at gam = 60, same packs.  (2)
     StagedStepper A (gam = 1e-10) through step / run(graph=False) / run(graph=True), then stepper B (gam = 60) on the same
@@ -208,6 +208,7 @@ def test_python_host_promise_is_not_carried_across_the_time_step_gate():
     units unsolved.  (Figures of the unfixed host on hardware: not measured yet; both rel_linf values are printed.)"""
     import torch
     import adi_thermal_fields_amd.adi3d_hip_coeff as hip
+    from adi_thermal_fields_amd._ledger import PromiseLedger
     from oracle import adi_oracle as orc
     mask, dm, dv = promise_config('dirichlet_plane')
     tiny, ordi = dt_of(GAM_TINY, DX), dt_of(60.0, DX)
@@ -224,7 +225,7 @@ def test_python_host_promise_is_not_carried_across_the_time_step_gate():
         _, work, _ = grid.scratch(2)
         work[:4].zero_()
     # (1) the step function
-    n_learn = hip._NoFallback.LEARN_AFTER
+    n_learn = PromiseLedger.LEARN_AFTER
     calls = [(tiny, n_learn), (ordi, 3)]
     packs = fresh_packs()
     zero_queue_word()
@@ -253,6 +254,96 @@ def test_python_host_promise_is_not_carried_across_the_time_step_gate():
     assert not any(v is True for p in packs for v in p._nofb.values())
     plain = _py_sequence(hip, hip.adi_step_hip_coeff, hip.to_device(T0), grid, fresh_packs(), calls).get()
     assert np.array_equal(got, plain)                      # the same kernels, with or without a graph
+
+
+class _EngineSlab:
+    """one slab that is the whole box, on one HipEngine and no communicator: extended arrays with empty halo planes, flags and
+    packs from E.build_flags / E.build_packs the way SlabStepper.set_mask builds them, interior views for the sweeps"""
+
+    def __init__(self, E, mask, dm, dv, T0):
+        import torch
+        import adi_thermal_fields_amd.adi3d_hip_coeff as hip
+        nx, ny, nz = mask.shape
+        assert E.plane_dims(ny, nz) == (ny, nz)                  # no padded planes at this shape
+
+        def ext(a, fill):
+            e = np.full((nx + 2, ny, nz), fill, dtype=a.dtype)
+            e[1:-1] = a
+            return e
+        self.E, self.Lext, self.Li = E, E.layout(nx + 2, ny, nz), E.layout(nx, ny, nz)
+        assert self.Li.sx == self.Lext.sx
+        d_mask = self.Lext.to_layout(ext(mask, False), torch.uint8)
+        flags = E.build_flags(self.Lext, d_mask)
+        packs = E.build_packs(self.Lext, d_mask, flags, DX, hip.Material(RHO, CP, K), ext(dm, False), ext(dv, 0.0), None, 300.0)
+        self.v, self.fl = packs[0].variant, flags[1:-1]
+        self.pk = [tuple(None if t is None else t[1:-1] for t in (p.d_coeff, p.d_dir_mask, p.d_dir_val, p.d_qflux))
+                   for p in packs]
+        self.keep = (d_mask, flags, packs)
+        self.Text = self.Lext.to_layout(ext(T0, 0.0), torch.float64)
+        self.out = [self.Lext.empty(zero=True)[1:-1] for _ in range(2)]
+        self.zero, self.ones = E.vec(ny * nz), E.vec(nx).fill_(1.0)
+
+    def run(self, form, gam):
+        """one call of each entry point of `form` at theta = 0.5 -> the outputs"""
+        E, Li, Ti, dt, th = self.E, self.Li, self.Text[1:-1], dt_of(gam, DX), 0.5
+        if form == 'sweep':                                      # axis 0 (256 rows: FAST kernel, queue), then axis 1 (16 rows)
+            E.sweep(0, self.v, Li, Ti, self.fl, self.pk[0], th, gam, dt, 20.0, self.out[0])
+            E.sweep(1, self.v, Li, Ti, self.fl, self.pk[1], th, gam, dt, 20.0, self.out[1])
+            return self.out
+        if form == 'fused':
+            E.sweep0_fused(self.v, Li, self.Text, 1, 0, self.fl, self.pk[0], DX, dt, ALPHA, th, 20.0, self.out[0])
+        else:
+            E.sweep_corrected(self.v, Li, Ti, self.fl, self.pk[1], th, gam, dt, 20.0, self.out[0], self.zero, self.zero,
+                              self.ones)
+        return self.out[:1]
+
+
+def test_slab_engine_promise_is_not_carried_across_the_time_step_gate():
+    """The same defect in the other Python host: dist_slab.HipEngine keeps its PromiseLedger on the ENGINE, under keys of data
+    pointers.  One engine, the box as one slab, a Dirichlet plane (queues at an ordinary step), the queue word of the engine's
+    workspace at 0; LEARN_AFTER calls of E.sweep at gam = 1e-10, then three at gam = 60.  Afterwards no entry of E._nofb is True,
+    the last output equals bit for bit that of an engine that never saw the small time step, and it agrees with adi_sweep_axis
+    of the single-domain host.  Then the same, bit for bit, for sweep0_fused and for sweep_corrected with zero ulo / uhi.
+    Every call of E.sweep(1, ...) is preceded by E.sweep(0, ...) with the same arguments, as in a step: axis 1 of this box has
+    16 rows, below the 64 from which a strided FAST kernel exists (strided_plan, csrc/adi_cart_host.hpp), so on its own it
+    neither queues anything nor writes the queue word -- nothing would be at stake, and the third call at gam = 60 would read
+    back the 0 this test put there.  Along axis 0 (256 rows) the FAST kernel runs and queues the Dirichlet tiles: its entry
+    must come out False (asserted), and the read-back of axis 1 then sees that count, as it does inside a step.
+    Without the fix, by the code: the vanishing sweeps read the stale 0 and learn True, and the gam = 60 sweeps along axis 0
+    leave the queued tiles unsolved.  On an MI355X: every entry False after each form, rel_linf 8.4e-16 (axis 0) and
+    2.6e-15 (axis 1) against adi_sweep_axis."""
+    import torch
+    import adi_thermal_fields_amd.adi3d_hip_coeff as hip
+    from adi_thermal_fields_amd import dist_slab
+    from adi_thermal_fields_amd._ledger import PromiseLedger
+    mask, dm, dv = promise_config('dirichlet_plane')
+    T0 = np.random.default_rng(8).uniform(20.0, 900.0, SHAPE_P)
+    taught, fresh = (_EngineSlab(dist_slab.HipEngine(), mask, dm, dv, T0) for _ in range(2))
+    E = taught.E
+    for form in ('sweep', 'fused', 'corrected'):
+        E._workspace(taught.Li)[:4].zero_()
+        before = dict(E._nofb)
+        for _ in range(PromiseLedger.LEARN_AFTER):
+            taught.run(form, GAM_TINY)
+        assert dict(E._nofb) == before                             # a sweep below the gate does not even count
+        for _ in range(3):
+            got = taught.run(form, 60.0)
+        want = fresh.run(form, 60.0)
+        torch.cuda.synchronize()
+        print(form, 'E._nofb:', list(E._nofb.values()), 'fresh:', list(fresh.E._nofb.values()))
+        assert not any(v is True for v in E._nofb.values())
+        for a, b in zip(got, want):
+            assert torch.equal(a, b), form
+        if form == 'sweep':
+            assert [v for k, v in E._nofb.items() if k[1] == 0] == [False]      # axis 0 did queue: something was at stake
+            grid = hip.Grid3D(*SHAPE_P, DX, mask)
+            mat = hip.Material(RHO, CP, K)
+            packs = hip.precompute_coeff_packs_unified(grid, mat, robin_h=300.0, dir_mask=dm, dir_value=dv)
+            for axis in (0, 1):
+                ref = hip.adi_sweep_axis(axis, T0, grid, mat, hip.Params(dt_of(60.0, DX), 0.5), packs[axis], Tinf=20.0)
+                e = rel_linf(got[axis].cpu().numpy(), ref)
+                print('E.sweep(%d) against adi_sweep_axis: rel_linf' % axis, e)
+                assert e <= TOL, (axis, e)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
