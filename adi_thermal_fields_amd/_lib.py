@@ -161,6 +161,8 @@ SIGNATURES = {
     'adi_source_workspace_bytes': (c_int, [c_void_p, c_int, c_int, c_int, c_double, ctypes.POINTER(c_size_t)]),
     'adi_explicit_rhs_src': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double,
                                      c_double, c_double, c_double, c_void_p, c_void_p]),
+    'adi_surface_loss_update': (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double,
+                                        c_double, c_double, c_void_pp, c_int, c_int, c_int, c_void_p]),
     'adi_cyl_source_set': (c_int, [c_void_p, c_void_p, c_double, c_double, ctypes.c_longlong, c_void_p]),
     'adi_cyl_source_sample': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double, c_double,
                                       c_void_p, c_void_p, c_void_p]),
@@ -182,6 +184,8 @@ MIXED_MIN_TG = 1e-9           # kMixedMinTg (csrc/adi_core.hpp): below this thet
 MAX_BOX_CELLS = 1 << 32       # ADI_MAX_BOX_CELLS: nx * plane_stride of a Cartesian box stays below it
 SOURCE_BLOCK_BYTES = 128     # ADI_SOURCE_BLOCK_BYTES
 SOURCE_E_CUT = 40.0          # ADI_SOURCE_E_CUT
+SURFACE_LOSS_MAX_KNOTS = 16  # ADI_SURFACE_LOSS_MAX_KNOTS
+SURFACE_LOSS_SIGMA = 5.670374419e-8   # ADI_SURFACE_LOSS_SIGMA (Stefan-Boltzmann, CODATA 2018)
 STLCORR_DROPPED = (1 << 63) - 1   # ADI_STLCORR_DROPPED
 STLCORR_MAX_SUBDIV = 4096    # ADI_STLCORR_MAX_SUBDIV
 
@@ -191,6 +195,12 @@ class HeatSource(ctypes.Structure):
     _fields_ = [('power', c_double), ('eta', c_double), ('a', c_double), ('b', c_double), ('c_f', c_double),
                 ('c_r', c_double), ('f_f', c_double), ('origin', c_double * 3), ('velocity', c_double),
                 ('travel_axis', c_int), ('travel_sign', c_int), ('depth_axis', c_int), ('reserved', c_int)]
+
+
+class SurfaceLossLaw(ctypes.Structure):
+    """adi_surface_loss (include/adi_hip.h)"""
+    _fields_ = [('h', c_double * 6), ('emissivity', c_double * 6), ('T_offset', c_double), ('n_knots', c_int),
+                ('reserved', c_int), ('knot_T', c_double * 16), ('knot_h', c_double * 16)]
 
 
 CYL_DEPTHS = {'z': 0, 'r': 1}   # ADI_CYL_DEPTH_Z, ADI_CYL_DEPTH_R

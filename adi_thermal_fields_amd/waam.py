@@ -109,8 +109,10 @@ def _birth(backend, T, grid, newborn, Ts):
 
 
 def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, layers, times_birth, times_out,
-                    on_frame=None, device_resident=True, device_loop=True):
-    """The event loop of waam_from_stl_v7_mm.py:515-550.  Returns (T_final as NumPy, number of ADI steps)."""
+                    on_frame=None, device_resident=True, device_loop=True, surface_loss=None):
+    """The event loop of waam_from_stl_v7_mm.py:515-550.  Returns (T_final as NumPy, number of ADI steps).
+    surface_loss (a SurfaceLoss of the backend): the surface loses heat by that law, evaluated at the temperature at the start
+    of every sub-step, in place of the constant `h` (which is then not used); device loop only.  None: the reference's loop."""
     nx, ny, nz = mask_full.shape
     mask_act = np.zeros_like(mask_full, dtype=bool)
     grid = backend.Grid3D(nx, ny, nz, dx, mask_act)
@@ -135,7 +137,13 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         params.dt = max(seg / nsub, 1e-15)
         if nsub >= GRAPH_MIN_NSUB and hasattr(backend, 'StagedStepper') and hasattr(T, 'fill_where'):
             # a long segment on the device backend: the nsub launches of this segment replayed from a HIP graph
-            T = backend.StagedStepper(grid, mat, params, packs, Tinf).run(T, nsub)
+            if surface_loss is None:
+                T = backend.StagedStepper(grid, mat, params, packs, Tinf).run(T, nsub)
+            else:
+                T = backend.StagedStepper(grid, mat, params, packs, Tinf, surface_loss=bpacks).run(T, nsub)
+        elif surface_loss is not None:
+            for _ in range(nsub):
+                T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, surface_loss=bpacks)
         else:
             for _ in range(nsub):
                 T = _step(backend, T, grid, mat, params, packs, Tinf)
@@ -147,12 +155,17 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     # and one plane either side) -- in place, no allocation, no host synchronisation: nothing crosses PCIe between
     # output times and nothing waits for the device between births
     dev_loop = device_loop and device_resident and hasattr(backend, 'BirthPacks') and hasattr(T, 'fill_where')
+    if surface_loss is not None and not (dev_loop and hasattr(backend, 'LossPacks')):
+        raise ValueError("run_layer_birth: surface_loss needs the device loop of a backend with LossPacks")
     if dev_loop:
         import torch
         d_full = grid.layout.to_layout(mask_full, torch.uint8)
         d_act = grid.layout.empty(torch.uint8, zero=True)
         grid.set_mask_device(d_act, all_solid=False)
-        bpacks = backend.BirthPacks(grid, mat, robin_h=robin)
+        # (with a surface loss: LossPacks, whose coefficients follow the field -- `update` ahead of every sub-step, inside the
+        # step; `rebuild` on the planes a birth changed)
+        bpacks = backend.BirthPacks(grid, mat, robin_h=robin) if surface_loss is None else \
+            backend.LossPacks(grid, mat, surface_loss, Tinf)
         packs = bpacks.packs
         plane_cells = np.asarray(mask_full).sum(axis=(0, 1)).astype(np.int64)      # newborn cells per plane, host-known
         plane_born = np.zeros(nz, dtype=bool)
@@ -168,7 +181,10 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
             n_active += int(plane_cells[ks:ke + 1][fresh].sum())
             plane_born[ks:ke + 1] = True
             grid.set_mask_device(d_act, ks - 1 if ks > 0 else 0, min(nz, ke + 2), all_solid=False)   # :494-495
-            packs = bpacks.update(ks - 1, ke + 2)                                 # :534, the planes that changed
+            if surface_loss is None:
+                packs = bpacks.update(ks - 1, ke + 2)                             # :534, the planes that changed
+            else:
+                packs = bpacks.rebuild(T, ks - 1, ke + 2)
             return
         born = np.zeros_like(mask_full, dtype=bool)
         born[:, :, ks:ke + 1] = mask_full[:, :, ks:ke + 1]
@@ -203,11 +219,14 @@ def track_source(heat_source, track_box, dx, yi, t_step):
 
 
 def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_track, theta, dt, t_step,
-                     device_resident=True, heat_source=None):
+                     device_resident=True, heat_source=None, surface_loss=None):
     """single_track_on_plate.py:150-177: the deposit advances one column per t_step along axis 1; packs are
     rebuilt after every column.  track_box = (x0, x1, z0, z1, n_columns).
     heat_source (a GoldakSource of the backend): the arc / laser as a moving volumetric source (track_source) during the
-    sub-steps of every column, on top of the newborn cells set to T_track.  None: the reference's driver, unchanged."""
+    sub-steps of every column, on top of the newborn cells set to T_track.  None: the reference's driver, unchanged.
+    surface_loss (a SurfaceLoss of the backend): the surface loses heat by that law, evaluated at the temperature at the start
+    of every sub-step, in place of the constant `h`; device loop only; columns of at least GRAPH_MIN_NSUB sub-steps are
+    replayed from a HIP graph.  None: the constant-h packs, unchanged."""
     x0, x1, z0, z1, ncol = track_box
     nx, ny, nz = plate_mask.shape
     mask = plate_mask.copy()
@@ -219,9 +238,12 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         T = backend.to_device(T)
     robin = {f: h for f in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')}
     dev_loop = device_resident and hasattr(grid, 'set_mask_device') and hasattr(T, 'fill_where')
+    if surface_loss is not None and not (dev_loop and hasattr(backend, 'LossPacks')):
+        raise ValueError("run_single_track: surface_loss needs the device loop of a backend with LossPacks")
     if dev_loop:                                    # the mask lives in HBM: a new column is two slice assignments
         import torch
         d_mask = grid.layout.to_layout(mask, torch.uint8)
+    lpacks = backend.LossPacks(grid, mat, surface_loss, Tinf) if surface_loss is not None else None
     for yi in range(ncol):
         if dev_loop:
             d_mask[x0:x1, yi:yi + 1, z0:z1] = 1
@@ -229,12 +251,23 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         else:
             mask[x0:x1, yi:yi + 1, z0:z1] = True
             grid.mask = mask
-        packs = backend.precompute_coeff_packs_unified(grid, mat, robin_h=robin, robin_Tinf=Tinf)
+        if lpacks is None:
+            packs = backend.precompute_coeff_packs_unified(grid, mat, robin_h=robin, robin_Tinf=Tinf)
         T[x0:x1, yi:yi + 1, z0:z1] = T_track
+        if lpacks is not None:
+            packs = lpacks.rebuild(T)                # the column changed the exposure: every cell, stale ones zeroed
         n_sub = max(1, int(math.ceil(t_step / dt)))
         dt_orig = params.dt
         params.dt = t_step / n_sub
-        if heat_source is None:
+        if lpacks is not None:
+            src = None if heat_source is None else track_source(heat_source, track_box, dx, yi, t_step)
+            if n_sub >= GRAPH_MIN_NSUB:
+                T = backend.StagedStepper(grid, mat, params, packs, Tinf, source=src, surface_loss=lpacks).run(T, n_sub, t0=0.0)
+            else:
+                for i in range(n_sub):
+                    T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=src, t=i * params.dt,
+                                                     surface_loss=lpacks)
+        elif heat_source is None:
             for _ in range(n_sub):
                 T = _step(backend, T, grid, mat, params, packs, Tinf)
         else:

@@ -622,6 +622,46 @@ int adi_explicit_rhs_src(const double *d_T, const double *d_S, const uint8_t *d_
                          double *d_R0, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Temperature-dependent surface loss of the Cartesian step (no counterpart in the reference, which freezes robin_h when the
+ * packs are built; it accepts per-voxel robin_h, so the lagged law below is a sequence of calls the reference can run).
+ * Before a step the Robin coefficient of every exposed cell is rewritten from the cell's own temperature T (degrees, the
+ * field's unit) at the START of the step.  For face f, with T in the cell, ambient Tinf and SIGMA = 5.670374419e-8:
+ *     Tk  = T + T_offset                      Ta = Tinf + T_offset                      (kelvin)
+ *     rad = ((emissivity[f]*SIGMA) * (Tk*Tk + Ta*Ta)) * (Tk + Ta)
+ *     tab = knot_h[j] + ((knot_h[j+1]-knot_h[j])/(knot_T[j+1]-knot_T[j])) * (T - knot_T[j])   for knot_T[j] <= T < knot_T[j+1],
+ *           knot_h[0] below the first knot, knot_h[n_knots-1] from the last knot on; 0 without a table and on a face whose
+ *           h[f] and emissivity[f] are both 0
+ *     h_f = (h[f] + tab) + rad
+ *     coeff[axis] += (h_f * dx^2 / (rho cp dx^3))    on cells exposed on face f, '-' face first, then '+'
+ * every operation IEEE fp64 in this order, no contraction: the arrays are bit-identical to adi_build_coeffs with the six
+ * h_f fields.  The radiation's ambient is the step's Tinf, the one the Robin term of the sweeps relaxes to.
+ * Valid: finite values, h[f] >= 0, 0 <= emissivity[f] <= 1, n_knots 0 or 2..ADI_SURFACE_LOSS_MAX_KNOTS with strictly
+ * increasing knot_T, Tinf + T_offset > 0.  Everything else is ADI_ERR_ARG, checked before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADI_SURFACE_LOSS_MAX_KNOTS 16
+#define ADI_SURFACE_LOSS_SIGMA 5.670374419e-8
+typedef struct adi_surface_loss {
+    double h[6];            /* convection coefficient per face [W/m^2/K]: x-, x+, y-, y+, z-, z+ */
+    double emissivity[6];   /* per face */
+    double T_offset;        /* field unit -> kelvin (273.15 for degrees Celsius) */
+    int n_knots, reserved;  /* 0: no table */
+    double knot_T[ADI_SURFACE_LOSS_MAX_KNOTS];
+    double knot_h[ADI_SURFACE_LOSS_MAX_KNOTS];
+} adi_surface_loss;
+
+/* Rewrites d_coeff[0..2] (the pack arrays of the three axes, box layout) from d_T on the planes [k_begin, k_end) of axis 2.
+ * Exposure comes from d_flags (adi_build_nbr_flags: in mask, and a neighbour bit of the axis clear).
+ * full = 0 (every step): writes d_coeff[axis] only at in-mask cells exposed along that axis, reads d_T only at cells with an
+ *   exposed face, and with d_bricks (adi_build_flag_bricks for the same flags; NULL: none) skips the bricks that hold no such
+ *   cell without reading their flags.  Nothing else is touched.
+ * full = 1 (a new pack set, or the planes a birth changed): also writes exact zeros to every other cell of those planes, so
+ *   a cell that stopped being exposed keeps no stale coefficient.
+ * The law travels by value in the launch: a captured graph keeps the law it was captured with. */
+int adi_surface_loss_update(const adi_surface_loss *h_law, double Tinf, const double *d_T, const uint8_t *d_flags,
+                            const uint32_t *d_bricks, int nx, int ny, int nz, long plane_stride, double dx, double rho,
+                            double cp, double *const d_coeff[3], int k_begin, int k_end, int full, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Moving heat source of the cylindrical step.  For a step t_n -> t_n + dt:
  *     R0 = Tn + dt * q(x_c, t_n + dt/2) / (rho*cp)
  * and the three sweeps run unchanged.  Cell centres r_i = r_in + (i+1/2) dr, phi_j = (j+1/2) dphi, z_k = (k+1/2) dz (z from
