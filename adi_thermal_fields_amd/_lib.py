@@ -163,6 +163,11 @@ SIGNATURES = {
                                      c_double, c_double, c_double, c_void_p, c_void_p]),
     'adi_surface_loss_update': (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double,
                                         c_double, c_double, c_void_pp, c_int, c_int, c_int, c_void_p]),
+    'adi_phase_summary_words': (ctypes.c_long, [c_int, c_int, c_int]),
+    'adi_phase_apply': (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                c_int, c_long, c_void_p]),
+    'adi_phase_seed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                               c_long, c_void_p]),
     'adi_cyl_source_set': (c_int, [c_void_p, c_void_p, c_double, c_double, ctypes.c_longlong, c_void_p]),
     'adi_cyl_source_sample': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double, c_double,
                                       c_void_p, c_void_p, c_void_p]),
@@ -201,6 +206,11 @@ class SurfaceLossLaw(ctypes.Structure):
     """adi_surface_loss (include/adi_hip.h)"""
     _fields_ = [('h', c_double * 6), ('emissivity', c_double * 6), ('T_offset', c_double), ('n_knots', c_int),
                 ('reserved', c_int), ('knot_T', c_double * 16), ('knot_h', c_double * 16)]
+
+
+class PhaseChangeLaw(ctypes.Structure):
+    """adi_phase_change (include/adi_hip.h)"""
+    _fields_ = [('latent_heat', c_double), ('T_solidus', c_double), ('T_liquidus', c_double)]
 
 
 CYL_DEPTHS = {'z': 0, 'r': 1}   # ADI_CYL_DEPTH_Z, ADI_CYL_DEPTH_R

@@ -40,7 +40,7 @@ __all__ = ['Grid3D', 'Material', 'Params', 'AxisCoeffPack', 'exposed_mask', 'pre
            'adi_step_hip_coeff', 'adi_step_numba_coeff', 'adi_step_gpu_coeff', 'DeviceField', 'to_device',
            'adi_explicit_rhs', 'adi_sweep_axis', 'StagedStepper', 'Layout', 'apply_surface_impulse_Q',
            'exposed_faces_per_layer', 'count_exposed_faces', 'perimeter_ratio', 'birth_planes', 'BirthPacks',
-           'GoldakSource', 'SurfaceLoss', 'LossPacks']
+           'GoldakSource', 'SurfaceLoss', 'LossPacks', 'PhaseChange', 'PhaseField']
 
 
 # Mask versions come from ONE process-wide counter: a pack remembers the version of the mask it was built for, and a
@@ -756,7 +756,7 @@ def _loss_update(surface_loss, packs, t_in, Tinf):
     surface_loss.update(t_in, Tinf)
 
 
-def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None):
+def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None, phase=None):
     """adi3d_numba_coeff.py:290-302 / adi3d_gpu_coeff.py:213-230: explicit stage, then the three
     implicit sweeps in the order axis 0, 1, 2.  Returns a NEW array of the kind it was given;
     `Tn` is never modified.
@@ -768,9 +768,12 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     to the output of sweep 0 by superposition (adi_source_lines0), after whichever sweep-0 form the step uses.
     t: the step's start time, used only by a source object.
     surface_loss: a LossPacks whose `.packs` are `packs`: their Robin coefficients are first rewritten from Tn (the law at the
-    temperature at the start of the step, adi_surface_loss_update), then the step runs as above.  None: no such launch."""
+    temperature at the start of the step, adi_surface_loss_update), then the step runs as above.  None: no such launch.
+    phase: a PhaseField of the grid: after sweep 2 the step's output is corrected for the latent heat from the liquid fraction
+    the PhaseField holds, which moves on with it (adi_phase_apply, the last launch, on the freshly allocated output).  None: no
+    such launch."""
     if S is not None and not isinstance(S, GoldakSource):
-        return _step_field_source(Tn, grid, mat, params, packs, Tinf, S, surface_loss)
+        return _step_field_source(Tn, grid, mat, params, packs, Tinf, S, surface_loss, phase)
     t_in, kind = _as_state(Tn, grid)
     if surface_loss is not None:
         _loss_update(surface_loss, packs, t_in, Tinf)
@@ -789,6 +792,8 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
         _source_lines0_into(tb, grid, mat, params, packx, S, grid)
     _sweep_into(1, tb, ta, grid, mat, params, packy, Tinf)
     _sweep_into(2, ta, out, grid, mat, params, packz, Tinf)
+    if phase is not None:
+        _phase_apply(phase, out, grid, mat, packs)
     return _wrap(out, kind)
 
 
@@ -798,7 +803,7 @@ def _explicit_src_into(t, d_S, out, grid, mat, params):
                                    params.theta, mat.rho, mat.cp, _p(out), _stream()))
 
 
-def _step_field_source(Tn, grid, mat, params, packs, Tinf, S, surface_loss=None):
+def _step_field_source(Tn, grid, mat, params, packs, Tinf, S, surface_loss=None, phase=None):
     """the step with a source FIELD: R0 with the source, then the three unfused sweeps"""
     t, kind = _as_state(Tn, grid)
     if surface_loss is not None:
@@ -812,6 +817,8 @@ def _step_field_source(Tn, grid, mat, params, packs, Tinf, S, surface_loss=None)
     _sweep_into(0, ta, tb, grid, mat, params, packs[0], Tinf)
     _sweep_into(1, tb, ta, grid, mat, params, packs[1], Tinf)
     _sweep_into(2, ta, out, grid, mat, params, packs[2], Tinf)
+    if phase is not None:
+        _phase_apply(phase, out, grid, mat, packs)
     return _wrap(out, kind)
 
 
@@ -1245,6 +1252,215 @@ class LossPacks:
         return self.packs
 
 
+# ---- latent heat of melting and freezing (include/adi_hip.h) -----------------------------------------
+class PhaseChange:
+    """Latent heat `latent_heat` [J/kg] released between `T_solidus` and `T_liquidus` (the field's unit), linearly in T: on
+    the equilibrium curve the liquid fraction is f_eq(T) = min(max((T - Ts)/(Tl - Ts), 0), 1).  The step runs at constant cp
+    from the state (T, f); afterwards the cell's enthalpy cp*T + L*f is put back on the curve (temperature recovery: lagged,
+    first order in dt).  `correct` is the definition, adi_phase_apply the same operations on the device."""
+
+    def __init__(self, latent_heat, T_solidus, T_liquidus):
+        self.latent_heat, self.T_solidus, self.T_liquidus = latent_heat, T_solidus, T_liquidus
+        self.validate()
+
+    def validate(self):
+        """ValueError for anything adi_phase_change rejects (include/adi_hip.h).  -> (L, Ts, Tl) as floats"""
+        try:
+            L, Ts, Tl = float(self.latent_heat), float(self.T_solidus), float(self.T_liquidus)
+        except (TypeError, ValueError):
+            raise ValueError("PhaseChange: latent_heat, T_solidus and T_liquidus must be real numbers")
+        if not (np.isfinite(L) and np.isfinite(Ts) and np.isfinite(Tl)):
+            raise ValueError("PhaseChange: non-finite parameter")
+        if not L > 0.0:
+            raise ValueError("PhaseChange: latent_heat must be > 0")
+        if not Tl > Ts:
+            raise ValueError("PhaseChange: T_liquidus must be above T_solidus")
+        return L, Ts, Tl
+
+    def as_c(self):
+        return _lib.PhaseChangeLaw(*self.validate())
+
+    def key(self):
+        """every parameter of the law: a launch takes it by value, so a captured graph holds the law of its capture"""
+        return self.validate()
+
+    def constants(self, cp):
+        """(dT, Hs, Hl, cm) for heat capacity cp, each one fp64 operation, as the library's host code evaluates them"""
+        L, Ts, Tl = self.validate()
+        cp = float(cp)
+        if not (np.isfinite(cp) and cp > 0.0):
+            raise ValueError("PhaseChange: cp must be finite and > 0")
+        dT = Tl - Ts
+        Hs = cp * Ts
+        h1 = cp * Tl
+        Hl = h1 + L
+        r = L / dT
+        cm = cp + r
+        return dT, Hs, Hl, cm
+
+    def f_eq(self, T):
+        """the liquid fraction on the equilibrium curve at temperatures T (ndarray)"""
+        _, Ts, Tl = self.validate()
+        T = np.asarray(T, dtype=np.float64)
+        dT = Tl - Ts
+        e = T - Ts
+        x = e / dT
+        x = np.where(x < 0.0, 0.0, x)
+        return np.where(x > 1.0, 1.0, x)
+
+    def correct(self, T_star, f, mask, dir_mask, cp):
+        """(T, f) after the correction of the step's result T_star from the liquid fraction f it started with: THE DEFINITION
+        of the law -- one fp64 operation per line, in the order the kernel performs them.  mask: the grid's mask; dir_mask: the
+        Dirichlet cells (None: none).  Off-mask cells, Dirichlet cells and cells at rest keep T_star and f bit for bit."""
+        L, Ts, Tl = self.validate()
+        dT, Hs, Hl, cm = self.constants(cp)
+        cp = float(cp)
+        Tst = np.asarray(T_star, dtype=np.float64)
+        f = np.asarray(f, dtype=np.float64)
+        act = np.asarray(mask, dtype=bool)
+        if dir_mask is not None:
+            act = act & ~np.asarray(dir_mask, dtype=bool)
+        rest = ((f == 0.0) & (Tst <= Ts)) | ((f == 1.0) & (Tst >= Tl))
+        act = act & ~rest
+        h1 = cp * Tst
+        h2 = L * f
+        H = h1 + h2
+        # H <= Hs: all solid
+        Ta = H / cp
+        # H >= Hl: all liquid
+        d1 = H - L
+        Tb = d1 / cp
+        # between: on the mushy branch of the curve
+        d2 = H - Hs
+        q = d2 / cm
+        Tc = Ts + q
+        e = Tc - Ts
+        x = e / dT
+        x = np.where(x < 0.0, 0.0, x)
+        fc = np.where(x > 1.0, 1.0, x)
+        lo, hi = H <= Hs, H >= Hl
+        Tn = np.where(lo, Ta, np.where(hi, Tb, Tc))
+        fn = np.where(lo, 0.0, np.where(hi, 1.0, fc))
+        return np.where(act, Tn, Tst), np.where(act, fn, f)
+
+
+class PhaseField:
+    """The liquid fraction of a grid under a PhaseChange law, on the device: `f` (fp64, the grid's layout, 0 off the mask) and
+    the phase summary (one word per 16^3 brick, 0 exactly when every f of the brick is 0: adi_phase_apply far from the melt
+    pool reads T once and nothing else).  Both buffers live as long as the object, so a StagedStepper's graph holds their
+    pointers.  T (optional): the field f is seeded from, f = f_eq(T) on the mask; without it everything is solid.
+    dir_mask (optional): the Dirichlet cells of `apply` calls that are not given any (the step passes its pack's).
+        apply(T)              the correction on a device field in the grid's layout, T and f in place: one launch
+        seed(T, sel=None)     f = f_eq(T) on the in-mask cells `sel` selects (None: all), 0 off the mask
+        sync_mask(T)          after `grid.mask` changed: the cells that joined the mask are seeded from T, those that left it
+                              are zeroed, every other cell keeps its f
+        snapshot() / restore(s), copy_state_from(other)     f and the summary"""
+
+    def __init__(self, grid, mat, law, T=None, dir_mask=None):
+        if not isinstance(law, PhaseChange):
+            raise TypeError("PhaseField: law must be a PhaseChange")
+        law.constants(mat.cp)
+        self.grid, self.mat, self.law = grid, mat, law
+        L = grid.layout
+        self._flat = torch.zeros(L.numel_padded, dtype=torch.float64, device=_device())
+        self.f = self._flat.as_strided(L.shape, L.strides)
+        self.summary = torch.zeros(self._words(), dtype=torch.int32, device=_device())
+        self.d_dir_mask = None if dir_mask is None else L.to_layout(dir_mask, torch.uint8)
+        self._seen = None
+        self._mask_version = None
+        if T is not None:
+            self.seed(T)
+        else:
+            self._remember_mask()
+
+    def _words(self):
+        n = int(lib.adi_phase_summary_words(*self.grid.layout.pd[:3]))
+        if n <= 0:
+            raise ValueError("PhaseField: bad grid")
+        return n
+
+    def _remember_mask(self):
+        self._seen = self.grid.d_mask.clone()
+        self._mask_version = self.grid.mask_version
+
+    def _native(self, T):
+        t = T.t if isinstance(T, DeviceField) else T
+        if not self.grid.layout.is_native(t) or t.dtype != torch.float64:
+            t = self.grid.layout.to_layout(T, torch.float64)
+        return t
+
+    @property
+    def liquid_fraction(self):
+        """a copy of f as a DeviceField of the grid's shape"""
+        return DeviceField(self.f).copy()
+
+    def apply(self, T, d_dir_mask=None):
+        """adi_phase_apply on T (a DeviceField or device tensor in the grid's layout), in place; d_dir_mask: the Dirichlet
+        cells as a uint8 device tensor in the grid's layout (default: the ones given at construction)"""
+        g = self.grid
+        t = T.t if isinstance(T, DeviceField) else T
+        if not g.layout.is_native(t) or t.dtype != torch.float64:
+            raise ValueError("PhaseField.apply: T must be a fp64 device field in the grid's layout (it is corrected in place)")
+        if g.mask_version != self._mask_version:
+            raise ValueError("PhaseField: the grid's mask changed since the liquid fraction was seeded; call sync_mask(T)")
+        assert self.summary.numel() == self._words()
+        dm = self.d_dir_mask if d_dir_mask is None else d_dir_mask
+        if dm is not None:
+            assert g.layout.is_native(dm) and dm.dtype == torch.uint8
+        check(lib.adi_phase_apply(ctypes.byref(self.law.as_c()), float(self.mat.cp), _p(t), _p(self.f), _p(g.d_flags),
+                                  _p(g.d_bricks), _p(dm), _p(self.summary), *g.layout.pd, _stream()))
+        return T
+
+    def seed(self, T, sel=None):
+        """adi_phase_seed: f = f_eq(T) on the in-mask cells `sel` selects (bool / uint8 array or tensor of the grid's shape;
+        None: every in-mask cell), 0 off the mask; the summary is rewritten"""
+        g = self.grid
+        d_sel = None if sel is None else g.layout.to_layout(sel, torch.uint8)
+        assert self.summary.numel() == self._words()
+        check(lib.adi_phase_seed(ctypes.byref(self.law.as_c()), _p(self._native(T)), _p(self.f), _p(g.d_flags), _p(g.d_bricks),
+                                 _p(d_sel), _p(self.summary), *g.layout.pd, _stream()))
+        self._remember_mask()
+
+    def sync_mask(self, T):
+        """after a mask change: seed the cells that joined the mask since the last seed / sync from T, zero those that left"""
+        g = self.grid
+        if g.mask_version == self._mask_version:
+            return
+        newborn = (g.d_mask != 0) & (self._seen == 0)
+        self.seed(T, sel=newborn)
+
+    def set_liquid_fraction(self, f):
+        """load f (array / tensor / DeviceField of the grid's shape; taken as 0 off the mask) and rebuild the summary from it
+        on the device: a seed that selects no cell keeps every in-mask f, zeroes the rest and rewrites every entry"""
+        g = self.grid
+        self.f.copy_(g.layout.to_layout(f, torch.float64))
+        self.seed(g.layout.empty(zero=True), sel=g.layout.empty(torch.uint8, zero=True))
+
+    def snapshot(self):
+        return self._flat.clone(), self.summary.clone()
+
+    def restore(self, s):
+        self._flat.copy_(s[0])
+        self.summary.copy_(s[1])
+
+    def copy_state_from(self, other):
+        if other.grid.layout.pd != self.grid.layout.pd:
+            raise ValueError("PhaseField.copy_state_from: the grids differ in layout")
+        self._flat.copy_(other._flat)
+        self.summary.copy_(other.summary)
+
+
+def _phase_apply(phase, out, grid, mat, packs):
+    """the last launch of a step with `phase=`: the correction of the step's own output buffer"""
+    if not isinstance(phase, PhaseField):
+        raise TypeError("phase must be a PhaseField")
+    if phase.grid is not grid:
+        raise ValueError("phase: the PhaseField belongs to another grid")
+    if float(phase.mat.cp) != float(mat.cp):
+        raise ValueError("phase: the PhaseField was made for cp = %r, the step runs with %r" % (phase.mat.cp, mat.cp))
+    phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
+
+
 # the reference's backend-specific names, so its drivers run unchanged on this module
 adi_step_numba_coeff = adi_step_hip_coeff
 adi_step_gpu_coeff = adi_step_hip_coeff
@@ -1254,9 +1470,11 @@ class StagedStepper:
     """The step of adi_step_hip_coeff with its arguments resolved once, for tight loops over a
     device-resident field (drivers call the step `nsub` times with the same packs and dt,
     quick_compare_dirichlet_robin.py:169-178).  `events`: optional list of 5 torch.cuda.Event recorded on
-    the launch stream before/between/after the four stage kernels (per-stage HIP-event timing)."""
+    the launch stream before/between/after the four stage kernels (per-stage HIP-event timing).  With `phase=` (a PhaseField
+    of the grid) the latent-heat correction is the last launch of every step, after the last of the five marks: the stage
+    times stay those of the stage kernels."""
 
-    def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None, surface_loss=None):
+    def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None, surface_loss=None, phase=None):
         self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
         # temperature-dependent surface loss: the packs' Robin coefficients rewritten from the step's INPUT buffer, the first
         # launch of every step -- captured with it (X -> Y reads X, Y -> X reads Y); the law travels by value in that launch,
@@ -1267,6 +1485,16 @@ class StagedStepper:
             if len(packs) != 3 or any(p is not q for p, q in zip(packs, surface_loss.packs)):
                 raise ValueError("StagedStepper: surface_loss needs its own packs (surface_loss.packs) as `packs`")
         self.surface_loss = surface_loss
+        # latent heat: the correction of the step's OUTPUT buffer, the last launch of every step -- captured with it; the law
+        # travels by value and f and the summary by pointer, so all three are part of run()'s graph key
+        if phase is not None:
+            if not isinstance(phase, PhaseField):
+                raise TypeError("StagedStepper: phase must be a PhaseField")
+            if phase.grid is not grid:
+                raise ValueError("StagedStepper: the PhaseField belongs to another grid")
+            if float(phase.mat.cp) != float(mat.cp):
+                raise ValueError("StagedStepper: the PhaseField was made for another cp")
+        self.phase = phase
         if source is not None and not isinstance(source, GoldakSource):
             raise TypeError("StagedStepper: source must be a GoldakSource (pass a source field to adi_step_numba_coeff)")
         # moving source: corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step counter
@@ -1307,6 +1535,8 @@ class StagedStepper:
             check(lib.adi_source_tick(_p(_source_block(self)), _stream()))
         self.sweep_into(1, tb, ta)
         self.sweep_into(2, ta, out)
+        if self.phase is not None:
+            _phase_apply(self.phase, out, g, self.mat, self.packs)
 
     def run(self, T, nsteps, graph=True, t0=0.0):
         """The drivers' `nsub` loop (quick_compare_dirichlet_robin.py:169-178, waam_from_stl_v7_mm.py:525-528): `nsteps`
@@ -1323,7 +1553,9 @@ class StagedStepper:
                tuple(getattr(p, 'mask_version', None) for p in self.packs),
                tuple(None if p.d_coeff is None else p.d_coeff.data_ptr() for p in self.packs), self.fused,
                None if self.source is None else self.source.shape_key(),
-               None if self.surface_loss is None else self.surface_loss.loss.key())
+               None if self.surface_loss is None else self.surface_loss.loss.key(),
+               None if self.phase is None else (self.phase.law.key(), self.phase.f.data_ptr(), self.phase.summary.data_ptr(),
+                                                None if self.phase.d_dir_mask is None else self.phase.d_dir_mask.data_ptr()))
         st = getattr(self, '_graph', None)
         if st is None or st['key'] != key:
             X, Y = g.layout.empty(), g.layout.empty()
@@ -1334,9 +1566,12 @@ class StagedStepper:
             self.source.set_block(_source_block(self), t0, prm.dt)
         if graph and nsteps >= 2 and st['g'] is None:
             g.scratch(2)                                   # every buffer exists before the capture
+            held = None if self.phase is None else self.phase.snapshot()   # (the warm-up steps would advance f)
             self._step_into(X, Y); self._step_into(Y, X)   # warm-up outside the capture (lazy module loads, and the
             self._step_into(X, Y); self._step_into(Y, X)   # no-fallback promise is learnt on the third step); harmless:
             X.copy_(g.layout.to_layout(T, torch.float64))  # X is restored
+            if held is not None:
+                self.phase.restore(held)                   # ... and so are f and the phase summary
             torch.cuda.synchronize()
             cg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(cg):
@@ -1392,4 +1627,6 @@ class StagedStepper:
         mark()
         self.sweep_into(2, ta, out)
         mark()
+        if self.phase is not None:
+            _phase_apply(self.phase, out, g, self.mat, self.packs)
         return DeviceField(out)

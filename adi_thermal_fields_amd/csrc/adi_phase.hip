@@ -1,0 +1,280 @@
+// adi_phase.hip -- latent heat of melting and freezing of the Cartesian step (include/adi_hip.h, "Latent heat"): after the
+// three sweeps the enthalpy cp*T + L*f of every in-mask, non-Dirichlet cell is put back on the equilibrium curve.
+//   k_phase_apply   every step, T and f in place
+//   k_phase_seed    f = f_eq(T) on selected in-mask cells, 0 off the mask (construction, newborn cells)
+// One workgroup of 256 threads per 16 x 16 x 16 brick of the flags summary; it owns the brick's cells and the brick's word of
+// the phase summary, so nothing is shared between workgroups and no atomic is needed.  A row piece of the brick is 16 doubles
+// = 128 bytes: lane l of a wave owns cells 2(l & 7), 2(l & 7) + 1 of row (l >> 3), so one 16-byte load instruction of a wave
+// covers eight whole 128-byte row pieces, and the eight loads of a thread cover the 256 rows of the brick.  The loads of a
+// thread are issued together ahead of the arithmetic; stores go cell by cell (8 bytes) so that a cell the law leaves alone is
+// never written.  No existing kernel changes.
+#include <math.h>
+
+#include "adi_cart_host.hpp"
+
+namespace adi {
+
+// the law as the kernels take it: the host constants of the header, each one fp64 operation
+struct PhaseLaw {
+    double cp, L, Ts, Tl;
+    double dT, Hs, Hl, cm;
+};
+
+constexpr int kPhaseIter = 8;     // row groups of a brick per thread: 256 rows / (256 threads / 8 lanes per row)
+
+struct PhaseCell {
+    long p;          // offset of the pair's first cell
+    unsigned in;     // bit c: cell c of the pair lies inside the box
+    unsigned m;      // bit c: ... and in the mask
+};
+
+// 16-byte access needs even row and plane strides and 16-byte aligned arrays (host: `vec`); then a pair never straddles the
+// end of a row.  Otherwise cell by cell.
+template <bool VEC>
+__device__ __forceinline__ void load_pair(const double *__restrict__ a, const PhaseCell &c, double &v0, double &v1)
+{
+    if (VEC) {
+        const double2 v = *reinterpret_cast<const double2 *>(a + c.p);
+        v0 = v.x; v1 = v.y;
+    } else {
+        v0 = a[c.p];
+        v1 = (c.in & 2u) ? a[c.p + 1] : 0.0;
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ unsigned load_mask_pair(const uint8_t *__restrict__ flags, const PhaseCell &c)
+{
+    if (VEC) {
+        const unsigned v = *reinterpret_cast<const unsigned short *>(flags + c.p);
+        return (v & 1u) | ((v >> 7) & 2u);
+    }
+    unsigned m = flags[c.p] & 1u;
+    if (c.in & 2u) m |= (flags[c.p + 1] & 1u) << 1;
+    return m;
+}
+
+// the pair of cells thread `tid` owns in row group `it` of brick (bi, bj, bk)
+__device__ __forceinline__ PhaseCell phase_cell(const Lay &L, int bi, int bj, int bk, int it, unsigned tid)
+{
+    const int row = it * 32 + (int)(tid >> 3);
+    const int i = bi * kBrick + (row >> 4), j = bj * kBrick + (row & 15), k = bk * kBrick + 2 * (int)(tid & 7u);
+    PhaseCell c;
+    c.p = (long)i * L.sx + (long)j * L.nz + k;
+    c.in = (i < L.nx && j < L.ny && k < L.nz) ? ((k + 1 < L.nz) ? 3u : 1u) : 0u;
+    c.m = 0u;
+    return c;
+}
+
+__device__ __forceinline__ bool brick_all_solid(const unsigned *__restrict__ bricks, const Lay &L, int bi, int bj, int bk)
+{
+    if (bricks == nullptr) return false;
+    const int nbx = (L.nx + kBrick - 1) / kBrick, nbz = (L.nz + kBrick - 1) / kBrick;
+    return (bricks[brick_word(bi * kBrick, bj * kBrick, bk * kBrick, nbz, (nbx + 31) >> 5)] & brick_bit(bi * kBrick)) != 0u;
+}
+
+__device__ __forceinline__ double clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_phase_apply(PhaseLaw w, double *__restrict__ T, double *__restrict__ F,
+                                                     const uint8_t *__restrict__ flags, const unsigned *__restrict__ bricks,
+                                                     const uint8_t *__restrict__ dir, unsigned *__restrict__ summary, Lay L,
+                                                     int nby, int nbz)
+{
+#pragma clang fp contract(off)
+    const int bk = (int)blockIdx.x, bj = (int)blockIdx.y, bi = (int)blockIdx.z;
+    const unsigned tid = threadIdx.x;
+    unsigned *entry = summary + ((long)bi * nby + bj) * nbz + bk;
+    const bool have_f = *entry != 0u;                       // (uniform over the workgroup)
+    const bool solid = brick_all_solid(bricks, L, bi, bj, bk);
+    PhaseCell c[kPhaseIter];
+    double t[kPhaseIter][2], f[kPhaseIter][2];
+    // the loads of the brick, issued together: f (only where some f of the brick is non-zero), flags (only where the flags
+    // summary does not say all-solid), T (only where a cell of the pair is in the mask)
+#pragma unroll
+    for (int it = 0; it < kPhaseIter; ++it) {
+        c[it] = phase_cell(L, bi, bj, bk, it, tid);
+        f[it][0] = 0.0; f[it][1] = 0.0;
+        if (have_f && c[it].in) load_pair<VEC>(F, c[it], f[it][0], f[it][1]);
+        if (c[it].in) c[it].m = solid ? c[it].in : (load_mask_pair<VEC>(flags, c[it]) & c[it].in);
+    }
+#pragma unroll
+    for (int it = 0; it < kPhaseIter; ++it) {
+        t[it][0] = 0.0; t[it][1] = 0.0;
+        if (c[it].m) load_pair<VEC>(T, c[it], t[it][0], t[it][1]);
+    }
+    bool any = false;                                       // a non-zero f in this thread's cells after the pass
+#pragma unroll
+    for (int it = 0; it < kPhaseIter; ++it) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const double fs = f[it][s], ts = t[it][s];
+            double fn = fs;
+            if ((c[it].m >> s) & 1u) {
+                const bool rest = (fs == 0.0 && ts <= w.Ts) || (fs == 1.0 && ts >= w.Tl);
+                if (!rest && (dir == nullptr || dir[c[it].p + s] == 0)) {
+                    const double h1 = w.cp * ts;
+                    const double h2 = w.L * fs;
+                    const double H = h1 + h2;
+                    double tn;
+                    if (H <= w.Hs) {
+                        tn = H / w.cp;
+                        fn = 0.0;
+                    } else if (H >= w.Hl) {
+                        const double d = H - w.L;
+                        tn = d / w.cp;
+                        fn = 1.0;
+                    } else {
+                        const double d = H - w.Hs;
+                        const double q = d / w.cm;
+                        tn = w.Ts + q;
+                        const double e = tn - w.Ts;
+                        fn = clamp01(e / w.dT);
+                    }
+                    T[c[it].p + s] = tn;
+                    F[c[it].p + s] = fn;
+                }
+            }
+            any = any || fn != 0.0;
+        }
+    }
+    const int nonzero = __syncthreads_or(any ? 1 : 0);
+    if (tid == 0 && (have_f || nonzero)) *entry = nonzero ? 1u : 0u;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_phase_seed(PhaseLaw w, const double *__restrict__ T, double *__restrict__ F,
+                                                    const uint8_t *__restrict__ flags, const unsigned *__restrict__ bricks,
+                                                    const uint8_t *__restrict__ sel, unsigned *__restrict__ summary, Lay L,
+                                                    int nby, int nbz)
+{
+#pragma clang fp contract(off)
+    const int bk = (int)blockIdx.x, bj = (int)blockIdx.y, bi = (int)blockIdx.z;
+    const unsigned tid = threadIdx.x;
+    const bool solid = brick_all_solid(bricks, L, bi, bj, bk);
+    bool any = false;
+#pragma unroll 2
+    for (int it = 0; it < kPhaseIter; ++it) {
+        PhaseCell c = phase_cell(L, bi, bj, bk, it, tid);
+        if (!c.in) continue;
+        c.m = solid ? c.in : (load_mask_pair<VEC>(flags, c) & c.in);
+        double t0 = 0.0, t1 = 0.0;
+        if (c.m) load_pair<VEC>(T, c, t0, t1);
+        for (int s = 0; s < 2; ++s) {
+            if (!((c.in >> s) & 1u)) continue;
+            const long p = c.p + s;
+            double fn;
+            if (!((c.m >> s) & 1u)) {
+                fn = 0.0;
+                F[p] = fn;
+            } else if (sel == nullptr || sel[p] != 0) {
+                const double e = (s ? t1 : t0) - w.Ts;
+                fn = clamp01(e / w.dT);
+                F[p] = fn;
+            } else {
+                fn = F[p];
+            }
+            any = any || fn != 0.0;
+        }
+    }
+    const int nonzero = __syncthreads_or(any ? 1 : 0);
+    if (tid == 0) summary[((long)bi * nby + bj) * nbz + bk] = nonzero ? 1u : 0u;
+}
+
+// ADI_OK and the law as the kernels take it, or the first rule of the header the arguments break
+static int make_phase_law(const char *who, const adi_phase_change &s, double cp, PhaseLaw *w)
+{
+#pragma clang fp contract(off)
+    ADI_REQUIRE(isfinite(s.latent_heat) && isfinite(s.T_solidus) && isfinite(s.T_liquidus),
+                "%s: latent_heat, T_solidus or T_liquidus not finite", who);
+    ADI_REQUIRE(s.latent_heat > 0.0, "%s: latent_heat must be > 0", who);
+    ADI_REQUIRE(s.T_liquidus > s.T_solidus, "%s: T_liquidus must be above T_solidus", who);
+    ADI_REQUIRE(isfinite(cp) && cp > 0.0, "%s: cp must be finite and > 0", who);
+    w->cp = cp; w->L = s.latent_heat; w->Ts = s.T_solidus; w->Tl = s.T_liquidus;
+    w->dT = w->Tl - w->Ts;
+    w->Hs = cp * w->Ts;
+    const double hl = cp * w->Tl;
+    w->Hl = hl + w->L;
+    const double r = w->L / w->dT;
+    w->cm = cp + r;
+    ADI_REQUIRE(isfinite(w->dT) && isfinite(w->Hl) && isfinite(w->cm), "%s: the law overflows fp64", who);
+    return ADI_OK;
+}
+
+struct PhaseLaunch {
+    Lay L;
+    dim3 grid;
+    int nby, nbz;
+};
+
+static int make_phase_launch(const char *who, int nx, int ny, int nz, long plane_stride, PhaseLaunch *g)
+{
+    if (int rc = make_lay(nx, ny, nz, plane_stride, &g->L)) return rc;
+    const int nbx = (nx + kBrick - 1) / kBrick;
+    g->nby = (ny + kBrick - 1) / kBrick;
+    g->nbz = (nz + kBrick - 1) / kBrick;
+    ADI_REQUIRE(g->nby <= 65535 && nbx <= 65535, "%s: box of %d x %d x %d is too large", who, nx, ny, nz);
+    g->grid = dim3((unsigned)g->nbz, (unsigned)g->nby, (unsigned)nbx);
+    return ADI_OK;
+}
+
+// 16-byte loads of the fields and 2-byte loads of the flags: pairs start on even offsets of aligned arrays
+static bool phase_vec(const Lay &L, const void *a, const void *b, const void *flags)
+{
+    return L.nz % 2 == 0 && L.sx % 2 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && ((uintptr_t)flags & 1) == 0;
+}
+
+}  // namespace adi
+
+using namespace adi;
+
+extern "C" {
+
+long adi_phase_summary_words(int nx, int ny, int nz)
+{
+    if (nx <= 0 || ny <= 0 || nz <= 0) return 0;
+    const long nbx = (nx + kBrick - 1) / kBrick, nby = (ny + kBrick - 1) / kBrick, nbz = (nz + kBrick - 1) / kBrick;
+    return nbx * nby * nbz;
+}
+
+int adi_phase_apply(const adi_phase_change *h_law, double cp, double *d_T, double *d_f, const uint8_t *d_flags,
+                    const uint32_t *d_bricks, const uint8_t *d_dir_mask, uint32_t *d_summary, int nx, int ny, int nz,
+                    long plane_stride, void *stream)
+{
+    ADI_REQUIRE(h_law && d_T && d_f && d_flags && d_summary, "adi_phase_apply: null argument");
+    ADI_REQUIRE(d_T != d_f, "adi_phase_apply: d_f aliases d_T");
+    PhaseLaw w;
+    if (int rc = make_phase_law("adi_phase_apply", *h_law, cp, &w)) return rc;
+    PhaseLaunch g;
+    if (int rc = make_phase_launch("adi_phase_apply", nx, ny, nz, plane_stride, &g)) return rc;
+    if (phase_vec(g.L, d_T, d_f, d_flags))
+        hipLaunchKernelGGL(k_phase_apply<true>, g.grid, dim3(256), 0, as_stream(stream), w, d_T, d_f, d_flags, d_bricks,
+                           d_dir_mask, (unsigned *)d_summary, g.L, g.nby, g.nbz);
+    else
+        hipLaunchKernelGGL(k_phase_apply<false>, g.grid, dim3(256), 0, as_stream(stream), w, d_T, d_f, d_flags, d_bricks,
+                           d_dir_mask, (unsigned *)d_summary, g.L, g.nby, g.nbz);
+    ADI_CHECK_LAUNCH();
+    return ADI_OK;
+}
+
+int adi_phase_seed(const adi_phase_change *h_law, const double *d_T, double *d_f, const uint8_t *d_flags,
+                   const uint32_t *d_bricks, const uint8_t *d_sel, uint32_t *d_summary, int nx, int ny, int nz,
+                   long plane_stride, void *stream)
+{
+    ADI_REQUIRE(h_law && d_T && d_f && d_flags && d_summary, "adi_phase_seed: null argument");
+    ADI_REQUIRE(d_T != d_f, "adi_phase_seed: d_f aliases d_T");
+    PhaseLaw w;
+    if (int rc = make_phase_law("adi_phase_seed", *h_law, 1.0, &w)) return rc;
+    PhaseLaunch g;
+    if (int rc = make_phase_launch("adi_phase_seed", nx, ny, nz, plane_stride, &g)) return rc;
+    if (phase_vec(g.L, d_T, d_f, d_flags))
+        hipLaunchKernelGGL(k_phase_seed<true>, g.grid, dim3(256), 0, as_stream(stream), w, d_T, d_f, d_flags, d_bricks, d_sel,
+                           (unsigned *)d_summary, g.L, g.nby, g.nbz);
+    else
+        hipLaunchKernelGGL(k_phase_seed<false>, g.grid, dim3(256), 0, as_stream(stream), w, d_T, d_f, d_flags, d_bricks, d_sel,
+                           (unsigned *)d_summary, g.L, g.nby, g.nbz);
+    ADI_CHECK_LAUNCH();
+    return ADI_OK;
+}
+
+}  // extern "C"

@@ -109,10 +109,13 @@ def _birth(backend, T, grid, newborn, Ts):
 
 
 def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, layers, times_birth, times_out,
-                    on_frame=None, device_resident=True, device_loop=True, surface_loss=None):
+                    on_frame=None, device_resident=True, device_loop=True, surface_loss=None, phase_change=None):
     """The event loop of waam_from_stl_v7_mm.py:515-550.  Returns (T_final as NumPy, number of ADI steps).
     surface_loss (a SurfaceLoss of the backend): the surface loses heat by that law, evaluated at the temperature at the start
-    of every sub-step, in place of the constant `h` (which is then not used); device loop only.  None: the reference's loop."""
+    of every sub-step, in place of the constant `h` (which is then not used); device loop only.  None: the reference's loop.
+    phase_change (a PhaseChange of the backend): latent heat of melting and freezing; one PhaseField lives through the run, every
+    sub-step ends with its correction, newborn cells are seeded at f_eq(Ts); device loop only.  The return value is then
+    (T_final, number of ADI steps, final liquid fraction as NumPy).  None: the loop without it, unchanged."""
     nx, ny, nz = mask_full.shape
     mask_act = np.zeros_like(mask_full, dtype=bool)
     grid = backend.Grid3D(nx, ny, nz, dx, mask_act)
@@ -135,15 +138,15 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         nonlocal T, nsteps
         nsub = max(1, int(math.ceil(seg / dt_cap)))
         params.dt = max(seg / nsub, 1e-15)
+        kw = {} if surface_loss is None else dict(surface_loss=bpacks)
+        if ph is not None:
+            kw['phase'] = ph
         if nsub >= GRAPH_MIN_NSUB and hasattr(backend, 'StagedStepper') and hasattr(T, 'fill_where'):
             # a long segment on the device backend: the nsub launches of this segment replayed from a HIP graph
-            if surface_loss is None:
-                T = backend.StagedStepper(grid, mat, params, packs, Tinf).run(T, nsub)
-            else:
-                T = backend.StagedStepper(grid, mat, params, packs, Tinf, surface_loss=bpacks).run(T, nsub)
-        elif surface_loss is not None:
+            T = backend.StagedStepper(grid, mat, params, packs, Tinf, **kw).run(T, nsub)
+        elif kw:
             for _ in range(nsub):
-                T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, surface_loss=bpacks)
+                T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, **kw)
         else:
             for _ in range(nsub):
                 T = _step(backend, T, grid, mat, params, packs, Tinf)
@@ -157,6 +160,9 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     dev_loop = device_loop and device_resident and hasattr(backend, 'BirthPacks') and hasattr(T, 'fill_where')
     if surface_loss is not None and not (dev_loop and hasattr(backend, 'LossPacks')):
         raise ValueError("run_layer_birth: surface_loss needs the device loop of a backend with LossPacks")
+    if phase_change is not None and not (dev_loop and hasattr(backend, 'PhaseField')):
+        raise ValueError("run_layer_birth: phase_change needs the device loop of a backend with PhaseField")
+    ph = None
     if dev_loop:
         import torch
         d_full = grid.layout.to_layout(mask_full, torch.uint8)
@@ -169,6 +175,8 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         packs = bpacks.packs
         plane_cells = np.asarray(mask_full).sum(axis=(0, 1)).astype(np.int64)      # newborn cells per plane, host-known
         plane_born = np.zeros(nz, dtype=bool)
+        if phase_change is not None:
+            ph = backend.PhaseField(grid, mat, phase_change)           # nothing is active yet: all solid
     else:
         packs = build_packs()
     n_active = 0
@@ -185,6 +193,8 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
                 packs = bpacks.update(ks - 1, ke + 2)                             # :534, the planes that changed
             else:
                 packs = bpacks.rebuild(T, ks - 1, ke + 2)
+            if ph is not None:
+                ph.sync_mask(T)                                                   # the newborn cells at f_eq(Ts)
             return
         born = np.zeros_like(mask_full, dtype=bool)
         born[:, :, ks:ke + 1] = mask_full[:, :, ks:ke + 1]
@@ -204,6 +214,8 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
             birth(*layers[arg])
         elif on_frame is not None:
             on_frame(arg, np.asarray(T), d_act.cpu().contiguous().numpy().astype(bool) if dev_loop else mask_act.copy())
+    if ph is not None:
+        return np.asarray(T), nsteps, np.asarray(ph.liquid_fraction)
     return np.asarray(T), nsteps
 
 
@@ -219,14 +231,17 @@ def track_source(heat_source, track_box, dx, yi, t_step):
 
 
 def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_track, theta, dt, t_step,
-                     device_resident=True, heat_source=None, surface_loss=None):
+                     device_resident=True, heat_source=None, surface_loss=None, phase_change=None):
     """single_track_on_plate.py:150-177: the deposit advances one column per t_step along axis 1; packs are
     rebuilt after every column.  track_box = (x0, x1, z0, z1, n_columns).
     heat_source (a GoldakSource of the backend): the arc / laser as a moving volumetric source (track_source) during the
     sub-steps of every column, on top of the newborn cells set to T_track.  None: the reference's driver, unchanged.
     surface_loss (a SurfaceLoss of the backend): the surface loses heat by that law, evaluated at the temperature at the start
     of every sub-step, in place of the constant `h`; device loop only; columns of at least GRAPH_MIN_NSUB sub-steps are
-    replayed from a HIP graph.  None: the constant-h packs, unchanged."""
+    replayed from a HIP graph.  None: the constant-h packs, unchanged.
+    phase_change (a PhaseChange of the backend): latent heat of melting and freezing; one PhaseField lives through the run, every
+    sub-step ends with its correction, the cells of a new column are seeded at f_eq(T_track); device loop only.  The return
+    value is then (T_final, final liquid fraction), both NumPy.  None: the loop without it, unchanged."""
     x0, x1, z0, z1, ncol = track_box
     nx, ny, nz = plate_mask.shape
     mask = plate_mask.copy()
@@ -240,10 +255,16 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     dev_loop = device_resident and hasattr(grid, 'set_mask_device') and hasattr(T, 'fill_where')
     if surface_loss is not None and not (dev_loop and hasattr(backend, 'LossPacks')):
         raise ValueError("run_single_track: surface_loss needs the device loop of a backend with LossPacks")
+    if phase_change is not None and not (dev_loop and hasattr(backend, 'PhaseField')):
+        raise ValueError("run_single_track: phase_change needs the device loop of a backend with PhaseField")
     if dev_loop:                                    # the mask lives in HBM: a new column is two slice assignments
         import torch
         d_mask = grid.layout.to_layout(mask, torch.uint8)
     lpacks = backend.LossPacks(grid, mat, surface_loss, Tinf) if surface_loss is not None else None
+    ph = backend.PhaseField(grid, mat, phase_change, T=T) if phase_change is not None else None
+    kw = {} if lpacks is None else dict(surface_loss=lpacks)
+    if ph is not None:
+        kw['phase'] = ph
     for yi in range(ncol):
         if dev_loop:
             d_mask[x0:x1, yi:yi + 1, z0:z1] = 1
@@ -256,17 +277,18 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         T[x0:x1, yi:yi + 1, z0:z1] = T_track
         if lpacks is not None:
             packs = lpacks.rebuild(T)                # the column changed the exposure: every cell, stale ones zeroed
+        if ph is not None:
+            ph.sync_mask(T)                          # the column's cells at f_eq(T_track)
         n_sub = max(1, int(math.ceil(t_step / dt)))
         dt_orig = params.dt
         params.dt = t_step / n_sub
-        if lpacks is not None:
+        if kw:
             src = None if heat_source is None else track_source(heat_source, track_box, dx, yi, t_step)
             if n_sub >= GRAPH_MIN_NSUB:
-                T = backend.StagedStepper(grid, mat, params, packs, Tinf, source=src, surface_loss=lpacks).run(T, n_sub, t0=0.0)
+                T = backend.StagedStepper(grid, mat, params, packs, Tinf, source=src, **kw).run(T, n_sub, t0=0.0)
             else:
                 for i in range(n_sub):
-                    T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=src, t=i * params.dt,
-                                                     surface_loss=lpacks)
+                    T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=src, t=i * params.dt, **kw)
         elif heat_source is None:
             for _ in range(n_sub):
                 T = _step(backend, T, grid, mat, params, packs, Tinf)
@@ -275,6 +297,8 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
             for i in range(n_sub):
                 T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=src, t=i * params.dt)
         params.dt = dt_orig
+    if ph is not None:
+        return np.asarray(T), np.asarray(ph.liquid_fraction)
     return np.asarray(T)
 
 

@@ -662,6 +662,48 @@ int adi_surface_loss_update(const adi_surface_loss *h_law, double Tinf, const do
                             double cp, double *const d_coeff[3], int k_begin, int k_end, int full, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Latent heat of melting and freezing of the Cartesian step (no counterpart in the reference, whose step has constant cp; the
+ * correction below is applied to the field its step returns, so the law is a sequence of calls the reference can run).
+ * State per cell: the temperature T and a liquid fraction f in [0, 1] (fp64, box layout, 0 off the mask).  The step runs at
+ * constant cp from (T, f); afterwards the enthalpy cp*T + L*f of every in-mask cell that is not a Dirichlet cell is put back
+ * on the equilibrium curve f_eq(T) = min(max((T - Ts)/(Tl - Ts), 0), 1) (temperature recovery: lagged, first order in dt).
+ * Host constants, one fp64 operation each: dT = Tl - Ts, Hs = cp*Ts, Hl = cp*Tl + L, cm = cp + L/dT.  With T* the step's
+ * result:
+ *     if (f == 0 and T* <= Ts) or (f == 1 and T* >= Tl):   nothing is written
+ *     else  H = cp*T* + L*f
+ *           H <= Hs:  T = H/cp;             f = 0
+ *           H >= Hl:  T = (H - L)/cp;       f = 1
+ *           else:     T = Ts + (H - Hs)/cm; f = min(max((T - Ts)/dT, 0), 1)
+ * every operation IEEE fp64 in this order, no contraction.  Off-mask cells and Dirichlet cells keep T and f bit for bit.
+ * Valid: finite values, latent_heat > 0, T_solidus < T_liquidus, cp > 0.  Everything else is ADI_ERR_ARG, checked before any
+ * HIP call.
+ *
+ * Phase summary: one 32-bit word per 16 x 16 x 16 brick of the box (the bricks of adi_build_flag_bricks), entry
+ * ((i/16) * nby + j/16) * nbz + k/16 with nby = ceil(ny/16), nbz = ceil(nz/16); adi_phase_summary_words gives their number
+ * (0: bad box).  An entry is 0 exactly when every f of the brick is 0 in memory.  One workgroup owns a brick, its cells and
+ * its entry: a workgroup whose entry is 0 does not load f (it takes f = 0); it loads flags only where d_bricks (the flags
+ * summary; NULL: none) does not say all-solid, the Dirichlet byte only of cells that reach the `else` above, and it rewrites
+ * its entry when it loaded f or wrote a non-zero f.  Far from the melt pool the pass costs one read of T.
+ * The law travels by value in the launch: a captured graph keeps the law it was captured with.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct adi_phase_change {
+    double latent_heat;     /* L [J/kg] */
+    double T_solidus;       /* Ts, the field's unit */
+    double T_liquidus;      /* Tl */
+} adi_phase_change;
+
+long adi_phase_summary_words(int nx, int ny, int nz);
+/* The correction, d_T and d_f in place.  d_dir_mask (NULL: no Dirichlet cells): box layout, non-zero on Dirichlet cells. */
+int adi_phase_apply(const adi_phase_change *h_law, double cp, double *d_T, double *d_f, const uint8_t *d_flags,
+                    const uint32_t *d_bricks, const uint8_t *d_dir_mask, uint32_t *d_summary, int nx, int ny, int nz,
+                    long plane_stride, void *stream);
+/* f = f_eq(T) on the in-mask cells d_sel selects (uint8, box layout; NULL: every in-mask cell), Dirichlet cells included;
+ * f = 0 off the mask; in-mask cells not selected keep f.  Every entry of the summary is rewritten. */
+int adi_phase_seed(const adi_phase_change *h_law, const double *d_T, double *d_f, const uint8_t *d_flags,
+                   const uint32_t *d_bricks, const uint8_t *d_sel, uint32_t *d_summary, int nx, int ny, int nz,
+                   long plane_stride, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Moving heat source of the cylindrical step.  For a step t_n -> t_n + dt:
  *     R0 = Tn + dt * q(x_c, t_n + dt/2) / (rho*cp)
  * and the three sweeps run unchanged.  Cell centres r_i = r_in + (i+1/2) dr, phi_j = (j+1/2) dphi, z_k = (k+1/2) dz (z from
