@@ -168,6 +168,13 @@ SIGNATURES = {
                                 c_int, c_long, c_void_p]),
     'adi_phase_seed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                c_long, c_void_p]),
+    'adi_history_record': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    'adi_history_set_clock': (c_int, [c_void_p, c_double, c_double, c_void_p]),
+    'adi_history_tick': (c_int, [c_void_p, c_void_p]),
+    'adi_history_seed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_long, c_void_p]),
+    'adi_history_reset_log': (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
     'adi_cyl_source_set': (c_int, [c_void_p, c_void_p, c_double, c_double, ctypes.c_longlong, c_void_p]),
     'adi_cyl_source_sample': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double, c_double,
                                       c_void_p, c_void_p, c_void_p]),
@@ -191,6 +198,8 @@ SOURCE_BLOCK_BYTES = 128     # ADI_SOURCE_BLOCK_BYTES
 SOURCE_E_CUT = 40.0          # ADI_SOURCE_E_CUT
 SURFACE_LOSS_MAX_KNOTS = 16  # ADI_SURFACE_LOSS_MAX_KNOTS
 SURFACE_LOSS_SIGMA = 5.670374419e-8   # ADI_SURFACE_LOSS_SIGMA (Stefan-Boltzmann, CODATA 2018)
+HISTORY_BLOCK_BYTES = 40     # ADI_HISTORY_BLOCK_BYTES: { double t0, dt; int64 n, slot, capacity }
+HISTORY_LOG_INTS = 8         # ADI_HISTORY_LOG_INTS: { cells, lo[3], hi[3], pad }
 STLCORR_DROPPED = (1 << 63) - 1   # ADI_STLCORR_DROPPED
 STLCORR_MAX_SUBDIV = 4096    # ADI_STLCORR_MAX_SUBDIV
 
@@ -211,6 +220,11 @@ class SurfaceLossLaw(ctypes.Structure):
 class PhaseChangeLaw(ctypes.Structure):
     """adi_phase_change (include/adi_hip.h)"""
     _fields_ = [('latent_heat', c_double), ('T_solidus', c_double), ('T_liquidus', c_double)]
+
+
+class HistoryLevelsC(ctypes.Structure):
+    """adi_history_levels (include/adi_hip.h)"""
+    _fields_ = [('T_hi', c_double), ('T_lo', c_double), ('T_melt', c_double)]
 
 
 CYL_DEPTHS = {'z': 0, 'r': 1}   # ADI_CYL_DEPTH_Z, ADI_CYL_DEPTH_R

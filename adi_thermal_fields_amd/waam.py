@@ -89,6 +89,13 @@ def layer_birth_schedule(times_birth, times_out):
 GRAPH_MIN_NSUB = 16      # segments at least this long run through StagedStepper.run (graph capture costs about a step)
 
 
+def history_result(hist):
+    """what the loops return of a ThermalHistory: T_peak, cooling_time, t_hi, t_lo as NumPy arrays (NaN off the mask and where
+    it never happened) and melt_pool(), the log of the run"""
+    return dict(T_peak=np.asarray(hist.T_peak), cooling_time=np.asarray(hist.cooling_time), t_hi=np.asarray(hist.t_hi),
+                t_lo=np.asarray(hist.t_lo), melt_pool=hist.melt_pool())
+
+
 def _is_device_backend(backend):
     return hasattr(backend, 'to_device')
 
@@ -109,13 +116,17 @@ def _birth(backend, T, grid, newborn, Ts):
 
 
 def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, layers, times_birth, times_out,
-                    on_frame=None, device_resident=True, device_loop=True, surface_loss=None, phase_change=None):
+                    on_frame=None, device_resident=True, device_loop=True, surface_loss=None, phase_change=None, history=None):
     """The event loop of waam_from_stl_v7_mm.py:515-550.  Returns (T_final as NumPy, number of ADI steps).
     surface_loss (a SurfaceLoss of the backend): the surface loses heat by that law, evaluated at the temperature at the start
     of every sub-step, in place of the constant `h` (which is then not used); device loop only.  None: the reference's loop.
     phase_change (a PhaseChange of the backend): latent heat of melting and freezing; one PhaseField lives through the run, every
     sub-step ends with its correction, newborn cells are seeded at f_eq(Ts); device loop only.  The return value is then
-    (T_final, number of ADI steps, final liquid fraction as NumPy).  None: the loop without it, unchanged."""
+    (T_final, number of ADI steps, final liquid fraction as NumPy).  None: the loop without it, unchanged.
+    history (a HistoryLevels of the backend): peak temperature, cooling time and melt pool; one ThermalHistory lives through the
+    run, sized from the schedule, every sub-step is recorded at the global time (which runs through the recorder's clock, idle
+    intervals included), newborn cells are seeded at Ts; device loop only.  The return value gains a last element, the result
+    dict of history_result.  None: the loop without it, unchanged."""
     nx, ny, nz = mask_full.shape
     mask_act = np.zeros_like(mask_full, dtype=bool)
     grid = backend.Grid3D(nx, ny, nz, dx, mask_act)
@@ -141,6 +152,8 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         kw = {} if surface_loss is None else dict(surface_loss=bpacks)
         if ph is not None:
             kw['phase'] = ph
+        if hist is not None:
+            kw['history'] = hist
         if nsub >= GRAPH_MIN_NSUB and hasattr(backend, 'StagedStepper') and hasattr(T, 'fill_where'):
             # a long segment on the device backend: the nsub launches of this segment replayed from a HIP graph
             T = backend.StagedStepper(grid, mat, params, packs, Tinf, **kw).run(T, nsub)
@@ -162,7 +175,9 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         raise ValueError("run_layer_birth: surface_loss needs the device loop of a backend with LossPacks")
     if phase_change is not None and not (dev_loop and hasattr(backend, 'PhaseField')):
         raise ValueError("run_layer_birth: phase_change needs the device loop of a backend with PhaseField")
-    ph = None
+    if history is not None and not (dev_loop and hasattr(backend, 'ThermalHistory')):
+        raise ValueError("run_layer_birth: history needs the device loop of a backend with ThermalHistory")
+    ph = hist = None
     if dev_loop:
         import torch
         d_full = grid.layout.to_layout(mask_full, torch.uint8)
@@ -177,6 +192,10 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         plane_born = np.zeros(nz, dtype=bool)
         if phase_change is not None:
             ph = backend.PhaseField(grid, mat, phase_change)           # nothing is active yet: all solid
+        if history is not None:                                        # one log row per sub-step the schedule can ask for
+            rows = sum(max(1, int(math.ceil(a / dt_cap))) for w, a in layer_birth_schedule(times_birth, times_out)
+                       if w == 'advance')
+            hist = backend.ThermalHistory(grid, history, capacity=max(1, rows), T=T)
     else:
         packs = build_packs()
     n_active = 0
@@ -195,6 +214,8 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
                 packs = bpacks.rebuild(T, ks - 1, ke + 2)
             if ph is not None:
                 ph.sync_mask(T)                                                   # the newborn cells at f_eq(Ts)
+            if hist is not None:
+                hist.sync_mask(T)                                                 # the newborn cells at T_peak = Ts
             return
         born = np.zeros_like(mask_full, dtype=bool)
         born[:, :, ks:ke + 1] = mask_full[:, :, ks:ke + 1]
@@ -210,13 +231,14 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         if what == 'advance':
             if n_active > 0:                           # no ADI steps while nothing is active (:524)
                 advance(arg)
+            elif hist is not None:
+                hist.t = hist.t + arg                  # (the global time moves on all the same)
         elif what == 'birth':
             birth(*layers[arg])
         elif on_frame is not None:
             on_frame(arg, np.asarray(T), d_act.cpu().contiguous().numpy().astype(bool) if dev_loop else mask_act.copy())
-    if ph is not None:
-        return np.asarray(T), nsteps, np.asarray(ph.liquid_fraction)
-    return np.asarray(T), nsteps
+    res = (np.asarray(T), nsteps) + (() if ph is None else (np.asarray(ph.liquid_fraction),))
+    return res if hist is None else res + (history_result(hist),)
 
 
 def track_source(heat_source, track_box, dx, yi, t_step):
@@ -231,7 +253,7 @@ def track_source(heat_source, track_box, dx, yi, t_step):
 
 
 def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_track, theta, dt, t_step,
-                     device_resident=True, heat_source=None, surface_loss=None, phase_change=None):
+                     device_resident=True, heat_source=None, surface_loss=None, phase_change=None, history=None):
     """single_track_on_plate.py:150-177: the deposit advances one column per t_step along axis 1; packs are
     rebuilt after every column.  track_box = (x0, x1, z0, z1, n_columns).
     heat_source (a GoldakSource of the backend): the arc / laser as a moving volumetric source (track_source) during the
@@ -241,7 +263,11 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     replayed from a HIP graph.  None: the constant-h packs, unchanged.
     phase_change (a PhaseChange of the backend): latent heat of melting and freezing; one PhaseField lives through the run, every
     sub-step ends with its correction, the cells of a new column are seeded at f_eq(T_track); device loop only.  The return
-    value is then (T_final, final liquid fraction), both NumPy.  None: the loop without it, unchanged."""
+    value is then (T_final, final liquid fraction), both NumPy.  None: the loop without it, unchanged.
+    history (a HistoryLevels of the backend): peak temperature, cooling time and melt pool; one ThermalHistory lives through the
+    run, sized from the schedule, every sub-step is recorded at the global time (the recorder's clock; the source's time still
+    counts from the start of each column), the cells of a new column are seeded at T_track; device loop only.  The return
+    value gains a last element, the result dict of history_result.  None: the loop without it, unchanged."""
     x0, x1, z0, z1, ncol = track_box
     nx, ny, nz = plate_mask.shape
     mask = plate_mask.copy()
@@ -257,6 +283,8 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         raise ValueError("run_single_track: surface_loss needs the device loop of a backend with LossPacks")
     if phase_change is not None and not (dev_loop and hasattr(backend, 'PhaseField')):
         raise ValueError("run_single_track: phase_change needs the device loop of a backend with PhaseField")
+    if history is not None and not (dev_loop and hasattr(backend, 'ThermalHistory')):
+        raise ValueError("run_single_track: history needs the device loop of a backend with ThermalHistory")
     if dev_loop:                                    # the mask lives in HBM: a new column is two slice assignments
         import torch
         d_mask = grid.layout.to_layout(mask, torch.uint8)
@@ -265,6 +293,10 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     kw = {} if lpacks is None else dict(surface_loss=lpacks)
     if ph is not None:
         kw['phase'] = ph
+    hist = None
+    if history is not None:
+        hist = backend.ThermalHistory(grid, history, capacity=ncol * max(1, int(math.ceil(t_step / dt))), T=T)
+        kw['history'] = hist
     for yi in range(ncol):
         if dev_loop:
             d_mask[x0:x1, yi:yi + 1, z0:z1] = 1
@@ -279,6 +311,8 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
             packs = lpacks.rebuild(T)                # the column changed the exposure: every cell, stale ones zeroed
         if ph is not None:
             ph.sync_mask(T)                          # the column's cells at f_eq(T_track)
+        if hist is not None:
+            hist.sync_mask(T)                        # the column's cells at T_peak = T_track
         n_sub = max(1, int(math.ceil(t_step / dt)))
         dt_orig = params.dt
         params.dt = t_step / n_sub
@@ -297,9 +331,10 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
             for i in range(n_sub):
                 T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=src, t=i * params.dt)
         params.dt = dt_orig
-    if ph is not None:
-        return np.asarray(T), np.asarray(ph.liquid_fraction)
-    return np.asarray(T)
+    res = (np.asarray(T),) + (() if ph is None else (np.asarray(ph.liquid_fraction),))
+    if hist is not None:
+        return res + (history_result(hist),)
+    return res if len(res) > 1 else res[0]
 
 
 def ring_source(heat_source, R_in, wall, z_top, tau):

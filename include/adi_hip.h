@@ -704,6 +704,56 @@ int adi_phase_seed(const adi_phase_change *h_law, const double *d_T, double *d_f
                    long plane_stride, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Thermal history of the Cartesian step (no counterpart in the reference; the rules below are applied to the pair of fields
+ * around one of its steps, so the recorder is a sequence of calls the reference can run).  State per cell (fp64, box layout,
+ * NaN off the mask and where "never happened"): the peak temperature T_peak, and the times t_hi, t_lo of the last downward
+ * crossing of the levels T_hi > T_lo (cooling time = t_lo - t_hi, the t8/5 of welding for 800 / 500 degrees C).  For a step
+ * A (the field at t_n) -> B (the step's final result at t_n + dt), on in-mask cells only:
+ *     1.  B > T_peak:              T_peak = B
+ *     2.  A > T_hi and B <= T_hi:  t_hi = t_n + dt*((A - T_hi)/(A - B));  t_lo = NaN   (a new cooling cycle begins)
+ *     3.  A > T_lo and B <= T_lo:  t_lo = t_n + dt*((A - T_lo)/(A - B))                (after 2: one step may do both)
+ *     4.  melt pool record of the step: the number of cells with B >= T_melt and the smallest / largest (i, j, k) among them
+ * every operation IEEE fp64 in this order, no contraction.  Off-mask cells are never written.
+ * Precondition: every in-mask A has been recorded, A <= T_peak (the recorder follows every step, and adi_history_seed follows
+ * every outside edit of T).  One workgroup owns a 16 x 16 x 16 brick (the bricks of adi_build_flag_bricks): it loads flags
+ * only where d_bricks (NULL: none) does not say all-solid, B and T_peak of in-mask cells, and A only when some T_peak of the
+ * brick exceeds T_lo -- under the precondition no other brick holds a crossing.  t_hi and t_lo are only ever stored.
+ *
+ * Clock and log: the block (device, ADI_HISTORY_BLOCK_BYTES) is five 8-byte words { double t0, dt; int64 n, slot, capacity };
+ * t_n = t0 + n*dt.  The record kernel reads it through the pointer, so a captured graph follows the clock; adi_history_tick
+ * (one thread) does n += 1, slot += 1 after it.  The log is (capacity + 1) rows of ADI_HISTORY_LOG_INTS 32-bit integers
+ * { cells, lo[3], hi[3], pad }; a step writes row min(slot, capacity) -- row `capacity` is a spill row -- with integer
+ * atomics (add / min / max), so the result does not depend on the order of the workgroups.  An empty row is
+ * { 0, INT32_MAX x 3, -1 x 3, 0 }.  slot never saturates: max(0, slot - capacity) steps were dropped.
+ * The levels travel by value in the launch: a captured graph keeps the levels it was captured with.
+ * Valid: finite levels, T_hi > T_lo (T_melt is independent), capacity >= 1, no state array aliasing a field or another state
+ * array.  Everything else is ADI_ERR_ARG, checked before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADI_HISTORY_BLOCK_BYTES 40
+#define ADI_HISTORY_LOG_INTS 8
+typedef struct adi_history_levels {
+    double T_hi;            /* upper level of the cooling time, the field's unit */
+    double T_lo;            /* lower level */
+    double T_melt;          /* a cell with T >= T_melt belongs to the melt pool */
+} adi_history_levels;
+
+/* rules 1 - 4 for the step d_T_in -> d_T_out at the block's clock, into the block's log row */
+int adi_history_record(const adi_history_levels *h_levels, const void *d_block, const double *d_T_in, const double *d_T_out,
+                       double *d_peak, double *d_t_hi, double *d_t_lo, int32_t *d_log, const uint8_t *d_flags,
+                       const uint32_t *d_bricks, int nx, int ny, int nz, long plane_stride, void *stream);
+/* t0 and dt of the block, n = 0; slot and capacity stay */
+int adi_history_set_clock(void *d_block, double t0, double dt, void *stream);
+/* n += 1, slot += 1 */
+int adi_history_tick(void *d_block, void *stream);
+/* T_peak = T, t_hi = t_lo = NaN on the in-mask cells d_sel selects (uint8, box layout; NULL: every in-mask cell); all three
+ * NaN off the mask; in-mask cells not selected keep their state */
+int adi_history_seed(const double *d_T, double *d_peak, double *d_t_hi, double *d_t_lo, const uint8_t *d_flags,
+                     const uint32_t *d_bricks, const uint8_t *d_sel, int nx, int ny, int nz, long plane_stride,
+                     void *stream);
+/* every one of the capacity + 1 rows of d_log empty; the block: slot = 0, n = 0, `capacity`; t0 and dt stay */
+int adi_history_reset_log(void *d_block, int32_t *d_log, long capacity, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Moving heat source of the cylindrical step.  For a step t_n -> t_n + dt:
  *     R0 = Tn + dt * q(x_c, t_n + dt/2) / (rho*cp)
  * and the three sweeps run unchanged.  Cell centres r_i = r_in + (i+1/2) dr, phi_j = (j+1/2) dphi, z_k = (k+1/2) dz (z from
