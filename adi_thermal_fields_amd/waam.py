@@ -267,8 +267,14 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     history (a HistoryLevels of the backend): peak temperature, cooling time and melt pool; one ThermalHistory lives through the
     run, sized from the schedule, every sub-step is recorded at the global time (the recorder's clock; the source's time still
     counts from the start of each column), the cells of a new column are seeded at T_track; device loop only.  The return
-    value gains a last element, the result dict of history_result.  None: the loop without it, unchanged."""
+    value gains a last element, the result dict of history_result.  None: the loop without it, unchanged.  With a recorder the
+    track box must not overlap the plate: T_track is written onto the whole box but only newborn cells are seeded (ValueError)."""
     x0, x1, z0, z1, ncol = track_box
+    if history is not None and np.asarray(plate_mask)[x0:x1, :ncol, z0:z1].any():
+        n = int(np.asarray(plate_mask)[x0:x1, :ncol, z0:z1].sum())
+        raise ValueError("run_single_track: the track box [%d:%d, 0:%d, %d:%d] overlaps the plate in %d cells; T_track is written "
+                         "onto those live cells without a seed, so the history recorder would miss it (a peak below the field, "
+                         "crossings skipped)" % (x0, x1, ncol, z0, z1, n))
     nx, ny, nz = plate_mask.shape
     mask = plate_mask.copy()
     grid = backend.Grid3D(nx, ny, nz, dx, mask)
