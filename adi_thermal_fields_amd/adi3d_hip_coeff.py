@@ -28,6 +28,7 @@ precompute_coeff_packs_unified(grid, ...) call, which is the documented synchron
 """
 import ctypes
 import itertools
+import math
 
 import numpy as np
 import torch
@@ -40,7 +41,7 @@ __all__ = ['Grid3D', 'Material', 'Params', 'AxisCoeffPack', 'exposed_mask', 'pre
            'adi_step_hip_coeff', 'adi_step_numba_coeff', 'adi_step_gpu_coeff', 'DeviceField', 'to_device',
            'adi_explicit_rhs', 'adi_sweep_axis', 'StagedStepper', 'Layout', 'apply_surface_impulse_Q',
            'exposed_faces_per_layer', 'count_exposed_faces', 'perimeter_ratio', 'birth_planes', 'BirthPacks',
-           'GoldakSource', 'SurfaceLoss', 'LossPacks', 'PhaseChange', 'PhaseField', 'HistoryLevels',
+           'GoldakSource', 'ScanPath', 'SurfaceLoss', 'LossPacks', 'PhaseChange', 'PhaseField', 'HistoryLevels',
            'ThermalHistory']
 
 
@@ -766,7 +767,8 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     cells, q evaluated at the step's mid-time.  None: the step of the reference, the same launches as without the keyword.
     An array of the grid's shape (NumPy / torch / DeviceField): the field form -- explicit stage with the source
     (adi_explicit_rhs_src), then the three unfused sweeps.  A GoldakSource: evaluated at t + dt/2 on the device and added
-    to the output of sweep 0 by superposition (adi_source_lines0), after whichever sweep-0 form the step uses.
+    to the output of sweep 0 by superposition (adi_source_lines0), after whichever sweep-0 form the step uses.  A ScanPath is
+    not accepted here: pass the field ScanPath.sample_step(grid, t, dt).
     t: the step's start time, used only by a source object.
     surface_loss: a LossPacks whose `.packs` are `packs`: their Robin coefficients are first rewritten from Tn (the law at the
     temperature at the start of the step, adi_surface_loss_update), then the step runs as above.  None: no such launch.
@@ -777,6 +779,9 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     own clock, which moves on by dt (adi_history_record and adi_history_tick, the last launches).  None: no such launch."""
     if history is not None:
         _history_of(history, grid)._check_mask()
+    if isinstance(S, ScanPath):
+        raise TypeError("adi_step_hip_coeff: a ScanPath has no device evaluator; pass its field, "
+                        "S=path.sample_step(grid, t, dt)")
     if S is not None and not isinstance(S, GoldakSource):
         return _step_field_source(Tn, grid, mat, params, packs, Tinf, S, surface_loss, phase, history)
     t_in, kind = _as_state(Tn, grid)
@@ -965,6 +970,336 @@ class GoldakSource:
 
     def set_block(self, blk, t0, dt, n=0):
         check(lib.adi_source_set(_p(blk), ctypes.byref(self.as_c()), float(t0), float(dt), int(n), _stream()))
+
+
+_erf = np.frompyfunc(math.erf, 1, 1)
+
+
+class ScanPath:
+    """Goldak's double ellipsoid driven along a path of straight segments (README, "Scan paths"): the HOST definition
+    of its step-averaged heat input.  A step takes it as a source field, adi_step_numba_coeff(..., S=path.sample_step(grid, t,
+    dt)); a path is not accepted as `S=` itself or as `source=` of a StagedStepper (there is no device evaluator).
+    Shape as GoldakSource: efficiency eta, a (half-width across the leg), b (depth), c_f / c_r (front / rear length) [m], front
+    fraction f_f; depth along depth_axis, the other two axes in increasing order are the in-plane axes (u, v).  `power` [W] is
+    the default of line_to.
+    The path starts at `start` (metres) at time t_start; line_to adds a straight leg at constant speed (power 0: a jump with
+    the beam off), dwell a stationary segment.  Segment k is active on [t_k, t_{k+1}).
+    The source of a step [t, t + dt] is q_step: the exact time average of the moving source over the step, summed over the
+    segments the step overlaps -- not a sample at mid-step, so a step may cross any number of legs, corners and jumps.
+    The cuts bound xi and (y, z) separately: the support around the centre is a box in the leg's frame."""
+    E_CUT = _lib.SOURCE_E_CUT
+    DELTA_MIN = 1e-3          # travel of a piece over min(c_f, c_r) below which q_step uses Simpson's rule instead of erf
+
+    def __init__(self, eta, a, b, c_f, c_r, f_f=0.6, depth_axis=2, power=0.0, start=(0.0, 0.0, 0.0), t_start=0.0):
+        self.eta, self.a, self.b, self.c_f, self.c_r, self.f_f = eta, a, b, c_f, c_r, f_f
+        self.depth_axis, self.power = depth_axis, power
+        self.validate()
+        self._pos = self._point(start, 'start')
+        self.start = self._pos
+        self.t_start = self._num(t_start, 't_start')
+        self._t_end = self.t_start
+        self._seg = []            # (t_begin, p0 (3), p1 (3), (d_u, d_v), speed, power)
+
+    @staticmethod
+    def _num(v, name, positive=False, nonneg=False):
+        try:
+            x = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("ScanPath: %s must be a real number" % name)
+        if not np.isfinite(x):
+            raise ValueError("ScanPath: non-finite %s" % name)
+        if (positive and x <= 0) or (nonneg and x < 0):
+            raise ValueError("ScanPath: %s must be %s" % (name, '> 0' if positive else '>= 0'))
+        return x
+
+    @classmethod
+    def _point(cls, p, name):
+        try:
+            q = tuple(float(v) for v in p)
+        except (TypeError, ValueError):
+            raise ValueError("ScanPath: %s must be three real numbers" % name)
+        if len(q) != 3:
+            raise ValueError("ScanPath: %s must have three coordinates" % name)
+        if not all(np.isfinite(v) for v in q):
+            raise ValueError("ScanPath: non-finite %s" % name)
+        return q
+
+    def validate(self):
+        """ValueError for a shape parameter out of range (the ranges of GoldakSource)"""
+        try:
+            vals = [float(v) for v in (self.eta, self.a, self.b, self.c_f, self.c_r, self.f_f, self.power)]
+        except (TypeError, ValueError):
+            raise ValueError("ScanPath: parameters must be real numbers")
+        if not all(np.isfinite(v) for v in vals):
+            raise ValueError("ScanPath: non-finite parameter")
+        eta, a, b, cf, cr, ff, P = vals
+        if P < 0:
+            raise ValueError("ScanPath: power < 0")
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError("ScanPath: eta outside [0, 1]")
+        if min(a, b, cf, cr) <= 0:
+            raise ValueError("ScanPath: lengths a, b, c_f, c_r must be > 0")
+        if not 0.0 < ff < 2.0:
+            raise ValueError("ScanPath: f_f outside (0, 2)")
+        ax = self.depth_axis
+        if isinstance(ax, bool) or not isinstance(ax, (int, np.integer)) or not 0 <= ax <= 2:
+            raise ValueError("ScanPath: depth_axis must be 0, 1 or 2")
+        return vals[:6]
+
+    @property
+    def axes(self):
+        """(u, v): the in-plane axes"""
+        da = int(self.depth_axis)
+        return (1 if da == 0 else 0), (1 if da == 2 else 2)
+
+    def _add(self, p1, d, speed, power, duration):
+        self._seg.append((self._t_end, self._pos, p1, d, speed, power))
+        self._pos = p1
+        self._t_end = self._t_end + duration
+        return self
+
+    def line_to(self, point, speed, power=None):
+        """a straight leg from the current point to `point` at `speed` [m/s]; power None: the path's default, 0: a jump.  A leg
+        with power keeps the depth coordinate; a jump may move anywhere (its time is its length in space over `speed`)."""
+        p1 = self._point(point, 'point')
+        speed = self._num(speed, 'speed', positive=True)
+        P = self._num(self.power if power is None else power, 'power', nonneg=True)
+        u, v = self.axes
+        du, dv, dz = p1[u] - self._pos[u], p1[v] - self._pos[v], p1[self.depth_axis] - self._pos[self.depth_axis]
+        plane = math.hypot(du, dv)
+        length = math.hypot(plane, dz)
+        if length == 0.0:
+            raise ValueError("ScanPath.line_to: a leg of zero length (use dwell)")
+        if P > 0 and dz != 0.0:
+            raise ValueError("ScanPath.line_to: a leg with power must keep the depth coordinate")
+        duration = length / speed
+        if not (np.isfinite(duration) and self._t_end + duration > self._t_end):
+            raise ValueError("ScanPath.line_to: the leg takes no time at this speed")
+        if plane > 0.0:
+            d, vel = (du / plane, dv / plane), plane / duration if dz != 0.0 else speed
+            n = math.hypot(*d)
+            d = (d[0] / n, d[1] / n)
+        else:
+            d, vel = (1.0, 0.0), 0.0
+        return self._add(p1, d, vel, P, duration)
+
+    def dwell(self, duration, power=0.0):
+        """a stationary segment; with power the ellipsoid keeps the direction of the leg before it ((1, 0) at the start)"""
+        duration = self._num(duration, 'duration', positive=True)
+        P = self._num(power, 'power', nonneg=True)
+        if not self._t_end + duration > self._t_end:
+            raise ValueError("ScanPath.dwell: the dwell takes no time")
+        d = self._seg[-1][3] if self._seg else (1.0, 0.0)
+        return self._add(self._pos, d, 0.0, P, duration)
+
+    @classmethod
+    def raster(cls, lo, hi, hatch, speed, power, angle_deg=0.0, bidirectional=True, jump_speed=None, depth=0.0, t_start=0.0,
+               **shape):
+        """a hatch over the in-plane rectangle lo = (u_lo, v_lo) .. hi = (u_hi, v_hi) at depth coordinate `depth`: parallel
+        tracks along (cos, sin)(angle_deg) spaced `hatch` apart along the normal (-sin, cos), the first through the corner with
+        the lowest normal coordinate, each clipped to the rectangle.  bidirectional: every other track runs backwards and a
+        jump (power 0, jump_speed, default `speed`) joins the end of a track to the start of the next; otherwise every track
+        runs forwards and the jump flies back."""
+        ulo, vlo = (cls._num(x, 'lo') for x in lo)
+        uhi, vhi = (cls._num(x, 'hi') for x in hi)
+        hatch = cls._num(hatch, 'hatch', positive=True)
+        depth = cls._num(depth, 'depth')
+        ang = math.radians(cls._num(angle_deg, 'angle_deg'))
+        if not (uhi > ulo and vhi > vlo):
+            raise ValueError("ScanPath.raster: empty rectangle")
+        jump_speed = speed if jump_speed is None else jump_speed
+        c, s = math.cos(ang), math.sin(ang)
+        if abs(c) < 1e-15:
+            c = 0.0
+        if abs(s) < 1e-15:
+            s = 0.0
+        corners = [(ulo, vlo), (uhi, vlo), (uhi, vhi), (ulo, vhi)]
+        sn = [-pu * s + pv * c for pu, pv in corners]
+        n_tracks = int(math.floor((max(sn) - min(sn)) / hatch + 1e-9)) + 1
+        tracks = []
+        for i in range(n_tracks):
+            off = min(sn) + i * hatch
+            # the line {off*n + l*t}: clip l to the rectangle (slab method)
+            ou, ov = -off * s, off * c
+            l0, l1 = -np.inf, np.inf
+            ok = True
+            for o, dcomp, a0, a1 in ((ou, c, ulo, uhi), (ov, s, vlo, vhi)):
+                if dcomp == 0.0:
+                    ok = ok and (a0 - 1e-12 * max(1.0, abs(a0)) <= o <= a1 + 1e-12 * max(1.0, abs(a1)))
+                else:
+                    la, lb = (a0 - o) / dcomp, (a1 - o) / dcomp
+                    l0, l1 = max(l0, min(la, lb)), min(l1, max(la, lb))
+            if ok and l1 - l0 > 1e-9 * hatch:
+                tracks.append(((ou + l0 * c, ov + l0 * s), (ou + l1 * c, ov + l1 * s)))
+        if not tracks:
+            raise ValueError("ScanPath.raster: no track fits the rectangle")
+        da = shape.get('depth_axis', 2)
+        u, v = (1 if da == 0 else 0), (1 if da == 2 else 2)
+
+        def pt(q):
+            p = [0.0, 0.0, 0.0]
+            p[u], p[v], p[da] = q[0], q[1], depth
+            return tuple(p)
+        path = None
+        for i, (q0, q1) in enumerate(tracks):
+            if bidirectional and i % 2 == 1:
+                q0, q1 = q1, q0
+            if path is None:
+                path = cls(power=power, start=pt(q0), t_start=t_start, **shape)
+            else:
+                path.line_to(pt(q0), jump_speed, power=0.0)
+            path.line_to(pt(q1), speed)
+        return path
+
+    # ---- plain readings
+    @property
+    def t_end(self):
+        return self._t_end
+
+    @property
+    def n_segments(self):
+        return len(self._seg)
+
+    def _t_next(self, k):
+        return self._seg[k + 1][0] if k + 1 < len(self._seg) else self._t_end
+
+    def _index(self, t):
+        """segment active at time t (a boundary belongs to the later segment); None outside [t_start, t_end)"""
+        if not self._seg or t < self.t_start or t >= self._t_end:
+            return None
+        return int(np.searchsorted([s[0] for s in self._seg], t, side='right')) - 1
+
+    def center(self, t):
+        """the centre at time t: the start before t_start, the last point from t_end on"""
+        t = float(t)
+        k = self._index(t)
+        if k is None:
+            return np.array(self.start if (t < self.t_start or not self._seg) else self._pos, dtype=np.float64)
+        tb, p0, p1 = self._seg[k][:3]
+        lam = (t - tb) / (self._t_next(k) - tb)
+        return np.array([a + (b - a) * lam for a, b in zip(p0, p1)], dtype=np.float64)
+
+    def power_at(self, t):
+        k = self._index(float(t))
+        return 0.0 if k is None else self._seg[k][5]
+
+    def table(self):
+        """the segments as a float64 array (K, 8): t_begin, start point p[3], in-plane unit direction d[2], speed, power"""
+        if not self._seg:
+            raise ValueError("ScanPath: the path has no segment")
+        return np.array([[tb, p0[0], p0[1], p0[2], d[0], d[1], vel, P] for tb, p0, _, d, vel, P in self._seg], dtype=np.float64)
+
+    # ---- the definition
+    def _piece(self, k, t, t1):
+        """(ta, tb, w): the piece of segment k inside [t, t1] as times since its start and its length; None if it deposits
+        nothing"""
+        tb, _, _, _, _, P = self._seg[k]
+        if not P > 0.0:
+            return None
+        tau0 = max(t, tb)
+        tau1 = min(t1, self._t_next(k))
+        if not tau1 > tau0:
+            return None
+        return tau0 - tb, tau1 - tb, tau1 - tau0
+
+    def _qi(self, P, xi, Et):
+        """the instantaneous double ellipsoid at along-leg offset xi, Et the exponent of the other two axes (no cut of its own)"""
+        eta, a, b, cf, cr, ff = self.validate()
+        front = xi >= 0.0
+        f = np.where(front, ff, 2.0 - ff)
+        cl = np.where(front, cf, cr)
+        E = 3.0 * (xi * xi) / (cl * cl) + Et
+        amp = (6.0 * np.sqrt(3.0) * f * eta * P) / (a * b * cl * np.pi ** 1.5)
+        with np.errstate(under='ignore'):
+            return amp * np.exp(-E)
+
+    def _qbar(self, k, x0, x1, x2, t, dt, branch=None):
+        """qbar_k at points (broadcast arrays): the time average over [t, t + dt] of the moving source during its overlap with
+        segment k.  branch: None -- the definition; 'erf' / 'simpson' force one of the two forms (tests)."""
+        eta, a, b, cf, cr, ff = self.validate()
+        shape = np.broadcast(x0, x1, x2).shape
+        out = np.zeros(shape, dtype=np.float64)
+        pc = self._piece(k, t, t + dt)
+        if pc is None:
+            return out
+        ta, tb, w = pc
+        _, p0, _, d, vel, P = self._seg[k]
+        u, v = self.axes
+        o = (x0 - p0[0], x1 - p0[1], x2 - p0[2])
+        ou, ov, z = o[u], o[v], o[self.depth_axis]
+        xi0 = ou * d[0] + ov * d[1]
+        y = ov * d[0] - ou * d[1]
+        xia = xi0 - vel * ta
+        xib = xi0 - vel * tb
+        Et = 3.0 * (y * y) / (a * a) + 3.0 * (z * z) / (b * b)
+        R = np.sqrt(self.E_CUT / 3.0)
+        ok = np.broadcast_to((Et <= self.E_CUT) & (xib <= R * cf) & (xia >= -(R * cr)), shape)
+        if not ok.any():
+            return out
+        xi0, xia, xib, Et = (np.broadcast_to(q, shape)[ok] for q in (xi0, xia, xib, Et))
+        travel = vel * w
+        delta = travel / min(cf, cr)
+        if branch == 'erf' or (branch is None and delta >= self.DELTA_MIN):
+            s3 = np.sqrt(3.0)
+            Ff = _erf(s3 * np.maximum(xia, 0.0) / cf).astype(np.float64) - _erf(s3 * np.maximum(xib, 0.0) / cf).astype(np.float64)
+            Fr = _erf(s3 * np.minimum(xia, 0.0) / cr).astype(np.float64) - _erf(s3 * np.minimum(xib, 0.0) / cr).astype(np.float64)
+            brace = ff * Ff + (2.0 - ff) * Fr
+            amp = (3.0 * eta * P) / (np.pi * a * b * vel * dt)
+            with np.errstate(under='ignore'):
+                val = (amp * np.exp(-Et)) * brace
+        elif travel == 0.0:
+            val = (w / dt) * self._qi(P, xia, Et)
+        else:
+            xim = xi0 - vel * (0.5 * (ta + tb))
+            qs = (self._qi(P, xia, Et) + 4.0 * self._qi(P, xim, Et)) + self._qi(P, xib, Et)
+            val = (w / dt) * (qs / 6.0)
+        out[ok] = val
+        return out
+
+    def q_step(self, x0, x1, x2, t, dt):
+        """the source of the step [t, t + dt] in W/m^3 at points (broadcast NumPy arrays, metres): the sum over the segments, in
+        ascending order, of their time averages: one fp64 operation per line"""
+        t, dt = float(t), self._num(dt, 'dt', positive=True)
+        x0, x1, x2 = (np.asarray(x, dtype=np.float64) for x in (x0, x1, x2))
+        q = np.zeros(np.broadcast(x0, x1, x2).shape, dtype=np.float64)
+        for k in range(len(self._seg)):
+            if self._piece(k, t, t + dt) is not None:
+                q += self._qbar(k, x0, x1, x2, t, dt)
+        return q
+
+    def _index_box(self, k, pc, n, dx):
+        """slices of the cells of an n[0] x n[1] x n[2] grid whose centres can lie in the support of piece pc of segment k: the
+        support reaches R hypot(max(c_f, c_r), a) from the centre in the plane and R b in depth (the cuts of _qbar)"""
+        eta, a, b, cf, cr, ff = self.validate()
+        R = np.sqrt(self.E_CUT / 3.0)
+        _, p0, _, d, vel, _ = self._seg[k]
+        u, v = self.axes
+        dirs = {u: d[0], v: d[1], int(self.depth_axis): 0.0}
+        sl = []
+        for ax in range(3):
+            m = (R * b if ax == self.depth_axis else R * math.hypot(max(cf, cr), a)) * (1.0 + 1e-9)
+            ca, cb = p0[ax] + dirs[ax] * (vel * pc[0]), p0[ax] + dirs[ax] * (vel * pc[1])
+            lo = int(min(max(math.floor((min(ca, cb) - m) / dx - 0.5), 0), n[ax]))
+            hi = int(min(max(math.ceil((max(ca, cb) + m) / dx - 0.5) + 1, 0), n[ax]))
+            sl.append(slice(lo, max(hi, lo)))
+        return tuple(sl)
+
+    def sample_step(self, grid, t, dt):
+        """q_step at the cell centres ((i+1/2)dx, (j+1/2)dx, (k+1/2)dx): float64 array of the grid's shape, 0 off the mask: the
+        source field of the step, for `S=`.  Every segment is evaluated on the index box of its support only (the cells outside
+        it get exactly 0 from q_step), so the temporaries are of the size of the support, not of the grid."""
+        t, dt = float(t), self._num(dt, 'dt', positive=True)
+        dx = float(grid.dx)
+        n = (grid.nx, grid.ny, grid.nz)
+        x = [(np.arange(m, dtype=np.float64) + 0.5) * dx for m in n]
+        q = np.zeros(n, dtype=np.float64)
+        for k in range(len(self._seg)):
+            pc = self._piece(k, t, t + dt)
+            if pc is None:
+                continue
+            si, sj, sk = self._index_box(k, pc, n, dx)
+            q[si, sj, sk] += self._qbar(k, x[0][si, None, None], x[1][None, sj, None], x[2][None, None, sk], t, dt)
+        return np.where(np.asarray(grid.mask, dtype=bool), q, 0.0)
 
 
 def apply_surface_impulse_Q(T, grid, mat, Q, face='z-'):
@@ -1764,7 +2099,8 @@ class StagedStepper:
         # -- captured with it; the levels travel by value and the five buffers by pointer, so all are part of run()'s graph key
         self.history = None if history is None else _history_of(history, grid)
         if source is not None and not isinstance(source, GoldakSource):
-            raise TypeError("StagedStepper: source must be a GoldakSource (pass a source field to adi_step_numba_coeff)")
+            raise TypeError("StagedStepper: source must be a GoldakSource (pass a source field, e.g. ScanPath.sample_step, to "
+                            "adi_step_numba_coeff)")
         # moving source: corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step counter
         # a captured tick advances -- power, origin, velocity, eta and f_f may change between runs without a new graph
         self.source = source
