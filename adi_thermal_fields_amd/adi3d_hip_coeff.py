@@ -641,6 +641,17 @@ def _wrap(t, kind):
     return DeviceField(t).get()
 
 
+def _native_f64(grid, T, strict=None):
+    """T (DeviceField / tensor / array) as an fp64 device tensor in the grid's layout: itself when it is one; otherwise a
+    ValueError with the text `strict`, or without `strict` a converted copy"""
+    t = T.t if isinstance(T, DeviceField) else T
+    if not grid.layout.is_native(t) or t.dtype != torch.float64:
+        if strict is not None:
+            raise ValueError(strict)
+        t = grid.layout.to_layout(T, torch.float64)
+    return t
+
+
 def adi_explicit_rhs(Tn, grid, mat, params):
     """R0 of adi3d_numba_coeff.py:292-298 (stage entry point for per-stage parity tests / benchmarks)."""
     t, kind = _as_state(Tn, grid)
@@ -749,13 +760,82 @@ def _ensure_general(pack):
         pack.d_qflux = L.empty(zero=True)
 
 
-def _loss_update(surface_loss, packs, t_in, Tinf):
-    """the first launch of a step with `surface_loss=`: the packs' Robin coefficients from the step's input field"""
-    if not isinstance(surface_loss, LossPacks):
-        raise TypeError("surface_loss must be a LossPacks")
-    if len(packs) != 3 or any(p is not q for p, q in zip(packs, surface_loss.packs)):
-        raise ValueError("surface_loss: the step must be given the LossPacks' own packs (surface_loss.packs)")
-    surface_loss.update(t_in, Tinf)
+def _check_extras(grid, mat, packs, source, surface_loss, phase, history):
+    """TypeError / ValueError for an optional argument of the step that is of the wrong kind or was made for other packs, another
+    grid or another cp: once per adi_step_hip_coeff call and once per StagedStepper, before anything is launched"""
+    if source is not None and not isinstance(source, GoldakSource):
+        raise TypeError("source must be a GoldakSource (pass a source field, e.g. ScanPath.sample_step, to "
+                        "adi_step_numba_coeff)")
+    if surface_loss is not None:
+        if not isinstance(surface_loss, LossPacks):
+            raise TypeError("surface_loss must be a LossPacks")
+        if len(packs) != 3 or any(p is not q for p, q in zip(packs, surface_loss.packs)):
+            raise ValueError("surface_loss: the step must be given the LossPacks' own packs (surface_loss.packs)")
+    if phase is not None:
+        if not isinstance(phase, PhaseField):
+            raise TypeError("phase must be a PhaseField")
+        if phase.grid is not grid:
+            raise ValueError("phase: the PhaseField belongs to another grid")
+        if float(phase.mat.cp) != float(mat.cp):
+            raise ValueError("phase: the PhaseField was made for cp = %r, the step runs with %r" % (phase.mat.cp, mat.cp))
+    if history is not None:
+        if not isinstance(history, ThermalHistory):
+            raise TypeError("history must be a ThermalHistory")
+        if history.grid is not grid:
+            raise ValueError("history: the ThermalHistory belongs to another grid")
+
+
+def _no_mark():
+    pass
+
+
+def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, source=None, owner=None, t_set=None,
+                 surface_loss=None, phase=None, history=None, captured=False, mark=_no_mark):
+    """THE launch sequence of one step t_in -> out (fp64 tensors in the grid's layout; nothing is allocated): the surface-loss
+    update from t_in, the explicit stage and sweep 0 (one launch when `fused`), the moving source's correction of sweep 0's
+    output, sweeps 1 and 2, the latent-heat correction of `out`, the history record.  Every form of the step calls it --
+    adi_step_hip_coeff with or without a source field, StagedStepper.step, and what StagedStepper.run captures -- with
+    arguments that _check_extras has passed.
+    d_S: a source FIELD in the grid's layout; the explicit stage takes it (adi_explicit_rhs_src), never fused.
+    source, owner: a GoldakSource and the object that holds its device block and workspace; t_set: the step's start time if the
+    block is to be set here, just ahead of the correction (None: the caller has set it).
+    captured: a graph may replay these launches and the caller keeps the clocks: the source's block is ticked after the
+    correction, and the history launches its record without moving its host clock.  Otherwise no tick, and history.record.
+    mark: called at the stage boundaries of per-stage timing: before the explicit stage, between it and sweep 0 when they are
+    two launches, after sweep 0 with the source's correction, after sweep 1 and after sweep 2."""
+    (ta, tb), _, _ = grid.scratch(2)
+    if surface_loss is not None:
+        surface_loss.update(t_in, Tinf)
+    mark()
+    if fused and d_S is None:
+        _explicit_sweep0_into(t_in, tb, grid, mat, params, packs[0], Tinf)
+    else:
+        if d_S is None:
+            kappa, _ = _gam(grid, mat, params)
+            check(lib.adi_explicit_rhs(_p(t_in), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt,
+                                       kappa, params.theta, _p(ta), _stream()))
+        else:
+            _explicit_src_into(t_in, d_S, ta, grid, mat, params)
+        mark()
+        _sweep_into(0, ta, tb, grid, mat, params, packs[0], Tinf)
+    if source is not None:
+        if t_set is not None:
+            source.set_block(_source_block(owner), t_set, params.dt)
+        _source_lines0_into(tb, grid, mat, params, packs[0], source, owner)
+        if captured:
+            check(lib.adi_source_tick(_p(_source_block(owner)), _stream()))
+    mark()
+    _sweep_into(1, tb, ta, grid, mat, params, packs[1], Tinf)
+    mark()
+    _sweep_into(2, ta, out, grid, mat, params, packs[2], Tinf)
+    mark()
+    if phase is not None:
+        phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
+    if history is not None:
+        if captured:
+            history._launch_record(t_in, out)
+        else:
+            history.record(t_in, out, params.dt)
 
 
 def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None, phase=None, history=None):
@@ -776,36 +856,24 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     the PhaseField holds, which moves on with it (adi_phase_apply, the last launch, on the freshly allocated output).  None: no
     such launch.
     history: a ThermalHistory of the grid: the step Tn -> result (after the correction of `phase`) is recorded at the recorder's
-    own clock, which moves on by dt (adi_history_record and adi_history_tick, the last launches).  None: no such launch."""
-    if history is not None:
-        _history_of(history, grid)._check_mask()
+    own clock, which moves on by dt (adi_history_record and adi_history_tick, the last launches).  None: no such launch.
+    Every optional argument is checked before the first launch (_check_extras); the launches are _launch_step's."""
     if isinstance(S, ScanPath):
         raise TypeError("adi_step_hip_coeff: a ScanPath has no device evaluator; pass its field, "
                         "S=path.sample_step(grid, t, dt)")
-    if S is not None and not isinstance(S, GoldakSource):
-        return _step_field_source(Tn, grid, mat, params, packs, Tinf, S, surface_loss, phase, history)
-    t_in, kind = _as_state(Tn, grid)
-    if surface_loss is not None:
-        _loss_update(surface_loss, packs, t_in, Tinf)
-    packx, packy, packz = packs
-    (ta, tb), _, _ = grid.scratch(2)
-    kappa, _ = _gam(grid, mat, params)
-    out = grid.layout.empty()
-    if fused_supported(grid):
-        _explicit_sweep0_into(t_in, tb, grid, mat, params, packx, Tinf)
-    else:
-        check(lib.adi_explicit_rhs(_p(t_in), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt,
-                                   kappa, params.theta, _p(ta), _stream()))
-        _sweep_into(0, ta, tb, grid, mat, params, packx, Tinf)
-    if S is not None:
-        S.set_block(_source_block(grid), t, params.dt)
-        _source_lines0_into(tb, grid, mat, params, packx, S, grid)
-    _sweep_into(1, tb, ta, grid, mat, params, packy, Tinf)
-    _sweep_into(2, ta, out, grid, mat, params, packz, Tinf)
-    if phase is not None:
-        _phase_apply(phase, out, grid, mat, packs)
+    source = S if isinstance(S, GoldakSource) else None
+    _check_extras(grid, mat, packs, source, surface_loss, phase, history)
     if history is not None:
-        history.record(t_in, out, params.dt)
+        history._check_mask()
+    t_in, kind = _as_state(Tn, grid)
+    d_S = None
+    if S is not None and source is None:
+        if tuple(S.shape) != grid.shape:
+            raise ValueError("S has shape %s, the grid %s" % (tuple(S.shape), grid.shape))
+        d_S = grid.layout.to_layout(S, torch.float64)
+    out = grid.layout.empty()
+    _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused_supported(grid), d_S=d_S, source=source, owner=grid, t_set=t,
+                 surface_loss=surface_loss, phase=phase, history=history)
     return _wrap(out, kind)
 
 
@@ -813,27 +881,6 @@ def _explicit_src_into(t, d_S, out, grid, mat, params):
     kappa, _ = _gam(grid, mat, params)
     check(lib.adi_explicit_rhs_src(_p(t), _p(d_S), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt, kappa,
                                    params.theta, mat.rho, mat.cp, _p(out), _stream()))
-
-
-def _step_field_source(Tn, grid, mat, params, packs, Tinf, S, surface_loss=None, phase=None, history=None):
-    """the step with a source FIELD: R0 with the source, then the three unfused sweeps"""
-    t, kind = _as_state(Tn, grid)
-    if surface_loss is not None:
-        _loss_update(surface_loss, packs, t, Tinf)
-    if tuple(S.shape) != grid.shape:
-        raise ValueError("S has shape %s, the grid %s" % (tuple(S.shape), grid.shape))
-    d_S = grid.layout.to_layout(S, torch.float64)
-    (ta, tb), _, _ = grid.scratch(2)
-    out = grid.layout.empty()
-    _explicit_src_into(t, d_S, ta, grid, mat, params)
-    _sweep_into(0, ta, tb, grid, mat, params, packs[0], Tinf)
-    _sweep_into(1, tb, ta, grid, mat, params, packs[1], Tinf)
-    _sweep_into(2, ta, out, grid, mat, params, packs[2], Tinf)
-    if phase is not None:
-        _phase_apply(phase, out, grid, mat, packs)
-    if history is not None:
-        history.record(t, out, params.dt)
-    return _wrap(out, kind)
 
 
 def _source_block(owner):
@@ -1563,9 +1610,7 @@ class LossPacks:
 
     def _launch(self, T, Tinf, k0, k1, full):
         g, m = self.grid, self.mat
-        t = T.t if isinstance(T, DeviceField) else T
-        if not g.layout.is_native(t) or t.dtype != torch.float64:
-            t = g.layout.to_layout(T, torch.float64)          # host arrays / foreign tensors: a copy (not the step's path)
+        t = _native_f64(g, T)                                 # host arrays / foreign tensors: a copy (not the step's path)
         law = self.loss.as_c(self.Tinf if Tinf is None else Tinf)
         check(lib.adi_surface_loss_update(ctypes.byref(law), float(self.Tinf if Tinf is None else Tinf), _p(t), _p(g.d_flags),
                                           _p(g.d_bricks), *g.layout.pd, g.dx, m.rho, m.cp, self._coeff, int(k0), int(k1),
@@ -1688,7 +1733,25 @@ class PhaseChange:
         return np.where(act, Tn, Tst), np.where(act, fn, f)
 
 
-class PhaseField:
+class _SeededForMask:
+    """What PhaseField and ThermalHistory share: a per-cell state seeded for one version of `self.grid`'s mask, the mask then
+    seen, and the re-seed of the cells that joined the mask since.  `seed(T, sel)` is the owner's and ends in _remember_mask."""
+    _seen = None                 # the device mask at the last seed (None: never seeded)
+    _mask_version = None
+
+    def _remember_mask(self):
+        self._seen = self.grid.d_mask.clone()
+        self._mask_version = self.grid.mask_version
+
+    def sync_mask(self, T):
+        """after a mask change: the cells that joined the mask since the last seed / sync are seeded from T, those that left it
+        are cleared (the seed does that off the mask), every other cell keeps its state; never seeded: every in-mask cell"""
+        g = self.grid
+        if g.mask_version != self._mask_version:
+            self.seed(T, sel=None if self._seen is None else (g.d_mask != 0) & (self._seen == 0))
+
+
+class PhaseField(_SeededForMask):
     """The liquid fraction of a grid under a PhaseChange law, on the device: `f` (fp64, the grid's layout, 0 off the mask) and
     the phase summary (one word per 16^3 brick, 0 exactly when every f of the brick is 0: adi_phase_apply far from the melt
     pool reads T once and nothing else).  Both buffers live as long as the object, so a StagedStepper's graph holds their
@@ -1710,8 +1773,6 @@ class PhaseField:
         self.f = self._flat.as_strided(L.shape, L.strides)
         self.summary = torch.zeros(self._words(), dtype=torch.int32, device=_device())
         self.d_dir_mask = None if dir_mask is None else L.to_layout(dir_mask, torch.uint8)
-        self._seen = None
-        self._mask_version = None
         if T is not None:
             self.seed(T)
         else:
@@ -1723,16 +1784,6 @@ class PhaseField:
             raise ValueError("PhaseField: bad grid")
         return n
 
-    def _remember_mask(self):
-        self._seen = self.grid.d_mask.clone()
-        self._mask_version = self.grid.mask_version
-
-    def _native(self, T):
-        t = T.t if isinstance(T, DeviceField) else T
-        if not self.grid.layout.is_native(t) or t.dtype != torch.float64:
-            t = self.grid.layout.to_layout(T, torch.float64)
-        return t
-
     @property
     def liquid_fraction(self):
         """a copy of f as a DeviceField of the grid's shape"""
@@ -1742,9 +1793,7 @@ class PhaseField:
         """adi_phase_apply on T (a DeviceField or device tensor in the grid's layout), in place; d_dir_mask: the Dirichlet
         cells as a uint8 device tensor in the grid's layout (default: the ones given at construction)"""
         g = self.grid
-        t = T.t if isinstance(T, DeviceField) else T
-        if not g.layout.is_native(t) or t.dtype != torch.float64:
-            raise ValueError("PhaseField.apply: T must be a fp64 device field in the grid's layout (it is corrected in place)")
+        t = _native_f64(g, T, "PhaseField.apply: T must be a fp64 device field in the grid's layout (it is corrected in place)")
         if g.mask_version != self._mask_version:
             raise ValueError("PhaseField: the grid's mask changed since the liquid fraction was seeded; call sync_mask(T)")
         assert self.summary.numel() == self._words()
@@ -1761,17 +1810,9 @@ class PhaseField:
         g = self.grid
         d_sel = None if sel is None else g.layout.to_layout(sel, torch.uint8)
         assert self.summary.numel() == self._words()
-        check(lib.adi_phase_seed(ctypes.byref(self.law.as_c()), _p(self._native(T)), _p(self.f), _p(g.d_flags), _p(g.d_bricks),
+        check(lib.adi_phase_seed(ctypes.byref(self.law.as_c()), _p(_native_f64(g, T)), _p(self.f), _p(g.d_flags), _p(g.d_bricks),
                                  _p(d_sel), _p(self.summary), *g.layout.pd, _stream()))
         self._remember_mask()
-
-    def sync_mask(self, T):
-        """after a mask change: seed the cells that joined the mask since the last seed / sync from T, zero those that left"""
-        g = self.grid
-        if g.mask_version == self._mask_version:
-            return
-        newborn = (g.d_mask != 0) & (self._seen == 0)
-        self.seed(T, sel=newborn)
 
     def set_liquid_fraction(self, f):
         """load f (array / tensor / DeviceField of the grid's shape; taken as 0 off the mask) and rebuild the summary from it
@@ -1793,16 +1834,10 @@ class PhaseField:
         self._flat.copy_(other._flat)
         self.summary.copy_(other.summary)
 
-
-def _phase_apply(phase, out, grid, mat, packs):
-    """the last launch of a step with `phase=`: the correction of the step's own output buffer"""
-    if not isinstance(phase, PhaseField):
-        raise TypeError("phase must be a PhaseField")
-    if phase.grid is not grid:
-        raise ValueError("phase: the PhaseField belongs to another grid")
-    if float(phase.mat.cp) != float(mat.cp):
-        raise ValueError("phase: the PhaseField was made for cp = %r, the step runs with %r" % (phase.mat.cp, mat.cp))
-    phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
+    def graph_key(self):
+        """what a captured graph holds of the field: the law by value, the buffers by pointer"""
+        return (self.law.key(), self.f.data_ptr(), self.summary.data_ptr(),
+                None if self.d_dir_mask is None else self.d_dir_mask.data_ptr())
 
 
 # ---- thermal history: peak temperature, cooling time, melt pool (include/adi_hip.h, DESIGN.md section 6h) -------------------
@@ -1838,7 +1873,7 @@ class HistoryLevels:
 _POOL_EMPTY_LO = np.iinfo(np.int32).max
 
 
-class ThermalHistory:
+class ThermalHistory(_SeededForMask):
     """Thermal history of a grid under HistoryLevels, on the device: `T_peak`, `t_hi`, `t_lo` (fp64, the grid's layout, NaN off
     the mask and where "never happened"), the melt-pool log (one row of ADI_HISTORY_LOG_INTS integers per recorded step, `capacity`
     rows and a spill row), the device block (clock and log slot) and the host clock `.t`: the time at which the next recorded
@@ -1874,8 +1909,6 @@ class ThermalHistory:
         self.d_block = torch.zeros(_lib.HISTORY_BLOCK_BYTES // 8, dtype=torch.int64, device=_device())
         self.t = float(t)
         self._times = []             # end time of every recorded step, host side
-        self._seen = None
-        self._mask_version = None
         check(lib.adi_history_reset_log(_p(self.d_block), _p(self.d_log), capacity, _stream()))
         if T is not None:
             self.reset(T, t)
@@ -1935,18 +1968,6 @@ class ThermalHistory:
         return np.where(s, np.asarray(T, dtype=np.float64), peak), np.where(s, np.nan, t_hi), np.where(s, np.nan, t_lo)
 
     # -- the device side -------------------------------------------------------------------------------------------------------
-    def _native(self, T, what, strict=False):
-        t = T.t if isinstance(T, DeviceField) else T
-        if not self.grid.layout.is_native(t) or t.dtype != torch.float64:
-            if strict:
-                raise ValueError("ThermalHistory.%s: T_in and T_out must be fp64 device fields in the grid's layout" % what)
-            t = self.grid.layout.to_layout(T, torch.float64)
-        return t
-
-    def _remember_mask(self):
-        self._seen = self.grid.d_mask.clone()
-        self._mask_version = self.grid.mask_version
-
     def _launch_record(self, t_in, t_out):
         g = self.grid
         check(lib.adi_history_record(ctypes.byref(self.levels.as_c()), _p(self.d_block), _p(t_in), _p(t_out), _p(self.d_peak),
@@ -1970,7 +1991,8 @@ class ThermalHistory:
     def record(self, T_in, T_out, dt):
         """one step T_in (at .t) -> T_out (at .t + dt), both fp64 device fields in the grid's layout: one record launch and the
         tick; afterwards .t = t0 + dt"""
-        t_in, t_out = self._native(T_in, 'record', True), self._native(T_out, 'record', True)
+        strict = "ThermalHistory.record: T_in and T_out must be fp64 device fields in the grid's layout"
+        t_in, t_out = _native_f64(self.grid, T_in, strict), _native_f64(self.grid, T_out, strict)
         self._check_mask()
         dt = float(dt)
         self.set_clock(dt)
@@ -1982,7 +2004,7 @@ class ThermalHistory:
         mask"""
         g = self.grid
         d_sel = None if sel is None else g.layout.to_layout(sel, torch.uint8)
-        check(lib.adi_history_seed(_p(self._native(T, 'seed')), _p(self.d_peak), _p(self.d_t_hi), _p(self.d_t_lo),
+        check(lib.adi_history_seed(_p(_native_f64(g, T)), _p(self.d_peak), _p(self.d_t_hi), _p(self.d_t_lo),
                                    _p(g.d_flags), _p(g.d_bricks), _p(d_sel), *g.layout.pd, _stream()))
         self._remember_mask()
 
@@ -1992,17 +2014,6 @@ class ThermalHistory:
         check(lib.adi_history_reset_log(_p(self.d_block), _p(self.d_log), self.capacity, _stream()))
         self._times = []
         self.t = float(t)
-
-    def sync_mask(self, T):
-        """after a mask change: seed the cells that joined the mask since the last seed / sync from T, NaN those that left"""
-        g = self.grid
-        if g.mask_version == self._mask_version:
-            return
-        if self._seen is None:
-            self.seed(T)
-            return
-        newborn = (g.d_mask != 0) & (self._seen == 0)
-        self.seed(T, sel=newborn)
 
     def snapshot(self):
         return [f.clone() for f in self._flat], self._log_store.clone(), self.d_block.clone(), self.t, list(self._times)
@@ -2050,14 +2061,6 @@ class ThermalHistory:
                     volume=cells * dx ** 3, dropped=max(0, slot - self.capacity))
 
 
-def _history_of(history, grid):
-    if not isinstance(history, ThermalHistory):
-        raise TypeError("history must be a ThermalHistory")
-    if history.grid is not grid:
-        raise ValueError("history: the ThermalHistory belongs to another grid")
-    return history
-
-
 # the reference's backend-specific names, so its drivers run unchanged on this module
 adi_step_numba_coeff = adi_step_hip_coeff
 adi_step_gpu_coeff = adi_step_hip_coeff
@@ -2075,32 +2078,18 @@ class StagedStepper:
 
     def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None, surface_loss=None, phase=None,
                  history=None):
+        _check_extras(grid, mat, packs, source, surface_loss, phase, history)
         self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
         # temperature-dependent surface loss: the packs' Robin coefficients rewritten from the step's INPUT buffer, the first
         # launch of every step -- captured with it (X -> Y reads X, Y -> X reads Y); the law travels by value in that launch,
         # so its parameters are part of run()'s graph key
-        if surface_loss is not None:
-            if not isinstance(surface_loss, LossPacks):
-                raise TypeError("StagedStepper: surface_loss must be a LossPacks")
-            if len(packs) != 3 or any(p is not q for p, q in zip(packs, surface_loss.packs)):
-                raise ValueError("StagedStepper: surface_loss needs its own packs (surface_loss.packs) as `packs`")
         self.surface_loss = surface_loss
         # latent heat: the correction of the step's OUTPUT buffer, the last launch of every step -- captured with it; the law
         # travels by value and f and the summary by pointer, so all three are part of run()'s graph key
-        if phase is not None:
-            if not isinstance(phase, PhaseField):
-                raise TypeError("StagedStepper: phase must be a PhaseField")
-            if phase.grid is not grid:
-                raise ValueError("StagedStepper: the PhaseField belongs to another grid")
-            if float(phase.mat.cp) != float(mat.cp):
-                raise ValueError("StagedStepper: the PhaseField was made for another cp")
         self.phase = phase
         # thermal history: the record of the step input -> output and the tick of its block, the last launches of every step
         # -- captured with it; the levels travel by value and the five buffers by pointer, so all are part of run()'s graph key
-        self.history = None if history is None else _history_of(history, grid)
-        if source is not None and not isinstance(source, GoldakSource):
-            raise TypeError("StagedStepper: source must be a GoldakSource (pass a source field, e.g. ScanPath.sample_step, to "
-                            "adi_step_numba_coeff)")
+        self.history = history
         # moving source: corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step counter
         # a captured tick advances -- power, origin, velocity, eta and f_f may change between runs without a new graph
         self.source = source
@@ -2121,28 +2110,10 @@ class StagedStepper:
         _sweep_into(axis, t_in, t_out, self.grid, self.mat, self.params, self.packs[axis], self.Tinf, variant,
                     dense=dense)
 
-    def _step_into(self, t, out):
+    def _step_into(self, t, out, captured=True, mark=_no_mark):
         """one step t -> out (both native-layout device tensors), no allocation: what a HIP graph captures"""
-        g, prm = self.grid, self.params
-        (ta, tb), _, _ = g.scratch(2)
-        kappa, _ = _gam(g, self.mat, prm)
-        if self.surface_loss is not None:
-            self.surface_loss.update(t, self.Tinf)
-        if self.fused:
-            _explicit_sweep0_into(t, tb, g, self.mat, prm, self.packs[0], self.Tinf)
-        else:
-            check(lib.adi_explicit_rhs(_p(t), _p(g.d_flags), *g.layout.pd, g.dx, prm.dt, kappa, prm.theta,
-                                       _p(ta), _stream()))
-            self.sweep_into(0, ta, tb)
-        if self.source is not None:
-            _source_lines0_into(tb, g, self.mat, prm, self.packs[0], self.source, self)
-            check(lib.adi_source_tick(_p(_source_block(self)), _stream()))
-        self.sweep_into(1, tb, ta)
-        self.sweep_into(2, ta, out)
-        if self.phase is not None:
-            _phase_apply(self.phase, out, g, self.mat, self.packs)
-        if self.history is not None:
-            self.history._launch_record(t, out)
+        _launch_step(t, out, self.grid, self.mat, self.params, self.packs, self.Tinf, self.fused, source=self.source, owner=self,
+                     surface_loss=self.surface_loss, phase=self.phase, history=self.history, captured=captured, mark=mark)
 
     def run(self, T, nsteps, graph=True, t0=0.0):
         """The drivers' `nsub` loop (quick_compare_dirichlet_robin.py:169-178, waam_from_stl_v7_mm.py:525-528): `nsteps`
@@ -2160,8 +2131,7 @@ class StagedStepper:
                tuple(None if p.d_coeff is None else p.d_coeff.data_ptr() for p in self.packs), self.fused,
                None if self.source is None else self.source.shape_key(),
                None if self.surface_loss is None else self.surface_loss.loss.key(),
-               None if self.phase is None else (self.phase.law.key(), self.phase.f.data_ptr(), self.phase.summary.data_ptr(),
-                                                None if self.phase.d_dir_mask is None else self.phase.d_dir_mask.data_ptr()),
+               None if self.phase is None else self.phase.graph_key(),
                None if self.history is None else self.history.graph_key())
         if self.history is not None:
             self.history._check_mask()
@@ -2175,17 +2145,15 @@ class StagedStepper:
             self.source.set_block(_source_block(self), t0, prm.dt)
         if graph and nsteps >= 2 and st['g'] is None:
             g.scratch(2)                                   # every buffer exists before the capture
-            held = None if self.phase is None else self.phase.snapshot()   # (the warm-up steps would advance f)
-            held_h = None if self.history is None else self.history.snapshot()   # (... and the history, its log and clock)
-            if held_h is not None:
+            stateful = [x for x in (self.phase, self.history) if x is not None]
+            held = [x.snapshot() for x in stateful]        # (the warm-up steps would advance f, the history, its log and clock)
+            if self.history is not None:
                 self.history.set_clock(prm.dt)
             self._step_into(X, Y); self._step_into(Y, X)   # warm-up outside the capture (lazy module loads, and the
             self._step_into(X, Y); self._step_into(Y, X)   # no-fallback promise is learnt on the third step); harmless:
             X.copy_(g.layout.to_layout(T, torch.float64))  # X is restored
-            if held is not None:
-                self.phase.restore(held)                   # ... and so are f and the phase summary
-            if held_h is not None:
-                self.history.restore(held_h)
+            for x, snap in zip(stateful, held):
+                x.restore(snap)                            # ... and so is what the extras hold
             torch.cuda.synchronize()
             cg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(cg):
@@ -2217,36 +2185,8 @@ class StagedStepper:
         g, prm = self.grid, self.params
         if self.source is not None:
             self.source.set_block(_source_block(self), t, prm.dt)
-        t = g.layout.to_layout(T, torch.float64)
-        (ta, tb), _, _ = g.scratch(2)
-        kappa, _ = _gam(g, self.mat, prm)
+        t_in = g.layout.to_layout(T, torch.float64)
         out = g.layout.empty()
-        ne = 0
-
-        def mark():
-            nonlocal ne
-            if events is not None:
-                events[ne].record()
-            ne += 1
-        if self.surface_loss is not None:
-            self.surface_loss.update(t, self.Tinf)
-        mark()
-        if self.fused:
-            _explicit_sweep0_into(t, tb, g, self.mat, prm, self.packs[0], self.Tinf)
-        else:
-            check(lib.adi_explicit_rhs(_p(t), _p(g.d_flags), *g.layout.pd, g.dx, prm.dt, kappa, prm.theta,
-                                       _p(ta), _stream()))
-            mark()
-            self.sweep_into(0, ta, tb)
-        if self.source is not None:
-            _source_lines0_into(tb, g, self.mat, prm, self.packs[0], self.source, self)
-        mark()
-        self.sweep_into(1, tb, ta)
-        mark()
-        self.sweep_into(2, ta, out)
-        mark()
-        if self.phase is not None:
-            _phase_apply(self.phase, out, g, self.mat, self.packs)
-        if self.history is not None:
-            self.history.record(t, out, prm.dt)
+        ev = iter(events or ())
+        self._step_into(t_in, out, captured=False, mark=(lambda: next(ev).record()) if events else _no_mark)
         return DeviceField(out)

@@ -100,6 +100,25 @@ def _is_device_backend(backend):
     return hasattr(backend, 'to_device')
 
 
+def _require_device_loop(who, backend, dev_loop, **asked):
+    """ValueError for an option (name = value) that is set where the loop cannot serve it"""
+    for name, cls in (('surface_loss', 'LossPacks'), ('phase_change', 'PhaseField'), ('history', 'ThermalHistory')):
+        if asked[name] is not None and not (dev_loop and hasattr(backend, cls)):
+            raise ValueError("%s: %s needs the device loop of a backend with %s" % (who, name, cls))
+
+
+def _extras_kw(lpacks, ph, hist):
+    """the keywords of a step / a stepper for the extras that are present"""
+    return {k: v for k, v in (('surface_loss', lpacks), ('phase', ph), ('history', hist)) if v is not None}
+
+
+def _sync_extras(T, ph, hist):
+    """after a birth / a new column: the newborn cells at f_eq(T) and at T_peak = T"""
+    for x in (ph, hist):
+        if x is not None:
+            x.sync_mask(T)
+
+
 def _step(backend, T, grid, mat, params, packs, Tinf):
     fn = getattr(backend, 'adi_step_hip_coeff', None) or backend.adi_step_numba_coeff
     return fn(T, grid, mat, params, packs, Tinf=Tinf)
@@ -149,11 +168,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         nonlocal T, nsteps
         nsub = max(1, int(math.ceil(seg / dt_cap)))
         params.dt = max(seg / nsub, 1e-15)
-        kw = {} if surface_loss is None else dict(surface_loss=bpacks)
-        if ph is not None:
-            kw['phase'] = ph
-        if hist is not None:
-            kw['history'] = hist
+        kw = _extras_kw(None if surface_loss is None else bpacks, ph, hist)
         if nsub >= GRAPH_MIN_NSUB and hasattr(backend, 'StagedStepper') and hasattr(T, 'fill_where'):
             # a long segment on the device backend: the nsub launches of this segment replayed from a HIP graph
             T = backend.StagedStepper(grid, mat, params, packs, Tinf, **kw).run(T, nsub)
@@ -171,12 +186,8 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     # and one plane either side) -- in place, no allocation, no host synchronisation: nothing crosses PCIe between
     # output times and nothing waits for the device between births
     dev_loop = device_loop and device_resident and hasattr(backend, 'BirthPacks') and hasattr(T, 'fill_where')
-    if surface_loss is not None and not (dev_loop and hasattr(backend, 'LossPacks')):
-        raise ValueError("run_layer_birth: surface_loss needs the device loop of a backend with LossPacks")
-    if phase_change is not None and not (dev_loop and hasattr(backend, 'PhaseField')):
-        raise ValueError("run_layer_birth: phase_change needs the device loop of a backend with PhaseField")
-    if history is not None and not (dev_loop and hasattr(backend, 'ThermalHistory')):
-        raise ValueError("run_layer_birth: history needs the device loop of a backend with ThermalHistory")
+    _require_device_loop('run_layer_birth', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
+                         history=history)
     ph = hist = None
     if dev_loop:
         import torch
@@ -212,10 +223,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
                 packs = bpacks.update(ks - 1, ke + 2)                             # :534, the planes that changed
             else:
                 packs = bpacks.rebuild(T, ks - 1, ke + 2)
-            if ph is not None:
-                ph.sync_mask(T)                                                   # the newborn cells at f_eq(Ts)
-            if hist is not None:
-                hist.sync_mask(T)                                                 # the newborn cells at T_peak = Ts
+            _sync_extras(T, ph, hist)
             return
         born = np.zeros_like(mask_full, dtype=bool)
         born[:, :, ks:ke + 1] = mask_full[:, :, ks:ke + 1]
@@ -285,24 +293,17 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         T = backend.to_device(T)
     robin = {f: h for f in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')}
     dev_loop = device_resident and hasattr(grid, 'set_mask_device') and hasattr(T, 'fill_where')
-    if surface_loss is not None and not (dev_loop and hasattr(backend, 'LossPacks')):
-        raise ValueError("run_single_track: surface_loss needs the device loop of a backend with LossPacks")
-    if phase_change is not None and not (dev_loop and hasattr(backend, 'PhaseField')):
-        raise ValueError("run_single_track: phase_change needs the device loop of a backend with PhaseField")
-    if history is not None and not (dev_loop and hasattr(backend, 'ThermalHistory')):
-        raise ValueError("run_single_track: history needs the device loop of a backend with ThermalHistory")
+    _require_device_loop('run_single_track', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
+                         history=history)
     if dev_loop:                                    # the mask lives in HBM: a new column is two slice assignments
         import torch
         d_mask = grid.layout.to_layout(mask, torch.uint8)
     lpacks = backend.LossPacks(grid, mat, surface_loss, Tinf) if surface_loss is not None else None
     ph = backend.PhaseField(grid, mat, phase_change, T=T) if phase_change is not None else None
-    kw = {} if lpacks is None else dict(surface_loss=lpacks)
-    if ph is not None:
-        kw['phase'] = ph
     hist = None
     if history is not None:
         hist = backend.ThermalHistory(grid, history, capacity=ncol * max(1, int(math.ceil(t_step / dt))), T=T)
-        kw['history'] = hist
+    kw = _extras_kw(lpacks, ph, hist)
     for yi in range(ncol):
         if dev_loop:
             d_mask[x0:x1, yi:yi + 1, z0:z1] = 1
@@ -315,10 +316,7 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         T[x0:x1, yi:yi + 1, z0:z1] = T_track
         if lpacks is not None:
             packs = lpacks.rebuild(T)                # the column changed the exposure: every cell, stale ones zeroed
-        if ph is not None:
-            ph.sync_mask(T)                          # the column's cells at f_eq(T_track)
-        if hist is not None:
-            hist.sync_mask(T)                        # the column's cells at T_peak = T_track
+        _sync_extras(T, ph, hist)
         n_sub = max(1, int(math.ceil(t_step / dt)))
         dt_orig = params.dt
         params.dt = t_step / n_sub
