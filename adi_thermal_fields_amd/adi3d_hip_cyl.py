@@ -15,7 +15,8 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
-from .adi3d_hip_coeff import DeviceField, Layout, to_device, _device, _stream, _p, _wrap, _source_block
+from .fields import DeviceField, Layout, to_device, _device, _stream, _p, _as_state, _wrap
+from .heat_source import goldak_shape, goldak_q, _source_block
 
 __all__ = ['StagedCylStepper', 'CylGoldakSource', 'GridCyl', 'Material', 'Params', 'RobinR', 'ZBC', 'adi_step', 'adi_step_masked', 'DeviceField', 'to_device']
 
@@ -97,23 +98,9 @@ class CylGoldakSource:
 
     def validate(self):
         """ValueError for any parameter adi_cyl_heat_source rejects (include/adi_hip.h); returns the twelve numbers"""
-        try:
-            vals = [float(v) for v in (self.power, self.eta, self.a, self.b, self.c_f, self.c_r, self.f_f, self.r_c,
-                                       self.phi0, self.omega, self.z0, self.v_z)]
-        except (TypeError, ValueError):
-            raise ValueError("CylGoldakSource: parameters must be real numbers")
-        if not all(np.isfinite(v) for v in vals):
-            raise ValueError("CylGoldakSource: non-finite source parameter")
-        P, eta, a, b, cf, cr, ff, rc = vals[:8]
-        if P < 0:
-            raise ValueError("CylGoldakSource: power < 0")
-        if not 0.0 <= eta <= 1.0:
-            raise ValueError("CylGoldakSource: eta outside [0, 1]")
-        if min(a, b, cf, cr) <= 0:
-            raise ValueError("CylGoldakSource: non-positive length")
-        if not 0.0 < ff < 2.0:
-            raise ValueError("CylGoldakSource: f_f outside (0, 2)")
-        if rc < 0:
+        vals = goldak_shape('CylGoldakSource', self.power, self.eta, self.a, self.b, self.c_f, self.c_r, self.f_f,
+                            more=(self.r_c, self.phi0, self.omega, self.z0, self.v_z))
+        if vals[7] < 0:
             raise ValueError("CylGoldakSource: r_c < 0")
         if not isinstance(self.depth, str) or self.depth not in _lib.CYL_DEPTHS:
             raise ValueError("CylGoldakSource: depth must be 'z' (0) or 'r' (1)")
@@ -142,13 +129,7 @@ class CylGoldakSource:
         rho = r * np.cos(delta) - rc
         zeta = z - zc
         lrad, lax = (a, b) if self.depth == 'z' else (b, a)
-        front = xi >= 0.0
-        f = np.where(front, ff, 2.0 - ff)
-        cl = np.where(front, cf, cr)
-        E = (3.0 * (xi * xi) / (cl * cl) + 3.0 * (rho * rho) / (lrad * lrad)) + 3.0 * (zeta * zeta) / (lax * lax)
-        amp = (6.0 * np.sqrt(3.0) * f * eta * P) / (a * b * cl * np.pi ** 1.5)
-        with np.errstate(under='ignore'):
-            return np.where(E <= self.E_CUT, amp * np.exp(-np.minimum(E, 745.0)), 0.0)
+        return goldak_q(xi, rho, zeta, xi >= 0.0, P, eta, lrad, lax, cf, cr, ff)
 
     def sample(self, grid, t, active=None):
         """q at the cell centres (r_i, (j+1/2) dphi, (k+1/2) dz) at time t: float64 array (nr, nphi, nz), 0 where `active`
@@ -204,14 +185,6 @@ def _plan(grid, mat, dt, robin_r, zbc):
     return pl
 
 
-def _state(Tn, grid):
-    kind = 'field' if isinstance(Tn, DeviceField) else ('torch' if isinstance(Tn, torch.Tensor) else 'numpy')
-    if kind == 'numpy':
-        Tn = np.asarray(Tn)
-    assert tuple(Tn.shape) == grid.shape
-    return grid.layout.to_layout(Tn, torch.float64), kind
-
-
 def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None):
     # adi3d_cyl_phi_v3.py:335: `scheme = prm.scheme if prm.scheme in ('be', 'douglas') else 'be'` -- every string but
     # 'douglas' is backward Euler in the reference, and so it is here
@@ -221,7 +194,7 @@ def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None):
     src = S if isinstance(S, CylGoldakSource) else None
     if src is not None and t is None:
         raise ValueError("t (the step's start time) is required when S is a CylGoldakSource")
-    x, kind = _state(Tn, grid)
+    x, kind = _as_state(Tn, grid)           # (a GridCyl has no mask to synchronise: the conversion alone)
     pl = _plan(grid, mat, prm.dt, robin_r, zbc)
     out = grid.layout.empty()
     d_act = None if active is None else grid.layout.to_layout(active, torch.uint8)

@@ -824,7 +824,7 @@ class SlabStepper:
         it (None).  Every rank attaches and detaches the same source at the same step: the plan depends on it (collective).
         Then step() needs t, the step's start time; the source is evaluated at t + dt/2."""
         if src is not None:
-            from .adi3d_hip_coeff import GoldakSource
+            from .heat_source import GoldakSource
             if not isinstance(src, GoldakSource):
                 raise TypeError("SlabStepper: source must be a GoldakSource or None, not %s" % type(src).__name__)
             if not all(hasattr(self.engine, m) for m in ('source_set', 'source_lines0', 'source_add_r0')):

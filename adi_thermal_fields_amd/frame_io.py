@@ -16,8 +16,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import adi3d_hip_coeff as _hip
 from ._lib import check, lib
+from .fields import DeviceField, _device, _stream
 
 __all__ = ['write_vtk_structured_points', 'write_vtk_structured_points_mm', 'write_npy', 'pack_frame_f32be']
 
@@ -25,17 +25,17 @@ __all__ = ['write_vtk_structured_points', 'write_vtk_structured_points_mm', 'wri
 def pack_frame_f32be(T):
     """DeviceField / device tensor / NumPy (nx, ny, nz) fp64 -> bytes of the big-endian float32 values in VTK point
     order (x fastest), packed on the device."""
-    t = T.t if isinstance(T, _hip.DeviceField) else T
+    t = T.t if isinstance(T, DeviceField) else T
     if not isinstance(t, torch.Tensor):
         t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.float64))
-    t = t.to(device=_hip._device(), dtype=torch.float64)
+    t = t.to(device=_device(), dtype=torch.float64)
     assert t.ndim == 3
     nx, ny, nz = t.shape
     if not (t.stride(2) == 1 and t.stride(1) == nz and t.stride(0) >= ny * nz):
         t = t.contiguous()
     out = torch.empty(nx * ny * nz, dtype=torch.int32, device=t.device)
     check(lib.adi_pack_frame_f32be(ctypes.c_void_p(t.data_ptr()), nx, ny, nz, t.stride(0), ctypes.c_void_p(out.data_ptr()),
-                                   _hip._stream()))
+                                   _stream()))
     return out.cpu().numpy().tobytes()
 
 
@@ -47,7 +47,7 @@ def _ascii_scalars9(f, name, flat):
 
 
 def _host(T):
-    return np.asarray(T.get() if isinstance(T, _hip.DeviceField) else (T.cpu().numpy() if isinstance(T, torch.Tensor) else T))
+    return np.asarray(T.get() if isinstance(T, DeviceField) else (T.cpu().numpy() if isinstance(T, torch.Tensor) else T))
 
 
 def _mask_field(mask):

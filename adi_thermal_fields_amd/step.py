@@ -1,0 +1,394 @@
+"""The Cartesian ADI step: the stage entry points, THE launch sequence (`_launch_step`), `adi_step_hip_coeff` with the
+reference's two names for it, and `StagedStepper`."""
+import ctypes
+
+import torch
+
+from . import _lib
+from ._lib import lib, check
+from ._ledger import PromiseLedger
+from .fields import DeviceField, _as_state, _wrap, _p, _stream
+from .packs import _fc_arg
+from .heat_source import GoldakSource, ScanPath, _source_block, _source_work
+from .surface_loss import LossPacks
+from .phase import PhaseField
+from .history import ThermalHistory
+
+
+def _gam(grid, mat, params):
+    kappa = mat.k / (mat.rho * mat.cp)                    # adi3d_numba_coeff.py:292
+    return kappa, kappa * params.dt / (grid.dx * grid.dx)
+
+
+def adi_explicit_rhs(Tn, grid, mat, params):
+    """R0 of adi3d_numba_coeff.py:292-298 (stage entry point for per-stage parity tests / benchmarks)."""
+    t, kind = _as_state(Tn, grid)
+    kappa, _ = _gam(grid, mat, params)
+    out = grid.layout.empty()
+    check(lib.adi_explicit_rhs(_p(t), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt,
+                               kappa, params.theta, _p(out), _stream()))
+    return _wrap(out, kind)
+
+
+def _sparse_arg(grid, pack, dense):
+    """the `sparse` argument of the sweep entry points: bit 0 = the pack arrays may be read only where the flags say a
+    cell is exposed, bit 1 = all-solid box hint.  Bit 0 needs packs built for the mask the flags describe: after
+    `grid.mask = new` WITHOUT a pack rebuild the reference pairs the stale packs with the live mask
+    (adi3d_numba_coeff.py:150-162 reads coeff at every in-mask cell), so stale packs are read densely here too."""
+    fresh = getattr(pack, 'mask_version', None) == grid.mask_version
+    return int(pack.sparse_ok and fresh and not dense) | (2 if getattr(grid, 'all_solid', False) else 0)
+
+
+def _ledger_key(grid, pack, entry, axis, v, sp, work, tg, plain=True):
+    """-> (the PromiseLedger kept on the PACK: every stepper on it shares it; this call's key, None when not eligible)"""
+    nf = pack.__dict__.get('_nofb')
+    if nf is None:
+        nf = pack._nofb = PromiseLedger()
+    if not nf.eligible(sp, work, tg, plain):
+        return nf, None
+    return nf, (entry, axis, v, sp, grid.mask_version, getattr(pack, 'mask_version', None), grid.shape, grid.sx,
+                None if pack.d_dir_mask is None else pack.d_dir_mask.data_ptr())
+
+
+def _sweep_into(axis, t_in, t_out, grid, mat, params, pack, Tinf, variant=None, xlo=None, xhi=None, dense=False):
+    _, gam = _gam(grid, mat, params)
+    _, work, wb = grid.scratch(2)
+    v = pack.variant if variant is None else variant
+    sp = _sparse_arg(grid, pack, dense)
+    nf, key = _ledger_key(grid, pack, 'sweep', axis, v, sp, work, params.theta * gam,
+                          plain=not (axis == 2 and (xlo is not None or xhi is not None)))
+    check(lib.adi_sweep_bricks(axis, v, _p(t_in), _p(grid.d_flags), _p(grid.d_bricks), _p(pack.d_coeff), _p(pack.d_dir_mask),
+                        _p(pack.d_dir_val), _p(pack.d_qflux), *grid.layout.pd,
+                        sp | nf.bit(key), params.theta,
+                        gam, params.dt, float(Tinf), _p(t_out),
+                        _p(xlo), _p(xhi), _fc_arg(grid, pack, sp),
+                        _p(work), wb, _stream()))
+    nf.learn(key, work, grid.mask_version)
+
+
+def fused_supported(grid, cond_pass=False):
+    """explicit stage folded into the axis-0 sweep (adi_explicit_sweep0, ABI v7) available for this grid"""
+    return bool(lib.adi_explicit_fused_supported(*grid.layout.pd, 1 if cond_pass else 0))
+
+
+def valid_range(t):
+    """element offsets relative to t's first element that lie inside its storage: the [valid_lo, valid_hi) of
+    adi_explicit_sweep0 / adi_explicit_condense0"""
+    off = t.storage_offset()
+    return -off, t.untyped_storage().nbytes() // t.element_size() - off
+
+
+def _explicit_sweep0_into(t, t_out, grid, mat, params, pack, Tinf, variant=None, dense=False):
+    """stages 1+2 of adi_step_numba_coeff (adi3d_numba_coeff.py:292-299) in one pass: R0 is evaluated inside the
+    loads of the axis-0 sweep.  Neighbours are read anywhere inside t's storage."""
+    kappa, gam = _gam(grid, mat, params)
+    _, work, wb = grid.scratch(2)
+    v = pack.variant if variant is None else variant
+    vlo, vhi = valid_range(t)
+    sp = _sparse_arg(grid, pack, dense)
+    nf, key = _ledger_key(grid, pack, 'fused', 0, v, sp, work, params.theta * gam)
+    check(lib.adi_explicit_sweep0_bricks(v, _p(t), vlo, vhi, _p(grid.d_flags), _p(grid.d_bricks), _p(pack.d_coeff),
+                                         _p(pack.d_dir_mask),
+                                  _p(pack.d_dir_val), _p(pack.d_qflux), *grid.layout.pd,
+                                  sp | nf.bit(key), grid.dx, params.dt, kappa, params.theta,
+                                  float(Tinf), _p(t_out), None, None, _fc_arg(grid, pack, sp), _p(work), wb, _stream()))
+    nf.learn(key, work, grid.mask_version)
+
+
+def adi_explicit_sweep_axis0(Tn, grid, mat, params, pack, Tinf=0.0, variant=None, dense=False):
+    """U of adi3d_numba_coeff.py:299 straight from Tn (stage entry point of the fused kernel)."""
+    t, kind = _as_state(Tn, grid)
+    if variant == _lib.SWEEP_GENERAL or (variant is None and pack.variant == _lib.SWEEP_GENERAL):
+        _ensure_general(pack)
+    out = grid.layout.empty()
+    _explicit_sweep0_into(t, out, grid, mat, params, pack, Tinf, variant, dense)
+    return _wrap(out, kind)
+
+
+def adi_sweep_axis(axis, stage_in, grid, mat, params, pack, Tinf=0.0, variant=None, dense=False):
+    """sweep_axis0/1/2 of adi3d_numba_coeff.py:133-237 for one axis (stage entry point).
+    variant=None picks the leanest kernel the pack allows; variant=_lib.SWEEP_GENERAL with dense=True forces
+    the 42 B/cell general-pack kernel that reads every pack array in full, like the reference does."""
+    t, kind = _as_state(stage_in, grid)
+    if variant == _lib.SWEEP_GENERAL or (variant is None and pack.variant == _lib.SWEEP_GENERAL):
+        _ensure_general(pack)
+    out = grid.layout.empty()
+    _sweep_into(axis, t, out, grid, mat, params, pack, Tinf, variant, dense=dense)
+    return _wrap(out, kind)
+
+
+def _ensure_general(pack):
+    """materialise the arrays a forced general-pack sweep reads (zeros, like the reference's packs)"""
+    L = pack.layout
+    if pack.d_dir_mask is None:
+        pack.d_dir_mask = L.empty(torch.uint8, zero=True)
+    if pack.d_dir_val is None:
+        pack.d_dir_val = L.empty(zero=True)
+    if pack.d_qflux is None:
+        pack.d_qflux = L.empty(zero=True)
+
+
+def _check_extras(grid, mat, packs, source, surface_loss, phase, history):
+    """TypeError / ValueError for an optional argument of the step that is of the wrong kind or was made for other packs, another
+    grid or another cp: once per adi_step_hip_coeff call and once per StagedStepper, before anything is launched"""
+    if source is not None and not isinstance(source, GoldakSource):
+        raise TypeError("source must be a GoldakSource (pass a source field, e.g. ScanPath.sample_step, to "
+                        "adi_step_numba_coeff)")
+    if surface_loss is not None:
+        if not isinstance(surface_loss, LossPacks):
+            raise TypeError("surface_loss must be a LossPacks")
+        if len(packs) != 3 or any(p is not q for p, q in zip(packs, surface_loss.packs)):
+            raise ValueError("surface_loss: the step must be given the LossPacks' own packs (surface_loss.packs)")
+    if phase is not None:
+        if not isinstance(phase, PhaseField):
+            raise TypeError("phase must be a PhaseField")
+        if phase.grid is not grid:
+            raise ValueError("phase: the PhaseField belongs to another grid")
+        if float(phase.mat.cp) != float(mat.cp):
+            raise ValueError("phase: the PhaseField was made for cp = %r, the step runs with %r" % (phase.mat.cp, mat.cp))
+    if history is not None:
+        if not isinstance(history, ThermalHistory):
+            raise TypeError("history must be a ThermalHistory")
+        if history.grid is not grid:
+            raise ValueError("history: the ThermalHistory belongs to another grid")
+
+
+def _no_mark():
+    pass
+
+
+def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, source=None, owner=None, t_set=None,
+                 surface_loss=None, phase=None, history=None, captured=False, mark=_no_mark):
+    """THE launch sequence of one step t_in -> out (fp64 tensors in the grid's layout; nothing is allocated): the surface-loss
+    update from t_in, the explicit stage and sweep 0 (one launch when `fused`), the moving source's correction of sweep 0's
+    output, sweeps 1 and 2, the latent-heat correction of `out`, the history record.  Every form of the step calls it --
+    adi_step_hip_coeff with or without a source field, StagedStepper.step, and what StagedStepper.run captures -- with
+    arguments that _check_extras has passed.
+    d_S: a source FIELD in the grid's layout; the explicit stage takes it (adi_explicit_rhs_src), never fused.
+    source, owner: a GoldakSource and the object that holds its device block and workspace; t_set: the step's start time if the
+    block is to be set here, just ahead of the correction (None: the caller has set it).
+    captured: a graph may replay these launches and the caller keeps the clocks: the source's block is ticked after the
+    correction, and the history launches its record without moving its host clock.  Otherwise no tick, and history.record.
+    mark: called at the stage boundaries of per-stage timing: before the explicit stage, between it and sweep 0 when they are
+    two launches, after sweep 0 with the source's correction, after sweep 1 and after sweep 2."""
+    (ta, tb), _, _ = grid.scratch(2)
+    if surface_loss is not None:
+        surface_loss.update(t_in, Tinf)
+    mark()
+    if fused and d_S is None:
+        _explicit_sweep0_into(t_in, tb, grid, mat, params, packs[0], Tinf)
+    else:
+        if d_S is None:
+            kappa, _ = _gam(grid, mat, params)
+            check(lib.adi_explicit_rhs(_p(t_in), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt,
+                                       kappa, params.theta, _p(ta), _stream()))
+        else:
+            _explicit_src_into(t_in, d_S, ta, grid, mat, params)
+        mark()
+        _sweep_into(0, ta, tb, grid, mat, params, packs[0], Tinf)
+    if source is not None:
+        if t_set is not None:
+            source.set_block(_source_block(owner), t_set, params.dt)
+        _source_lines0_into(tb, grid, mat, params, packs[0], source, owner)
+        if captured:
+            check(lib.adi_source_tick(_p(_source_block(owner)), _stream()))
+    mark()
+    _sweep_into(1, tb, ta, grid, mat, params, packs[1], Tinf)
+    mark()
+    _sweep_into(2, ta, out, grid, mat, params, packs[2], Tinf)
+    mark()
+    if phase is not None:
+        phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
+    if history is not None:
+        if captured:
+            history._launch_record(t_in, out)
+        else:
+            history.record(t_in, out, params.dt)
+
+
+def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None, phase=None, history=None):
+    """adi3d_numba_coeff.py:290-302 / adi3d_gpu_coeff.py:213-230: explicit stage, then the three
+    implicit sweeps in the order axis 0, 1, 2.  Returns a NEW array of the kind it was given;
+    `Tn` is never modified.
+
+    S: volumetric heat source in W/m^3 (include/adi_hip.h, "Volumetric heat source"): R0 gains dt*q/(rho cp) on in-mask
+    cells, q evaluated at the step's mid-time.  None: the step of the reference, the same launches as without the keyword.
+    An array of the grid's shape (NumPy / torch / DeviceField): the field form -- explicit stage with the source
+    (adi_explicit_rhs_src), then the three unfused sweeps.  A GoldakSource: evaluated at t + dt/2 on the device and added
+    to the output of sweep 0 by superposition (adi_source_lines0), after whichever sweep-0 form the step uses.  A ScanPath is
+    not accepted here: pass the field ScanPath.sample_step(grid, t, dt).
+    t: the step's start time, used only by a source object.
+    surface_loss: a LossPacks whose `.packs` are `packs`: their Robin coefficients are first rewritten from Tn (the law at the
+    temperature at the start of the step, adi_surface_loss_update), then the step runs as above.  None: no such launch.
+    phase: a PhaseField of the grid: after sweep 2 the step's output is corrected for the latent heat from the liquid fraction
+    the PhaseField holds, which moves on with it (adi_phase_apply, the last launch, on the freshly allocated output).  None: no
+    such launch.
+    history: a ThermalHistory of the grid: the step Tn -> result (after the correction of `phase`) is recorded at the recorder's
+    own clock, which moves on by dt (adi_history_record and adi_history_tick, the last launches).  None: no such launch.
+    Every optional argument is checked before the first launch (_check_extras); the launches are _launch_step's."""
+    if isinstance(S, ScanPath):
+        raise TypeError("adi_step_hip_coeff: a ScanPath has no device evaluator; pass its field, "
+                        "S=path.sample_step(grid, t, dt)")
+    source = S if isinstance(S, GoldakSource) else None
+    _check_extras(grid, mat, packs, source, surface_loss, phase, history)
+    if history is not None:
+        history._check_mask()
+    t_in, kind = _as_state(Tn, grid)
+    d_S = None
+    if S is not None and source is None:
+        if tuple(S.shape) != grid.shape:
+            raise ValueError("S has shape %s, the grid %s" % (tuple(S.shape), grid.shape))
+        d_S = grid.layout.to_layout(S, torch.float64)
+    out = grid.layout.empty()
+    _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused_supported(grid), d_S=d_S, source=source, owner=grid, t_set=t,
+                 surface_loss=surface_loss, phase=phase, history=history)
+    return _wrap(out, kind)
+
+
+def _explicit_src_into(t, d_S, out, grid, mat, params):
+    kappa, _ = _gam(grid, mat, params)
+    check(lib.adi_explicit_rhs_src(_p(t), _p(d_S), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt, kappa,
+                                   params.theta, mat.rho, mat.cp, _p(out), _stream()))
+
+
+def _source_lines0_into(U, grid, mat, params, pack, src, owner):
+    """U += A0^-1 s on the axis-0 lines the support can meet (adi_source_lines0), in place; the block and the workspace
+    are `owner`'s"""
+    _, gam = _gam(grid, mat, params)
+    sp = _sparse_arg(grid, pack, False)
+    work = _source_work(owner, grid.layout.pd[:3], grid.dx, src)
+    check(lib.adi_source_lines0(_p(_source_block(owner)), ctypes.byref(src.as_c()), _p(U), _p(grid.d_flags),
+                                _p(pack.d_coeff), _p(pack.d_dir_mask if pack.has_dir else None), *grid.layout.pd, sp,
+                                grid.dx, params.theta, gam, params.dt, mat.rho, mat.cp, _fc_arg(grid, pack, sp),
+                                _p(work), 0 if work is None else work.numel(), _stream()))
+
+
+# the reference's backend-specific names, so its drivers run unchanged on this module
+adi_step_numba_coeff = adi_step_hip_coeff
+adi_step_gpu_coeff = adi_step_hip_coeff
+
+
+class StagedStepper:
+    """The step of adi_step_hip_coeff with its arguments resolved once, for tight loops over a
+    device-resident field (drivers call the step `nsub` times with the same packs and dt,
+    quick_compare_dirichlet_robin.py:169-178).  `events`: optional list of 5 torch.cuda.Event recorded on
+    the launch stream before/between/after the four stage kernels (per-stage HIP-event timing).  With `phase=` (a PhaseField
+    of the grid) the latent-heat correction is the last launch of every step, after the last of the five marks: the stage
+    times stay those of the stage kernels.  With `history=` (a ThermalHistory of the grid) the record launch and its tick follow,
+    the last launches of every step; `run` sets the recorder's block from the recorder's own clock `history.t` (not from `t0`,
+    which stays the source's time origin) and moves that clock on by nsteps*dt."""
+
+    def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None, surface_loss=None, phase=None,
+                 history=None):
+        _check_extras(grid, mat, packs, source, surface_loss, phase, history)
+        self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
+        # temperature-dependent surface loss: the packs' Robin coefficients rewritten from the step's INPUT buffer, the first
+        # launch of every step -- captured with it (X -> Y reads X, Y -> X reads Y); the law travels by value in that launch,
+        # so its parameters are part of run()'s graph key
+        self.surface_loss = surface_loss
+        # latent heat: the correction of the step's OUTPUT buffer, the last launch of every step -- captured with it; the law
+        # travels by value and f and the summary by pointer, so all three are part of run()'s graph key
+        self.phase = phase
+        # thermal history: the record of the step input -> output and the tick of its block, the last launches of every step
+        # -- captured with it; the levels travel by value and the five buffers by pointer, so all are part of run()'s graph key
+        self.history = history
+        # moving source: corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step counter
+        # a captured tick advances -- power, origin, velocity, eta and f_f may change between runs without a new graph
+        self.source = source
+        self.captures = 0              # HIP graphs captured by run() so far
+        self.fused = fused_supported(grid) if fused is None else (bool(fused) and fused_supported(grid))
+        if self.fused:
+            # the fused kernel reads T + flags (+ the pack arrays of the axis-0 sweep) and writes U: the sweep's own
+            # byte count (SURVEY.md 8(d) variant rule); R0 never reaches HBM
+            self.stage_names = ['explicit+sweep_axis0', 'sweep_axis1', 'sweep_axis2_contig']
+            self.stage_bytes_per_cell = [p.bytes_per_cell for p in packs]
+        else:
+            self.stage_names = ['explicit', 'sweep_axis0', 'sweep_axis1', 'sweep_axis2_contig']
+            self.stage_bytes_per_cell = [float(_lib.EXPLICIT_BYTES_PER_CELL)] + [p.bytes_per_cell for p in packs]
+
+    def sweep_into(self, axis, t_in, t_out, variant=None, dense=False):
+        if variant == _lib.SWEEP_GENERAL:
+            _ensure_general(self.packs[axis])
+        _sweep_into(axis, t_in, t_out, self.grid, self.mat, self.params, self.packs[axis], self.Tinf, variant,
+                    dense=dense)
+
+    def _step_into(self, t, out, captured=True, mark=_no_mark):
+        """one step t -> out (both native-layout device tensors), no allocation: what a HIP graph captures"""
+        _launch_step(t, out, self.grid, self.mat, self.params, self.packs, self.Tinf, self.fused, source=self.source, owner=self,
+                     surface_loss=self.surface_loss, phase=self.phase, history=self.history, captured=captured, mark=mark)
+
+    def run(self, T, nsteps, graph=True, t0=0.0):
+        """The drivers' `nsub` loop (quick_compare_dirichlet_robin.py:169-178, waam_from_stl_v7_mm.py:525-528): `nsteps`
+        steps with the same packs and dt on a device-resident field, returned as a new DeviceField.  The launches of
+        two steps (X -> Y -> X) are captured once into a HIP graph and replayed, so small grids are not bound by the
+        host's launch path (64^3: 3 kernels + 3 memsets per step, each a ctypes call); the graph is rebuilt when dt,
+        theta, Tinf, the mask or the packs change.  graph=False: plain launches.
+        t0: time at the start of the first step (a source's step i runs at t0 + i*dt + dt/2); the source's block is
+        written here, so its power / origin / velocity as they are now hold for this run, and a change of its support's
+        extent recaptures."""
+        g, prm = self.grid, self.params
+        nsteps = int(nsteps)
+        key = (float(prm.dt), float(prm.theta), self.Tinf, g.mask_version, tuple(id(p) for p in self.packs),
+               tuple(getattr(p, 'mask_version', None) for p in self.packs),
+               tuple(None if p.d_coeff is None else p.d_coeff.data_ptr() for p in self.packs), self.fused,
+               None if self.source is None else self.source.shape_key(),
+               None if self.surface_loss is None else self.surface_loss.loss.key(),
+               None if self.phase is None else self.phase.graph_key(),
+               None if self.history is None else self.history.graph_key())
+        if self.history is not None:
+            self.history._check_mask()
+        st = getattr(self, '_graph', None)
+        if st is None or st['key'] != key:
+            X, Y = g.layout.empty(), g.layout.empty()
+            st = self._graph = dict(key=key, X=X, Y=Y, g=None)
+        X, Y = st['X'], st['Y']
+        X.copy_(g.layout.to_layout(T, torch.float64))
+        if self.source is not None:
+            self.source.set_block(_source_block(self), t0, prm.dt)
+        if graph and nsteps >= 2 and st['g'] is None:
+            g.scratch(2)                                   # every buffer exists before the capture
+            stateful = [x for x in (self.phase, self.history) if x is not None]
+            held = [x.snapshot() for x in stateful]        # (the warm-up steps would advance f, the history, its log and clock)
+            if self.history is not None:
+                self.history.set_clock(prm.dt)
+            self._step_into(X, Y); self._step_into(Y, X)   # warm-up outside the capture (lazy module loads, and the
+            self._step_into(X, Y); self._step_into(Y, X)   # no-fallback promise is learnt on the third step); harmless:
+            X.copy_(g.layout.to_layout(T, torch.float64))  # X is restored
+            for x, snap in zip(stateful, held):
+                x.restore(snap)                            # ... and so is what the extras hold
+            torch.cuda.synchronize()
+            cg = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(cg):
+                self._step_into(X, Y)
+                self._step_into(Y, X)
+            st['g'] = cg
+            self.captures += 1
+        if self.source is not None:
+            self.source.set_block(_source_block(self), t0, prm.dt)   # (after the warm-up: the counter starts at 0)
+        if self.history is not None:
+            self.history.set_clock(prm.dt)                 # (likewise; the recorder's own clock, not t0)
+        done = 0
+        if graph and st['g'] is not None:
+            for _ in range(nsteps // 2):
+                st['g'].replay()
+            done = 2 * (nsteps // 2)
+        cur, oth = X, Y
+        for _ in range(nsteps - done):
+            self._step_into(cur, oth)
+            cur, oth = oth, cur
+        if self.history is not None:
+            self.history.advance_clock(self.history.t, float(prm.dt), nsteps)
+        out = g.layout.empty()
+        out.copy_(cur)
+        return DeviceField(out)
+
+    def step(self, T, events=None, t=0.0):
+        """one step from time t (the source, if any, at t + dt/2)"""
+        g, prm = self.grid, self.params
+        if self.source is not None:
+            self.source.set_block(_source_block(self), t, prm.dt)
+        t_in = g.layout.to_layout(T, torch.float64)
+        out = g.layout.empty()
+        ev = iter(events or ())
+        self._step_into(t_in, out, captured=False, mark=(lambda: next(ev).record()) if events else _no_mark)
+        return DeviceField(out)

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import FACES, check, lib, ptr_array
-from .adi3d_hip_coeff import DeviceField, Layout
+from .fields import DeviceField, Layout
 
 __all__ = ['STLBoundaryCorrector', 'build_corrected_robin_fields', 'TriangleMesh', 'load_stl']
 

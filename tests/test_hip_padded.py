@@ -1,5 +1,5 @@
 """Padded extents: a ragged (nx, ny, nz) grid is allocated as the physical box adi_recommended_dims() picks, the extra
-cells are off-mask, the kernels run on the physical box and the caller sees the logical one (Layout, adi3d_hip_coeff.py).
+cells are off-mask, the kernels run on the physical box and the caller sees the logical one (Layout, fields.py).
 The fuzz and parity suites cover these layouts implicitly (any long axis that is not a friendly length); this file pins
 the properties of the mechanism itself."""
 import ctypes
