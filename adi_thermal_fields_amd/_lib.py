@@ -161,6 +161,10 @@ SIGNATURES = {
     'adi_source_workspace_bytes': (c_int, [c_void_p, c_int, c_int, c_int, c_double, ctypes.POINTER(c_size_t)]),
     'adi_explicit_rhs_src': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double,
                                      c_double, c_double, c_double, c_void_p, c_void_p]),
+    'adi_scan_sample_host': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_int, c_int, c_double, c_double,
+                                     c_double, c_void_p]),
+    'adi_scan_sample': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_int, c_int, c_long, c_double, c_double,
+                                c_double, c_void_p, c_void_p]),
     'adi_surface_loss_update': (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double,
                                         c_double, c_double, c_void_pp, c_int, c_int, c_int, c_void_p]),
     'adi_phase_summary_words': (ctypes.c_long, [c_int, c_int, c_int]),
@@ -196,6 +200,7 @@ MIXED_MIN_TG = 1e-9           # kMixedMinTg (csrc/adi_core.hpp): below this thet
 MAX_BOX_CELLS = 1 << 32       # ADI_MAX_BOX_CELLS: nx * plane_stride of a Cartesian box stays below it
 SOURCE_BLOCK_BYTES = 128     # ADI_SOURCE_BLOCK_BYTES
 SOURCE_E_CUT = 40.0          # ADI_SOURCE_E_CUT
+SCAN_TABLE_COLS = 8          # ADI_SCAN_TABLE_COLS: { t_begin, p[3], d[2], speed, power }
 SURFACE_LOSS_MAX_KNOTS = 16  # ADI_SURFACE_LOSS_MAX_KNOTS
 SURFACE_LOSS_SIGMA = 5.670374419e-8   # ADI_SURFACE_LOSS_SIGMA (Stefan-Boltzmann, CODATA 2018)
 HISTORY_BLOCK_BYTES = 40     # ADI_HISTORY_BLOCK_BYTES: { double t0, dt; int64 n, slot, capacity }
@@ -209,6 +214,12 @@ class HeatSource(ctypes.Structure):
     _fields_ = [('power', c_double), ('eta', c_double), ('a', c_double), ('b', c_double), ('c_f', c_double),
                 ('c_r', c_double), ('f_f', c_double), ('origin', c_double * 3), ('velocity', c_double),
                 ('travel_axis', c_int), ('travel_sign', c_int), ('depth_axis', c_int), ('reserved', c_int)]
+
+
+class ScanShape(ctypes.Structure):
+    """adi_scan_shape (include/adi_hip.h)"""
+    _fields_ = [('eta', c_double), ('a', c_double), ('b', c_double), ('c_f', c_double), ('c_r', c_double), ('f_f', c_double),
+                ('depth_axis', c_int), ('reserved', c_int)]
 
 
 class SurfaceLossLaw(ctypes.Structure):

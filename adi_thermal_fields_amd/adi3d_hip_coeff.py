@@ -28,7 +28,7 @@ precompute_coeff_packs_unified(grid, ...) call, which is the documented synchron
 
 Where things live: this module defines nothing, it re-exports.  fields.py -- Layout, DeviceField, to_device, Grid3D and the
 device helpers; packs.py -- Material, Params, AxisCoeffPack, exposed_mask, precompute_coeff_packs_unified; heat_source.py --
-GoldakSource, ScanPath and the one host definition of Goldak's double ellipsoid; deposition.py -- the surface impulse, the
+GoldakSource, ScanPath, ScanPathSource and the one host definition of Goldak's double ellipsoid; deposition.py -- the surface impulse, the
 perimeter ratio, birth_planes, BirthPacks; surface_loss.py -- SurfaceLoss, LossPacks; phase.py -- PhaseChange, PhaseField;
 history.py -- HistoryLevels, ThermalHistory; step.py -- the stage entry points, the launch sequence, adi_step_hip_coeff,
 StagedStepper.  Each imports only those before it in this list ("Module map"); code inside the package imports
@@ -41,7 +41,7 @@ from ._lib import lib, check, ptr_array
 from .fields import (_MASK_VERSIONS, _device, _stream, _p, _sweep_workspace_bytes, recommended_dims, Layout, DeviceField,
                      to_device, Grid3D, _wrap)
 from .packs import Material, Params, AxisCoeffPack, exposed_mask, _fc_arg, precompute_coeff_packs_unified
-from .heat_source import GoldakSource, ScanPath, _source_block, _source_work
+from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .deposition import (apply_surface_impulse_Q, exposed_faces_per_layer, count_exposed_faces, perimeter_ratio, birth_planes,
                          BirthPacks)
 from .surface_loss import SurfaceLoss, LossPacks
@@ -57,6 +57,7 @@ __all__ = ['Grid3D', 'Material', 'Params', 'AxisCoeffPack', 'exposed_mask', 'pre
            'exposed_faces_per_layer', 'count_exposed_faces', 'perimeter_ratio', 'birth_planes', 'BirthPacks',
            'GoldakSource', 'ScanPath', 'SurfaceLoss', 'LossPacks', 'PhaseChange', 'PhaseField', 'HistoryLevels',
            'ThermalHistory']
+# (ScanPathSource is exported like the names above but is not part of the pinned `__all__`)
 
 # an assignment to a name above reaches the module that defined it (_facade.ReExporting)
 sys.modules[__name__].__class__ = ReExporting

@@ -1,5 +1,7 @@
 """Goldak's double-ellipsoid heat source on the host: its one definition (`goldak_shape`, `goldak_q`), the moving source
-`GoldakSource`, the step-averaged `ScanPath`, and the device block and workspace a moving source's owner keeps."""
+`GoldakSource`, the step-averaged `ScanPath` with its frozen form `ScanPathSource`, which the library evaluates, and the device
+block and workspace a moving source's owner keeps."""
+import copy
 import ctypes
 import math
 
@@ -166,7 +168,8 @@ _erf = np.frompyfunc(math.erf, 1, 1)
 class ScanPath:
     """Goldak's double ellipsoid driven along a path of straight segments (README, "Scan paths"): the HOST definition
     of its step-averaged heat input.  A step takes it as a source field, adi_step_numba_coeff(..., S=path.sample_step(grid, t,
-    dt)); a path is not accepted as `S=` itself or as `source=` of a StagedStepper (there is no device evaluator).
+    dt)); a path is not accepted as `S=` itself or as `source=` of a StagedStepper.  `path.on_device()` freezes it into a
+    ScanPathSource, whose `sample_step_device` evaluates the same field on the device (no NumPy erf, nothing over PCIe).
     Shape as GoldakSource: efficiency eta, a (half-width across the leg), b (depth), c_f / c_r (front / rear length) [m], front
     fraction f_f; depth along depth_axis, the other two axes in increasing order are the in-plane axes (u, v).  `power` [W] is
     the default of line_to.
@@ -325,6 +328,10 @@ class ScanPath:
             path.line_to(pt(q1), speed)
         return path
 
+    def on_device(self):
+        """the path as it is now, frozen for the device: a ScanPathSource"""
+        return ScanPathSource(self)
+
     # ---- plain readings
     @property
     def t_end(self):
@@ -471,3 +478,71 @@ class ScanPath:
             si, sj, sk = self._index_box(k, pc, n, dx)
             q[si, sj, sk] += self._qbar(k, x[0][si, None, None], x[1][None, sj, None], x[2][None, None, sk], t, dt)
         return np.where(np.asarray(grid.mask, dtype=bool), q, 0.0)
+
+
+class ScanPathSource:
+    """A ScanPath frozen for the device (`ScanPathSource(path)`, `path.on_device()`).  It snapshots the path's segment table,
+    t_start, t_end, shape and depth_axis: later line_to / dwell calls on `path` do not reach it, and nothing of it can be changed
+    (another power or path: make a new one).  It owns one device tensor, the table (K x 8 fp64 as ScanPath.table(), then
+    t_end), allocated here on the current device and never written again.  ValueError for a path without segments.
+    `sample_step_device(grid, t, dt)` is q_step of the step [t, t + dt] evaluated by the device (adi_scan_sample: include/adi_hip.h,
+    "Scan path"), a DeviceField for the `S=` argument of adi_step_numba_coeff; `sample_step_host` the same code run by the library
+    on the CPU; `sample_step` the NumPy definition of the snapshot.  Like a ScanPath it is not itself accepted as `S=` or as
+    `source=` of a StagedStepper."""
+
+    def __init__(self, path):
+        if not isinstance(path, ScanPath):
+            raise TypeError("ScanPathSource: a ScanPath is needed, got %s" % type(path).__name__)
+        tab = path.table()                                   # (ValueError: the path has no segment)
+        eta, a, b, cf, cr, ff = path.validate()
+        snap = copy.copy(path)
+        snap._seg = list(path._seg)
+        self._path = snap                                    # the host definition of this very snapshot
+        self.K = int(tab.shape[0])
+        self.t_start, self.t_end = float(path.t_start), float(path.t_end)
+        self.shape_params = (eta, a, b, cf, cr, ff)
+        self.depth_axis = int(path.depth_axis)
+        self._h_table = np.ascontiguousarray(np.concatenate([tab.ravel(), [self.t_end]]), dtype=np.float64)
+        self._h_table.setflags(write=False)
+        self._c_shape = _lib.ScanShape(eta, a, b, cf, cr, ff, self.depth_axis, 0)
+        one = np.empty(1)                                    # (the library's own checks of the table, before any launch)
+        check(lib.adi_scan_sample_host(*self._path_args(self._h_table.ctypes.data), None, 1, 1, 1, 1.0, self.t_start, 1.0,
+                                       one.ctypes.data))
+        dev = _device() if torch.cuda.is_available() else torch.device('cpu')   # (no GPU: the host evaluators only)
+        self.d_table = torch.from_numpy(self._h_table.copy()).to(dev)
+
+    def table(self):
+        """the snapshot's segments, (K, 8) float64, read-only"""
+        return self._h_table[:-1].reshape(self.K, _lib.SCAN_TABLE_COLS)
+
+    def graph_key(self):
+        """what a launch holds of the source: the table's address, K and the shape"""
+        return (self.d_table.data_ptr(), self.K, self.shape_params + (self.depth_axis,))
+
+    def _path_args(self, table):
+        return ctypes.byref(self._c_shape), table, self.K, self.t_end
+
+    # ---- the host definition
+    def sample_step(self, grid, t, dt):
+        """ScanPath.sample_step of the snapshot (NumPy: the ground truth the tests hold the kernels to)"""
+        return self._path.sample_step(grid, t, dt)
+
+    def sample_step_host(self, grid, t, dt):
+        """the library's evaluator on the CPU (adi_scan_sample_host, no GPU needed): q_step at the cell centres of anything with
+        nx, ny, nz, dx and mask, 0 off the mask"""
+        n = (int(grid.nx), int(grid.ny), int(grid.nz))
+        mask = np.ascontiguousarray(np.asarray(grid.mask, dtype=bool), dtype=np.uint8)
+        if mask.shape != n:
+            raise ValueError("sample_step_host: the mask has shape %s, the grid %s" % (mask.shape, n))
+        out = np.empty(n, dtype=np.float64)
+        check(lib.adi_scan_sample_host(*self._path_args(self._h_table.ctypes.data), mask.ctypes.data, *n, float(grid.dx),
+                                       float(t), float(dt), out.ctypes.data))
+        return out
+
+    # ---- the device
+    def sample_step_device(self, grid, t, dt):
+        """q_step of the step [t, t + dt] at the cell centres, evaluated on the device (adi_scan_sample): a DeviceField"""
+        out = grid.layout.empty()
+        check(lib.adi_scan_sample(*self._path_args(_p(self.d_table)), _p(grid.d_flags), *grid.layout.pd, grid.dx, float(t),
+                                  float(dt), _p(out), _stream()))
+        return DeviceField(out)

@@ -9,7 +9,7 @@ from ._lib import lib, check
 from ._ledger import PromiseLedger
 from .fields import DeviceField, _as_state, _wrap, _p, _stream
 from .packs import _fc_arg
-from .heat_source import GoldakSource, ScanPath, _source_block, _source_work
+from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .surface_loss import LossPacks
 from .phase import PhaseField
 from .history import ThermalHistory
@@ -215,8 +215,9 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     cells, q evaluated at the step's mid-time.  None: the step of the reference, the same launches as without the keyword.
     An array of the grid's shape (NumPy / torch / DeviceField): the field form -- explicit stage with the source
     (adi_explicit_rhs_src), then the three unfused sweeps.  A GoldakSource: evaluated at t + dt/2 on the device and added
-    to the output of sweep 0 by superposition (adi_source_lines0), after whichever sweep-0 form the step uses.  A ScanPath is
-    not accepted here: pass the field ScanPath.sample_step(grid, t, dt).
+    to the output of sweep 0 by superposition (adi_source_lines0), after whichever sweep-0 form the step uses.  A ScanPath or a
+    ScanPathSource is not accepted here: pass the field, ScanPath.sample_step(grid, t, dt) or, evaluated on the device,
+    ScanPathSource.sample_step_device(grid, t, dt).
     t: the step's start time, used only by a source object.
     surface_loss: a LossPacks whose `.packs` are `packs`: their Robin coefficients are first rewritten from Tn (the law at the
     temperature at the start of the step, adi_surface_loss_update), then the step runs as above.  None: no such launch.
@@ -226,9 +227,9 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     history: a ThermalHistory of the grid: the step Tn -> result (after the correction of `phase`) is recorded at the recorder's
     own clock, which moves on by dt (adi_history_record and adi_history_tick, the last launches).  None: no such launch.
     Every optional argument is checked before the first launch (_check_extras); the launches are _launch_step's."""
-    if isinstance(S, ScanPath):
-        raise TypeError("adi_step_hip_coeff: a ScanPath has no device evaluator; pass its field, "
-                        "S=path.sample_step(grid, t, dt)")
+    if isinstance(S, (ScanPath, ScanPathSource)):
+        raise TypeError("adi_step_hip_coeff: a scan path enters the step as its field: S=path.sample_step(grid, t, dt) from the "
+                        "host, or S=path.on_device().sample_step_device(grid, t, dt) evaluated on the device")
     source = S if isinstance(S, GoldakSource) else None
     _check_extras(grid, mat, packs, source, surface_loss, phase, history)
     if history is not None:

@@ -622,6 +622,47 @@ int adi_explicit_rhs_src(const double *d_T, const double *d_S, const uint8_t *d_
                          double *d_R0, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Scan path: Goldak's double ellipsoid driven along straight segments, STEP-AVERAGED.  The source of a step [t, t + dt] is
+ *     q_step(x) = sum over the segments k, ascending, of (1/dt) * integral over [t, t + dt] n [t_k, t_{k+1}] of q_k(x, tau) dtau
+ * with q_k the double ellipsoid above in the frame of segment k (xi along its in-plane direction d, y across it, z along
+ * depth_axis; the other two axes in increasing order are the in-plane axes u, v), its centre at p + d*speed*(tau - t_k).  The
+ * integral is closed (four erf per point) where the piece travels at least 1e-3 min(c_f, c_r), Simpson's rule on three
+ * instantaneous values below that, and the instantaneous value times the piece's length for a dwell.  The cuts bound xi and
+ * (y, z) separately: the exponent of (y, z) at most ADI_SOURCE_E_CUT, xi within sqrt(E_CUT/3) times c_f ahead of the piece's
+ * last centre and c_r behind its first.  The host definition is heat_source.ScanPath (q_step); csrc/adi_scan_eval.hpp follows
+ * it operation for operation, fp64, no contraction, so the device differs from it by the rounding of erf and exp only.
+ *
+ * Segment table: K rows of ADI_SCAN_TABLE_COLS doubles { t_begin, p[3] start point [m], d[2] in-plane unit direction,
+ * speed [m/s], power [W] }, segment k active on [t_begin[k], t_begin[k+1]), the last one up to t_end.  Valid: finite values,
+ * 1 <= K <= ADI_SCAN_MAX_SEGMENTS, t_begin strictly ascending, t_end after the last t_begin, |d| = 1, speed >= 0, power >= 0
+ * (0: a jump or an idle dwell, which deposits nothing); the shape as adi_heat_source.  Everything else is ADI_ERR_ARG,
+ * checked before any HIP call wherever the table is a host array.  A device table (d_table) is the same rows in device
+ * memory; the kernels read it only at rows [0, K), K travelling by value in every launch.
+ *
+ * The step takes the result as a source FIELD (adi_explicit_rhs_src); a correction of sweep 0 from the path itself, as
+ * adi_source_lines0 does for the moving source, is not part of the library.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct adi_scan_shape {
+    double eta;          /* efficiency */
+    double a, b;         /* half-width across the leg, depth [m] */
+    double c_f, c_r;     /* front / rear length [m] */
+    double f_f;          /* front fraction; f_r = 2 - f_f */
+    int depth_axis, reserved;
+} adi_scan_shape;
+
+#define ADI_SCAN_TABLE_COLS 8
+#define ADI_SCAN_MAX_SEGMENTS (1 << 24)
+
+/* q_step of the step [t, t + dt] at the cell centres of a dense C-order (nx, ny, nz) HOST array h_out, 0 where h_mask (same
+ * shape; NULL: every cell) is 0: the evaluator on the CPU.  No HIP call: it runs on a machine without a GPU. */
+int adi_scan_sample_host(const adi_scan_shape *h_shape, const double *h_table, int K, double t_end, const uint8_t *h_mask,
+                         int nx, int ny, int nz, double dx, double t, double dt, double *h_out);
+/* the same on the device into d_out (box layout; 0 on off-mask cells): the twin of adi_source_sample for a window.  d_table:
+ * the K rows in device memory. */
+int adi_scan_sample(const adi_scan_shape *h_shape, const double *d_table, int K, double t_end, const uint8_t *d_flags, int nx,
+                    int ny, int nz, long plane_stride, double dx, double t, double dt, double *d_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Temperature-dependent surface loss of the Cartesian step (no counterpart in the reference, which freezes robin_h when the
  * packs are built; it accepts per-voxel robin_h, so the lagged law below is a sequence of calls the reference can run).
  * Before a step the Robin coefficient of every exposed cell is rewritten from the cell's own temperature T (degrees, the
