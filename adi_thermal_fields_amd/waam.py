@@ -447,8 +447,8 @@ def run_layer_birth_slab(comm, i0, i1, mask_full, dx, mat, params_cls, h, Tinf, 
     dev_loop = on_device and st.device_births_supported()
     if dev_loop:
         E = st.engine
-        m_ext = np.zeros((i1 - i0 + 2, st.ny, st.nz), dtype=np.bool_)          # (the slab's planes may be padded: st._pad)
-        m_ext[1:-1] = st._pad(np.asarray(mask_full[i0:i1], dtype=np.bool_), False)
+        m_ext = np.zeros((i1 - i0 + 2, st.ny, st.nz), dtype=np.bool_)          # (the slab's planes may be padded: st.pad)
+        m_ext[1:-1] = st.pad(np.asarray(mask_full[i0:i1], dtype=np.bool_), False)
         d_full_int = st.Lext.to_layout(m_ext, torch.uint8)[1:-1]
         count = torch.zeros(1, dtype=torch.int64, device=E.device)
         plane_cells = np.asarray(mask_full).sum(axis=(0, 1)).astype(np.int64)
@@ -467,9 +467,8 @@ def run_layer_birth_slab(comm, i0, i1, mask_full, dx, mat, params_cls, h, Tinf, 
     def birth(ks, ke):
         nonlocal T, n_active
         if dev_loop:
-            if not isinstance(T, torch.Tensor) or T.data_ptr() != dist_slab._interior(st._ext_bufs[st._cur]).data_ptr():
-                T = st._logical(dist_slab._interior(st._load_state(T)))   # the state buffer itself (nothing stepped yet)
-            E.birth_planes(st.Lint, T, dist_slab._interior(st.d_mask_ext), d_full_int, ks, ke + 1, Ts, count)
+            T = st.state_interior(T)                     # the state buffer itself (also when nothing has stepped yet)
+            E.birth_planes(st.Lint, T, st.mask_interior(), d_full_int, ks, ke + 1, Ts, count)
             fresh = ~plane_born[ks:ke + 1]
             n_active += int(plane_cells[ks:ke + 1][fresh].sum())
             plane_born[ks:ke + 1] = True
@@ -496,7 +495,7 @@ def run_layer_birth_slab(comm, i0, i1, mask_full, dx, mat, params_cls, h, Tinf, 
         elif what == 'birth':
             birth(*layers[arg])
         elif on_frame is not None:
-            act = st._logical(dist_slab._interior(st.d_mask_ext)).cpu().contiguous().numpy().astype(bool) if dev_loop \
+            act = st.mask_interior(logical=True).cpu().contiguous().numpy().astype(bool) if dev_loop \
                 else mask_act[i0:i1].copy()
             on_frame(arg, np.array(st.local_numpy(T)), act)
     return np.array(st.local_numpy(T)), nsteps
@@ -531,7 +530,7 @@ def run_single_track_slab(comm, i0, i1, plate_mask, track_box, dx, mat, params_c
     for yi in range(ncol):
         if dev_loop:
             if lx0 < lx1:
-                dist_slab._interior(st.d_mask_ext)[lx0:lx1, yi:yi + 1, z0:z1] = 1
+                st.mask_interior()[lx0:lx1, yi:yi + 1, z0:z1] = 1
             st.set_mask_device(z0, z1)                         # collective: halo planes of the mask, flags and packs in place
         else:
             mask[x0:x1, yi:yi + 1, z0:z1] = True

@@ -1,5 +1,5 @@
-"""Reference engine for the slab decomposition (tests only): NumPy/oracle restatements of the five engine
-calls of adi_thermal_fields_amd.dist_slab, on CPU tensors, so the exchange logic and the algebra of the
+"""Reference engine for the slab decomposition (tests only): NumPy/oracle restatements of the engine
+calls of adi_thermal_fields_amd.dist_slab.SlabStepper (product: slab_engine.HipEngine), on CPU tensors, so the exchange logic and the algebra of the
 reduced interface system can be run on gloo ranks without a GPU.  The interface solve here assembles the
 dense (2R x 2R) system per line instead of merging, as an independent check of the product's method."""
 import numpy as np

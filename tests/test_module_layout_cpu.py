@@ -14,6 +14,8 @@ sys.path.insert(0, ROOT)
 PKG = 'adi_thermal_fields_amd'
 # in import order: a module imports only from those before it (and _lib, _ledger)
 MODULES = ['fields', 'packs', 'heat_source', 'deposition', 'surface_loss', 'phase', 'history', 'step']
+# the slab decomposition: dist_slab (SlabStepper) re-exports the comms of slab_comm and the HipEngine of slab_engine
+SLAB_MODULES = ['slab_comm', 'slab_engine', 'dist_slab']
 
 ALL = ['Grid3D', 'Material', 'Params', 'AxisCoeffPack', 'exposed_mask', 'precompute_coeff_packs_unified',
        'adi_step_hip_coeff', 'adi_step_numba_coeff', 'adi_step_gpu_coeff', 'DeviceField', 'to_device',
@@ -63,11 +65,11 @@ def test_every_exported_name_is_its_home_modules_object(hip):
 def fresh_imports():
     """one fresh interpreter per module, all started at once (an interpreter spends its time importing torch)"""
     procs = {m: subprocess.Popen([sys.executable, '-c', 'import %s.%s' % (PKG, m)], cwd=ROOT, stdout=subprocess.DEVNULL,
-                                 stderr=subprocess.PIPE, text=True) for m in MODULES}
+                                 stderr=subprocess.PIPE, text=True) for m in MODULES + SLAB_MODULES}
     return {m: (p.communicate()[1], p.returncode) for m, p in procs.items()}
 
 
-@pytest.mark.parametrize('mod', MODULES)
+@pytest.mark.parametrize('mod', MODULES + SLAB_MODULES)
 def test_module_imports_on_its_own(fresh_imports, mod):
     """(a cycle that only works once the facade has imported everything in order shows up here)"""
     err, rc = fresh_imports[mod]
@@ -96,14 +98,14 @@ def test_no_module_imports_the_facade_and_the_order_holds(mod):
     assert found <= allowed, (mod, sorted(found - allowed))
 
 
-@pytest.mark.parametrize('mod', ['dist_slab', 'adi3d_hip_cyl', 'frame_io', 'voxel_bc_correction', 'waam'])
+@pytest.mark.parametrize('mod', SLAB_MODULES + ['adi3d_hip_cyl', 'frame_io', 'voxel_bc_correction', 'waam'])
 def test_the_packages_other_modules_import_from_the_new_homes(mod):
-    """(dist_slab.HipEngine alone keeps its one handle on the facade, taken inside its constructor)"""
+    """(slab_engine.HipEngine alone keeps its one handle on the facade, taken inside its constructor)"""
     with open(os.path.join(ROOT, PKG, mod + '.py')) as f:
         tree = ast.parse(f.read())
     top = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom))]
     assert not any('adi3d_hip_coeff' in ast.dump(n) for n in top)
-    if mod != 'dist_slab':
+    if mod != 'slab_engine':
         assert 'adi3d_hip_coeff' not in _imports(mod)
 
 
@@ -132,3 +134,13 @@ def test_module_state_exists_once_and_assignment_reaches_the_home(hip):
     finally:
         hip.recommended_dims = real
     assert fields.recommended_dims is real and hip.recommended_dims is real
+
+
+def test_dist_slab_hands_out_the_moved_names_themselves():
+    slab, comm, engine = (importlib.import_module('%s.%s' % (PKG, m)) for m in ('dist_slab', 'slab_comm', 'slab_engine'))
+    assert slab.__all__ == ['SlabStepper', 'TorchDistComm', 'HostStagedDistComm', 'LocalComm', 'LoopbackComm', 'SelfLoopDistComm',
+                            'HipEngine', 'split_planes', 'rccl_env_defaults', 'gather_slabs']
+    for n in comm.__all__:
+        assert getattr(slab, n) is getattr(comm, n), n
+    assert slab.HipEngine is engine.HipEngine and engine.__all__ == ['HipEngine']
+    assert set(comm.__all__) | {'HipEngine', 'SlabStepper'} == set(slab.__all__)
