@@ -9,6 +9,7 @@ import types
 import numpy as np
 import pytest
 
+import cart_dt_cases as cd
 import cases
 import cyl_ref_ld
 import cyl_switch_cases as csc
@@ -25,6 +26,28 @@ def test_oracle_within_a_tenth_of_the_gpu_bar_of_the_long_double_reference(tag, 
     print('oracle vs long double: %-44s %.3e' % (tag, err))
     assert np.all(np.isfinite(got))
     assert err <= 1e-11, (tag, err)
+    # the increment metric of cart_dt_cases: the oracle within a quarter of the bar the GPU sweep is held to
+    f = cd.cyl_figures(got, key)
+    print('%22s inc %.2e K  err %.2e K = %6.2f ulp = %.1e inc' % ('', f['inc'], f['abs_err'], f['ulp'], f['of_inc']))
+    assert f['abs_err'] <= cd.bar(f, cd.A_CYL / 4), (tag, f)
+    _ULP[key] = f['ulp']
+
+
+_ULP = {}
+
+
+def test_recorded_cyl_oracle_worst_is_the_measured_one():
+    """A_CYL as A of cart_dt_cases: 4 x the oracle's worst error at f <= 1e-3 in units of eps64 max|W|, rounded up to 2^n; the
+    recorded worst is not below the measured one and not above twice it"""
+    ks = [key for _, key in csc.dt_params() if key[2] <= 1e-3]
+    for key in ks:
+        if key not in _ULP:
+            _ULP[key] = cd.cyl_figures(csc.run_case(cyl_oracle, csc.dt_case(*key)), key)['ulp']
+    worst = max(_ULP[key] for key in ks)
+    print('worst cylindrical oracle error at f <= 1e-3: %.3f eps64 max|W|; recorded %.3f, A_CYL = %g'
+          % (worst, cd.CYL_ORACLE_WORST_ULP, cd.A_CYL))
+    assert worst <= cd.CYL_ORACLE_WORST_ULP <= 2.0 * worst, (worst, cd.CYL_ORACLE_WORST_ULP)
+    assert cd.A_CYL == cd.bar_factor(cd.CYL_ORACLE_WORST_ULP)
 
 
 class _LdApi:
