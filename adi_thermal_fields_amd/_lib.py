@@ -172,6 +172,11 @@ SIGNATURES = {
                                 c_int, c_long, c_void_p]),
     'adi_phase_seed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                c_long, c_void_p]),
+    'adi_matlaw_theta': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    'adi_matlaw_recover': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long,
+                                   c_void_p]),
+    'adi_matlaw_loss_update': (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long,
+                                       c_double, c_double, c_double, c_void_pp, c_int, c_int, c_int, c_void_p]),
     'adi_history_record': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
     'adi_history_set_clock': (c_int, [c_void_p, c_double, c_double, c_void_p]),
@@ -203,6 +208,7 @@ SOURCE_E_CUT = 40.0          # ADI_SOURCE_E_CUT
 SCAN_TABLE_COLS = 8          # ADI_SCAN_TABLE_COLS: { t_begin, p[3], d[2], speed, power }
 SURFACE_LOSS_MAX_KNOTS = 16  # ADI_SURFACE_LOSS_MAX_KNOTS
 SURFACE_LOSS_SIGMA = 5.670374419e-8   # ADI_SURFACE_LOSS_SIGMA (Stefan-Boltzmann, CODATA 2018)
+MATLAW_MAX_KNOTS = 16        # ADI_MATLAW_MAX_KNOTS
 HISTORY_BLOCK_BYTES = 40     # ADI_HISTORY_BLOCK_BYTES: { double t0, dt; int64 n, slot, capacity }
 HISTORY_LOG_INTS = 8         # ADI_HISTORY_LOG_INTS: { cells, lo[3], hi[3], pad }
 STLCORR_DROPPED = (1 << 63) - 1   # ADI_STLCORR_DROPPED
@@ -231,6 +237,12 @@ class SurfaceLossLaw(ctypes.Structure):
 class PhaseChangeLaw(ctypes.Structure):
     """adi_phase_change (include/adi_hip.h)"""
     _fields_ = [('latent_heat', c_double), ('T_solidus', c_double), ('T_liquidus', c_double)]
+
+
+class MaterialLawC(ctypes.Structure):
+    """adi_material_law (include/adi_hip.h)"""
+    _fields_ = [('n_knots', c_int), ('reserved', c_int), ('k_ref', c_double), ('cp_ref', c_double), ('c_lo', c_double)] + [
+        (name, c_double * 16) for name in ('x', 'kq', 'hks', 'ks2', 'theta', 'c', 'hcs', 'cs2', 'H')]
 
 
 class HistoryLevelsC(ctypes.Structure):

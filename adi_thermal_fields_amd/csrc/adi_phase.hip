@@ -3,14 +3,12 @@
 //   k_phase_apply   every step, T and f in place
 //   k_phase_seed    f = f_eq(T) on selected in-mask cells, 0 off the mask (construction, newborn cells)
 // One workgroup of 256 threads per 16 x 16 x 16 brick of the flags summary; it owns the brick's cells and the brick's word of
-// the phase summary, so nothing is shared between workgroups and no atomic is needed.  A row piece of the brick is 16 doubles
-// = 128 bytes: lane l of a wave owns cells 2(l & 7), 2(l & 7) + 1 of row (l >> 3), so one 16-byte load instruction of a wave
-// covers eight whole 128-byte row pieces, and the eight loads of a thread cover the 256 rows of the brick.  The loads of a
-// thread are issued together ahead of the arithmetic; stores go cell by cell (8 bytes) so that a cell the law leaves alone is
-// never written.  No existing kernel changes.
+// the phase summary, so nothing is shared between workgroups and no atomic is needed.  Which cells a thread owns and how it
+// loads them is in adi_brick_dev.hpp (shared with adi_matlaw.hip).  The loads of a thread are issued together ahead of the
+// arithmetic; stores go cell by cell (8 bytes) so that a cell the law leaves alone is never written.  No existing kernel changes.
 #include <math.h>
 
-#include "adi_cart_host.hpp"
+#include "adi_brick_dev.hpp"
 
 namespace adi {
 
@@ -19,59 +17,6 @@ struct PhaseLaw {
     double cp, L, Ts, Tl;
     double dT, Hs, Hl, cm;
 };
-
-constexpr int kPhaseIter = 8;     // row groups of a brick per thread: 256 rows / (256 threads / 8 lanes per row)
-
-struct PhaseCell {
-    long p;          // offset of the pair's first cell
-    unsigned in;     // bit c: cell c of the pair lies inside the box
-    unsigned m;      // bit c: ... and in the mask
-};
-
-// 16-byte access needs even row and plane strides and 16-byte aligned arrays (host: `vec`); then a pair never straddles the
-// end of a row.  Otherwise cell by cell.
-template <bool VEC>
-__device__ __forceinline__ void load_pair(const double *__restrict__ a, const PhaseCell &c, double &v0, double &v1)
-{
-    if (VEC) {
-        const double2 v = *reinterpret_cast<const double2 *>(a + c.p);
-        v0 = v.x; v1 = v.y;
-    } else {
-        v0 = a[c.p];
-        v1 = (c.in & 2u) ? a[c.p + 1] : 0.0;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ unsigned load_mask_pair(const uint8_t *__restrict__ flags, const PhaseCell &c)
-{
-    if (VEC) {
-        const unsigned v = *reinterpret_cast<const unsigned short *>(flags + c.p);
-        return (v & 1u) | ((v >> 7) & 2u);
-    }
-    unsigned m = flags[c.p] & 1u;
-    if (c.in & 2u) m |= (flags[c.p + 1] & 1u) << 1;
-    return m;
-}
-
-// the pair of cells thread `tid` owns in row group `it` of brick (bi, bj, bk)
-__device__ __forceinline__ PhaseCell phase_cell(const Lay &L, int bi, int bj, int bk, int it, unsigned tid)
-{
-    const int row = it * 32 + (int)(tid >> 3);
-    const int i = bi * kBrick + (row >> 4), j = bj * kBrick + (row & 15), k = bk * kBrick + 2 * (int)(tid & 7u);
-    PhaseCell c;
-    c.p = (long)i * L.sx + (long)j * L.nz + k;
-    c.in = (i < L.nx && j < L.ny && k < L.nz) ? ((k + 1 < L.nz) ? 3u : 1u) : 0u;
-    c.m = 0u;
-    return c;
-}
-
-__device__ __forceinline__ bool brick_all_solid(const unsigned *__restrict__ bricks, const Lay &L, int bi, int bj, int bk)
-{
-    if (bricks == nullptr) return false;
-    const int nbx = (L.nx + kBrick - 1) / kBrick, nbz = (L.nz + kBrick - 1) / kBrick;
-    return (bricks[brick_word(bi * kBrick, bj * kBrick, bk * kBrick, nbz, (nbx + 31) >> 5)] & brick_bit(bi * kBrick)) != 0u;
-}
 
 __device__ __forceinline__ double clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
 
@@ -199,29 +144,6 @@ static int make_phase_law(const char *who, const adi_phase_change &s, double cp,
     w->cm = cp + r;
     ADI_REQUIRE(isfinite(w->dT) && isfinite(w->Hl) && isfinite(w->cm), "%s: the law overflows fp64", who);
     return ADI_OK;
-}
-
-struct PhaseLaunch {
-    Lay L;
-    dim3 grid;
-    int nby, nbz;
-};
-
-static int make_phase_launch(const char *who, int nx, int ny, int nz, long plane_stride, PhaseLaunch *g)
-{
-    if (int rc = make_lay(nx, ny, nz, plane_stride, &g->L)) return rc;
-    const int nbx = (nx + kBrick - 1) / kBrick;
-    g->nby = (ny + kBrick - 1) / kBrick;
-    g->nbz = (nz + kBrick - 1) / kBrick;
-    ADI_REQUIRE(g->nby <= 65535 && nbx <= 65535, "%s: box of %d x %d x %d is too large", who, nx, ny, nz);
-    g->grid = dim3((unsigned)g->nbz, (unsigned)g->nby, (unsigned)nbx);
-    return ADI_OK;
-}
-
-// 16-byte loads of the fields and 2-byte loads of the flags: pairs start on even offsets of aligned arrays
-static bool phase_vec(const Lay &L, const void *a, const void *b, const void *flags)
-{
-    return L.nz % 2 == 0 && L.sx % 2 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && ((uintptr_t)flags & 1) == 0;
 }
 
 }  // namespace adi

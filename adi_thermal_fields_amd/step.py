@@ -11,7 +11,7 @@ from .fields import DeviceField, _as_state, _wrap, _p, _stream
 from .packs import _fc_arg
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .surface_loss import LossPacks
-from .phase import PhaseField
+from .phase import PhaseField, NonlinearPacks
 from .history import ThermalHistory
 
 
@@ -128,9 +128,26 @@ def _ensure_general(pack):
         pack.d_qflux = L.empty(zero=True)
 
 
-def _check_extras(grid, mat, packs, source, surface_loss, phase, history):
+def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material=None):
     """TypeError / ValueError for an optional argument of the step that is of the wrong kind or was made for other packs, another
     grid or another cp: once per adi_step_hip_coeff call and once per StagedStepper, before anything is launched"""
+    if material is not None:
+        if not isinstance(material, NonlinearPacks):
+            raise TypeError("material must be a NonlinearPacks")
+        if material.grid is not grid:
+            raise ValueError("material: the NonlinearPacks belongs to another grid")
+        if len(packs) != 3 or any(p is not q for p, q in zip(packs, material.packs)):
+            raise ValueError("material: the step must be given the NonlinearPacks' own packs (material.packs)")
+        m = material.mat
+        if (float(mat.rho), float(mat.cp), float(mat.k)) != (m.rho, m.cp, m.k):
+            raise ValueError("material: the step must be given the NonlinearPacks' own material (material.mat): the linear step "
+                             "runs with (rho, cp_ref, k_ref)")
+        if phase is not None or surface_loss is not None:
+            raise ValueError("material: phase= / surface_loss= cannot be combined with it; the MaterialLaw carries the latent "
+                             "heat and the NonlinearPacks the surface loss")
+        if params.theta < material.law.min_theta():
+            raise ValueError("material: theta = %r is below the law's stability limit cp_ref / (2 min c_eff) = %r"
+                             % (params.theta, material.law.min_theta()))
     if source is not None and not isinstance(source, GoldakSource):
         raise TypeError("source must be a GoldakSource (pass a source field, e.g. ScanPath.sample_step, to "
                         "adi_step_numba_coeff)")
@@ -158,10 +175,12 @@ def _no_mark():
 
 
 def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, source=None, owner=None, t_set=None,
-                 surface_loss=None, phase=None, history=None, captured=False, mark=_no_mark):
+                 surface_loss=None, phase=None, history=None, captured=False, mark=_no_mark, material=None):
     """THE launch sequence of one step t_in -> out (fp64 tensors in the grid's layout; nothing is allocated): the surface-loss
     update from t_in, the explicit stage and sweep 0 (one launch when `fused`), the moving source's correction of sweep 0's
-    output, sweeps 1 and 2, the latent-heat correction of `out`, the history record.  Every form of the step calls it --
+    output, sweeps 1 and 2, the latent-heat correction of `out`, the history record.  With `material` (a NonlinearPacks): its
+    `begin(t_in)` first, the launches above on its Kirchhoff field with Theta(Tinf) as the ambient, its `recover(t_in, out)`
+    after sweep 2, and the history on (t_in, out) as ever.  Every form of the step calls it --
     adi_step_hip_coeff with or without a source field, StagedStepper.step, and what StagedStepper.run captures -- with
     arguments that _check_extras has passed.
     d_S: a source FIELD in the grid's layout; the explicit stage takes it (adi_explicit_rhs_src), never fused.
@@ -172,18 +191,21 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
     mark: called at the stage boundaries of per-stage timing: before the explicit stage, between it and sweep 0 when they are
     two launches, after sweep 0 with the source's correction, after sweep 1 and after sweep 2."""
     (ta, tb), _, _ = grid.scratch(2)
+    u = t_in                                               # what the linear step runs on
+    if material is not None:
+        u, Tinf = material.begin(t_in), material.theta_inf
     if surface_loss is not None:
         surface_loss.update(t_in, Tinf)
     mark()
     if fused and d_S is None:
-        _explicit_sweep0_into(t_in, tb, grid, mat, params, packs[0], Tinf)
+        _explicit_sweep0_into(u, tb, grid, mat, params, packs[0], Tinf)
     else:
         if d_S is None:
             kappa, _ = _gam(grid, mat, params)
-            check(lib.adi_explicit_rhs(_p(t_in), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt,
+            check(lib.adi_explicit_rhs(_p(u), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt,
                                        kappa, params.theta, _p(ta), _stream()))
         else:
-            _explicit_src_into(t_in, d_S, ta, grid, mat, params)
+            _explicit_src_into(u, d_S, ta, grid, mat, params)
         mark()
         _sweep_into(0, ta, tb, grid, mat, params, packs[0], Tinf)
     if source is not None:
@@ -197,6 +219,8 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
     mark()
     _sweep_into(2, ta, out, grid, mat, params, packs[2], Tinf)
     mark()
+    if material is not None:
+        material.recover(t_in, out)
     if phase is not None:
         phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
     if history is not None:
@@ -206,7 +230,8 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
             history.record(t_in, out, params.dt)
 
 
-def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None, phase=None, history=None):
+def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None, phase=None, history=None,
+                       material=None):
     """adi3d_numba_coeff.py:290-302 / adi3d_gpu_coeff.py:213-230: explicit stage, then the three
     implicit sweeps in the order axis 0, 1, 2.  Returns a NEW array of the kind it was given;
     `Tn` is never modified.
@@ -226,12 +251,17 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     such launch.
     history: a ThermalHistory of the grid: the step Tn -> result (after the correction of `phase`) is recorded at the recorder's
     own clock, which moves on by dt (adi_history_record and adi_history_tick, the last launches).  None: no such launch.
+    material: a NonlinearPacks of the grid, with `packs` its `.packs` and `mat` its `.mat`: temperature-dependent k(T) and cp(T)
+    (and latent heat) by its MaterialLaw, surface loss by its SurfaceLoss.  The step runs on the Kirchhoff temperature and the
+    enthalpy is put back on its curve afterwards (adi_matlaw_theta first, adi_matlaw_recover after sweep 2); the
+    ambient is the NonlinearPacks' own, `Tinf` here is not used.  Combines with S= in either form and history=, not with phase=
+    or surface_loss=; params.theta must reach law.min_theta().  None: no such launch.
     Every optional argument is checked before the first launch (_check_extras); the launches are _launch_step's."""
     if isinstance(S, (ScanPath, ScanPathSource)):
         raise TypeError("adi_step_hip_coeff: a scan path enters the step as its field: S=path.sample_step(grid, t, dt) from the "
                         "host, or S=path.on_device().sample_step_device(grid, t, dt) evaluated on the device")
     source = S if isinstance(S, GoldakSource) else None
-    _check_extras(grid, mat, packs, source, surface_loss, phase, history)
+    _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material)
     if history is not None:
         history._check_mask()
     t_in, kind = _as_state(Tn, grid)
@@ -242,7 +272,7 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
         d_S = grid.layout.to_layout(S, torch.float64)
     out = grid.layout.empty()
     _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused_supported(grid), d_S=d_S, source=source, owner=grid, t_set=t,
-                 surface_loss=surface_loss, phase=phase, history=history)
+                 surface_loss=surface_loss, phase=phase, history=history, material=material)
     return _wrap(out, kind)
 
 
@@ -280,8 +310,8 @@ class StagedStepper:
     which stays the source's time origin) and moves that clock on by nsteps*dt."""
 
     def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None, surface_loss=None, phase=None,
-                 history=None):
-        _check_extras(grid, mat, packs, source, surface_loss, phase, history)
+                 history=None, material=None):
+        _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material)
         self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
         # temperature-dependent surface loss: the packs' Robin coefficients rewritten from the step's INPUT buffer, the first
         # launch of every step -- captured with it (X -> Y reads X, Y -> X reads Y); the law travels by value in that launch,
@@ -293,6 +323,10 @@ class StagedStepper:
         # thermal history: the record of the step input -> output and the tick of its block, the last launches of every step
         # -- captured with it; the levels travel by value and the five buffers by pointer, so all are part of run()'s graph key
         self.history = history
+        # k(T), cp(T): the Kirchhoff transform of the step's INPUT buffer (with the loss update, the first launches) and the
+        # recovery of its OUTPUT buffer after sweep 2 -- captured with it; the laws and the ambient travel by value, the
+        # Kirchhoff field by pointer, so all are part of run()'s graph key.  Stateless: the warm-up steps need no snapshot
+        self.material = material
         # moving source: corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step counter
         # a captured tick advances -- power, origin, velocity, eta and f_f may change between runs without a new graph
         self.source = source
@@ -316,7 +350,8 @@ class StagedStepper:
     def _step_into(self, t, out, captured=True, mark=_no_mark):
         """one step t -> out (both native-layout device tensors), no allocation: what a HIP graph captures"""
         _launch_step(t, out, self.grid, self.mat, self.params, self.packs, self.Tinf, self.fused, source=self.source, owner=self,
-                     surface_loss=self.surface_loss, phase=self.phase, history=self.history, captured=captured, mark=mark)
+                     surface_loss=self.surface_loss, phase=self.phase, history=self.history, captured=captured, mark=mark,
+                     material=self.material)
 
     def run(self, T, nsteps, graph=True, t0=0.0):
         """The drivers' `nsub` loop (quick_compare_dirichlet_robin.py:169-178, waam_from_stl_v7_mm.py:525-528): `nsteps`
@@ -335,12 +370,15 @@ class StagedStepper:
                None if self.source is None else self.source.shape_key(),
                None if self.surface_loss is None else self.surface_loss.loss.key(),
                None if self.phase is None else self.phase.graph_key(),
-               None if self.history is None else self.history.graph_key())
+               None if self.history is None else self.history.graph_key(),
+               None if self.material is None else self.material.graph_key())
         if self.history is not None:
             self.history._check_mask()
         st = getattr(self, '_graph', None)
         if st is None or st['key'] != key:
-            X, Y = g.layout.empty(), g.layout.empty()
+            # (zeroed where the box is padded, as Layout.to_layout does: the cells outside the logical grid are identity rows of
+            # the sweeps, and a NaN left there by whoever owned the memory before comes back in every cell of the result)
+            X, Y = g.layout._fresh(torch.float64), g.layout._fresh(torch.float64)
             st = self._graph = dict(key=key, X=X, Y=Y, g=None)
         X, Y = st['X'], st['Y']
         X.copy_(g.layout.to_layout(T, torch.float64))

@@ -102,14 +102,15 @@ def _is_device_backend(backend):
 
 def _require_device_loop(who, backend, dev_loop, **asked):
     """ValueError for an option (name = value) that is set where the loop cannot serve it"""
-    for name, cls in (('surface_loss', 'LossPacks'), ('phase_change', 'PhaseField'), ('history', 'ThermalHistory')):
-        if asked[name] is not None and not (dev_loop and hasattr(backend, cls)):
+    for name, cls in (('surface_loss', 'LossPacks'), ('phase_change', 'PhaseField'), ('history', 'ThermalHistory'),
+                      ('material_law', 'NonlinearPacks')):
+        if asked.get(name) is not None and not (dev_loop and hasattr(backend, cls)):
             raise ValueError("%s: %s needs the device loop of a backend with %s" % (who, name, cls))
 
 
-def _extras_kw(lpacks, ph, hist):
+def _extras_kw(lpacks, ph, hist, nm=None):
     """the keywords of a step / a stepper for the extras that are present"""
-    return {k: v for k, v in (('surface_loss', lpacks), ('phase', ph), ('history', hist)) if v is not None}
+    return {k: v for k, v in (('surface_loss', lpacks), ('phase', ph), ('history', hist), ('material', nm)) if v is not None}
 
 
 def _sync_extras(T, ph, hist):
@@ -261,7 +262,8 @@ def track_source(heat_source, track_box, dx, yi, t_step):
 
 
 def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_track, theta, dt, t_step,
-                     device_resident=True, heat_source=None, surface_loss=None, phase_change=None, history=None):
+                     device_resident=True, heat_source=None, surface_loss=None, phase_change=None, history=None,
+                     material_law=None):
     """single_track_on_plate.py:150-177: the deposit advances one column per t_step along axis 1; packs are
     rebuilt after every column.  track_box = (x0, x1, z0, z1, n_columns).
     heat_source (a GoldakSource of the backend): the arc / laser as a moving volumetric source (track_source) during the
@@ -276,8 +278,15 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     run, sized from the schedule, every sub-step is recorded at the global time (the recorder's clock; the source's time still
     counts from the start of each column), the cells of a new column are seeded at T_track; device loop only.  The return
     value gains a last element, the result dict of history_result.  None: the loop without it, unchanged.  With a recorder the
-    track box must not overlap the plate: T_track is written onto the whole box but only newborn cells are seeded (ValueError)."""
+    track box must not overlap the plate: T_track is written onto the whole box but only newborn cells are seeded (ValueError).
+    material_law (a MaterialLaw of the backend): temperature-dependent k(T) and cp(T), with the law's latent heat; one
+    NonlinearPacks lives through the run and is rebuilt after every column.  rho comes from mat_args, whose cp and k are not
+    used; the scalar `h` becomes SurfaceLoss(h=h) unless surface_loss is given; device loop only; not together with
+    phase_change (ValueError).  None: the loop without it, unchanged."""
     x0, x1, z0, z1, ncol = track_box
+    if material_law is not None and phase_change is not None:
+        raise ValueError("run_single_track: phase_change cannot be combined with material_law (the MaterialLaw carries the "
+                         "latent heat)")
     if history is not None and np.asarray(plate_mask)[x0:x1, :ncol, z0:z1].any():
         n = int(np.asarray(plate_mask)[x0:x1, :ncol, z0:z1].sum())
         raise ValueError("run_single_track: the track box [%d:%d, 0:%d, %d:%d] overlaps the plate in %d cells; T_track is written "
@@ -294,16 +303,21 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     robin = {f: h for f in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')}
     dev_loop = device_resident and hasattr(grid, 'set_mask_device') and hasattr(T, 'fill_where')
     _require_device_loop('run_single_track', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
-                         history=history)
+                         history=history, material_law=material_law)
     if dev_loop:                                    # the mask lives in HBM: a new column is two slice assignments
         import torch
         d_mask = grid.layout.to_layout(mask, torch.uint8)
-    lpacks = backend.LossPacks(grid, mat, surface_loss, Tinf) if surface_loss is not None else None
+    nm = None
+    if material_law is not None:
+        nm = backend.NonlinearPacks(grid, mat.rho, material_law, Tinf,
+                                    loss=surface_loss if surface_loss is not None else backend.SurfaceLoss(h=h))
+        mat = nm.mat
+    lpacks = backend.LossPacks(grid, mat, surface_loss, Tinf) if surface_loss is not None and nm is None else None
     ph = backend.PhaseField(grid, mat, phase_change, T=T) if phase_change is not None else None
     hist = None
     if history is not None:
         hist = backend.ThermalHistory(grid, history, capacity=ncol * max(1, int(math.ceil(t_step / dt))), T=T)
-    kw = _extras_kw(lpacks, ph, hist)
+    kw = _extras_kw(lpacks, ph, hist, nm)
     for yi in range(ncol):
         if dev_loop:
             d_mask[x0:x1, yi:yi + 1, z0:z1] = 1
@@ -311,11 +325,11 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         else:
             mask[x0:x1, yi:yi + 1, z0:z1] = True
             grid.mask = mask
-        if lpacks is None:
+        if lpacks is None and nm is None:
             packs = backend.precompute_coeff_packs_unified(grid, mat, robin_h=robin, robin_Tinf=Tinf)
         T[x0:x1, yi:yi + 1, z0:z1] = T_track
-        if lpacks is not None:
-            packs = lpacks.rebuild(T)                # the column changed the exposure: every cell, stale ones zeroed
+        if lpacks is not None or nm is not None:
+            packs = (nm or lpacks).rebuild(T)        # the column changed the exposure: every cell, stale ones zeroed
         _sync_extras(T, ph, hist)
         n_sub = max(1, int(math.ceil(t_step / dt)))
         dt_orig = params.dt

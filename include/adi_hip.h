@@ -745,6 +745,56 @@ int adi_phase_seed(const adi_phase_change *h_law, const double *d_T, double *d_f
                    long plane_stride, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Temperature-dependent conductivity and heat capacity of the Cartesian step (no counterpart in the reference, whose Material
+ * is three scalars; the two passes below run around its step, so the law is a sequence of calls the reference can run).
+ * k(T) and cp(T) are piecewise-linear in n_knots knots x[] and held at their end values outside; cp may jump at a knot (latent
+ * heat as a boost of cp between two knots).  Two exact changes of variable:
+ *     Kirchhoff temperature  Theta(T) = x[0] + (1/k_ref) int_{x[0]}^{T} k dT,   so div(k grad T) = k_ref lap(Theta)
+ *     enthalpy               H(T) = int cp dT [J/kg],  H = c_lo*T below the first knot
+ * and rho dH/dt = k_ref lap(Theta) + q is stepped as: theta = Theta(T_n) (adi_matlaw_theta); the linear step on theta with
+ * the constant material (rho, cp_ref, k_ref), ambient Theta(Tinf), Dirichlet values Theta(value), sources and Neumann fluxes
+ * unchanged (they are energy); then per cell H(T_new) = H(T_n) + cp_ref*(theta* - Theta(T_n)) (adi_matlaw_recover).  Lagged,
+ * first order in dt, stateless.  Stable exactly when cp_ref <= 2 theta_imp min(cp k_ref / k), theta_imp the step's implicitness.
+ * Tables (host constants, each one fp64 operation; piece m is anchored at x[m], the last piece has slope 0):
+ *     kq[m] = k(x[m])/k_ref          hks[m] = half the slope of k/k_ref on [x[m], x[m+1])        ks2[m] = twice that slope
+ *     c[m]  = cp just right of x[m]  hcs[m], cs2[m] likewise for cp                              c_lo = cp below x[0]
+ *     theta[0] = x[0], theta[m+1] = theta[m] + (kq[m] + hks[m]*d)*d with d = x[m+1] - x[m];  H[0] = c_lo*x[0], H[m+1] likewise
+ * On the piece that holds t (the last m with t >= x[m]; below x[0]: anchored at x[0] with values kq[0] / c_lo and slope 0):
+ *     V(t) = V[m] + (y[m] + hs[m]*e)*e,  e = t - x[m]
+ *     inverse (the last m with V >= V[m]):  dV = V - V[m];  t = x[m] + (dV + dV) / (y[m] + sqrt(y[m]*y[m] + s2[m]*dV))
+ * every operation IEEE fp64 in this order, no contraction.
+ * Valid: 2..ADI_MATLAW_MAX_KNOTS knots, finite values, x, theta and H strictly increasing, kq, c, c_lo, k_ref, cp_ref > 0, zero
+ * slopes on the last piece, radicands > 0 on every interval.  Everything else is ADI_ERR_ARG, checked before any HIP call.
+ * The law travels by value in every launch: a captured graph keeps the law it was captured with.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADI_MATLAW_MAX_KNOTS 16
+typedef struct adi_material_law {
+    int n_knots, reserved;
+    double k_ref, cp_ref, c_lo;
+    double x[ADI_MATLAW_MAX_KNOTS];
+    double kq[ADI_MATLAW_MAX_KNOTS], hks[ADI_MATLAW_MAX_KNOTS], ks2[ADI_MATLAW_MAX_KNOTS], theta[ADI_MATLAW_MAX_KNOTS];
+    double c[ADI_MATLAW_MAX_KNOTS], hcs[ADI_MATLAW_MAX_KNOTS], cs2[ADI_MATLAW_MAX_KNOTS], H[ADI_MATLAW_MAX_KNOTS];
+} adi_material_law;
+
+/* d_theta = Theta(d_T) on in-mask cells, d_T bit for bit on every other cell of the box (the sweeps pass off-mask cells
+ * through, so the step's result holds T there).  One workgroup per 16^3 brick; d_bricks (NULL: none) spares the flags of
+ * all-solid bricks. */
+int adi_matlaw_theta(const adi_material_law *h_law, const double *d_T, double *d_theta, const uint8_t *d_flags,
+                     const uint32_t *d_bricks, int nx, int ny, int nz, long plane_stride, void *stream);
+/* d_out holds theta* (the linear step's result) and is overwritten with T_new; d_T is T_n.  Off-mask cells are not written.
+ * Dirichlet cells (d_dir_mask non-zero; NULL: none): T_new = Theta^-1(theta*).  Every other in-mask cell:
+ *     d = theta* - Theta(T_n);   d == 0: T_new = T_n bit for bit;   else T_new = H^-1(H(T_n) + cp_ref*d) */
+int adi_matlaw_recover(const adi_material_law *h_law, const double *d_T, double *d_out, const uint8_t *d_flags,
+                       const uint32_t *d_bricks, const uint8_t *d_dir_mask, int nx, int ny, int nz, long plane_stride,
+                       void *stream);
+/* adi_surface_loss_update with every h_f multiplied, ahead of dx^2 / (rho cp dx^3), by
+ *     ratio = (T - Tinf) / (Theta(T) - Theta(Tinf)),   1 / (k(Tinf)/k_ref) where the denominator is 0
+ * so that the sweeps' sink coeff*(theta - Theta(Tinf)) is the loss h_f (T - Tinf).  cp: cp_ref.  Both modes of `full`. */
+int adi_matlaw_loss_update(const adi_material_law *h_mat, const adi_surface_loss *h_law, double Tinf, const double *d_T,
+                           const uint8_t *d_flags, const uint32_t *d_bricks, int nx, int ny, int nz, long plane_stride, double dx,
+                           double rho, double cp, double *const d_coeff[3], int k_begin, int k_end, int full, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Thermal history of the Cartesian step (no counterpart in the reference; the rules below are applied to the pair of fields
  * around one of its steps, so the recorder is a sequence of calls the reference can run).  State per cell (fp64, box layout,
  * NaN off the mask and where "never happened"): the peak temperature T_peak, and the times t_hi, t_lo of the last downward
