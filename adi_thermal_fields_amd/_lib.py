@@ -143,6 +143,10 @@ SIGNATURES = {
     'adi_cyl_plan_create_annular': (c_int, [c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double, c_double, c_double,
                                             c_double, c_double, c_double, c_double, c_int, c_int, c_double, c_double, c_double,
                                             c_double, c_double, c_double, c_void_pp]),
+    'adi_cyl_plan_tables': (c_int, [c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double,
+                                    c_double, c_double, c_double, c_double, c_int, c_int, c_double, c_double, c_double,
+                                    c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_long]),
     'adi_cyl_plan_destroy': (c_int, [c_void_p]),
     'adi_cyl_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_double, c_double, c_void_p]),
@@ -205,7 +209,10 @@ MIXED_MIN_TG = 1e-9           # kMixedMinTg (csrc/adi_core.hpp): below this thet
 MAX_BOX_CELLS = 1 << 32       # ADI_MAX_BOX_CELLS: nx * plane_stride of a Cartesian box stays below it
 SOURCE_BLOCK_BYTES = 128     # ADI_SOURCE_BLOCK_BYTES
 SOURCE_E_CUT = 40.0          # ADI_SOURCE_E_CUT
-SCAN_TABLE_COLS = 8          # ADI_SCAN_TABLE_COLS: { t_begin, p[3], d[2], speed, power }
+CYL_ZCLOSURE_LEN = 11        # ADI_CYL_ZCLOSURE_LEN: f b0 bN aN c0 add0 addN T0 TN dir0 dirN
+CYL_RF_MAXM = 16             # ADI_CYL_RF_MAXM
+CYL_RF_STRIDE = 83           # ADI_CYL_RF_STRIDE: doubles per segment of the r FAST tables
+SCAN_TABLE_COLS = 8         # ADI_SCAN_TABLE_COLS: { t_begin, p[3], d[2], speed, power }
 SURFACE_LOSS_MAX_KNOTS = 16  # ADI_SURFACE_LOSS_MAX_KNOTS
 SURFACE_LOSS_SIGMA = 5.670374419e-8   # ADI_SURFACE_LOSS_SIGMA (Stefan-Boltzmann, CODATA 2018)
 MATLAW_MAX_KNOTS = 16        # ADI_MATLAW_MAX_KNOTS

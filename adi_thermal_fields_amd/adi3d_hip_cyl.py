@@ -246,30 +246,25 @@ class StagedCylStepper:
         g = self.grid
         if self.source is not None:
             self.source.set_block(_source_block(self), t, self.dt)
-        t = g.layout.to_layout(T, torch.float64)
         out = g.layout.empty()
-        seq = ((0, t, out), (1, out, out), (2, out, out)) if g.nphi > 1 else ((0, t, out), (2, out, out))
+        self._sweeps(g.layout.to_layout(T, torch.float64), out, events)
+        return DeviceField(out)
+
+    def _sweeps(self, x, out, events):
+        """the launches of one step: the r sweep x -> out, then the phi and z sweeps in place on out (out may be x)"""
         if events is not None:
             events[0].record()
-        for ax, a, b in seq:
-            self._sweep(ax, a, b)
+        for ax in ((0, 1, 2) if self.grid.nphi > 1 else (0, 2)):
+            self._sweep(ax, x if ax == 0 else out, out)
             if events is not None:
                 events[ax + 1].record()
-                if ax == 0 and g.nphi == 1:
+                if ax == 0 and self.grid.nphi == 1:
                     events[2].record()         # no phi sweep (phi_solve_spectral copies, :319-320): an empty interval
-        return DeviceField(out)
 
     def _step_inplace(self, x, events=None):
         """one step on x in place (native-layout device tensor), no allocation: what a HIP graph captures.
         events: as in step()"""
-        if events is not None:
-            events[0].record()
-        for ax in ((0, 1, 2) if self.grid.nphi > 1 else (0, 2)):
-            self._sweep(ax, x, x)
-            if events is not None:
-                events[ax + 1].record()
-                if ax == 0 and self.grid.nphi == 1:
-                    events[2].record()
+        self._sweeps(x, x, events)
 
     def run(self, T, nsteps, graph=True, t0=0.0):
         """`nsteps` BE steps with the same plan on a device-resident field (the drivers' inner loops,

@@ -7,7 +7,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/adi_hip.h"
+#include "adi_goldak_dev.hpp"
 
 #if defined(__HIPCC__)
 #define ADI_SCAN_HD __host__ __device__ inline
@@ -17,7 +17,6 @@
 
 namespace adi {
 
-constexpr double kScanECut = ADI_SOURCE_E_CUT;
 constexpr double kScanDeltaMin = 1e-3;     // ScanPath.DELTA_MIN: travel of a piece over min(c_f, c_r) below which Simpson's rule
 constexpr int kScanCols = ADI_SCAN_TABLE_COLS;
 
@@ -56,8 +55,8 @@ ADI_SCAN_HD double scan_qi(const adi_scan_shape &h, double P, double xi, double 
     const bool front = xi >= 0.0;
     const double f = front ? h.f_f : 2.0 - h.f_f;
     const double cl = front ? h.c_f : h.c_r;
-    const double amp = (6.0 * sqrt(3.0) * f * h.eta * P) / (h.a * h.b * cl * pow(M_PI, 1.5));
-    const double E = 3.0 * (xi * xi) / (cl * cl) + Et;
+    const double amp = goldak_amp(f, h.eta, P, h.a, h.b, cl);
+    const double E = goldak_eterm(xi, cl) + Et;
     return amp * exp(-E);
 }
 
@@ -74,9 +73,9 @@ ADI_SCAN_HD double scan_qbar(const adi_scan_shape &h, const double *s, double ta
     const double y = ov * d0 - ou * d1;
     const double xia = xi0 - vel * ta;
     const double xib = xi0 - vel * tb;
-    const double Et = 3.0 * (y * y) / (h.a * h.a) + 3.0 * (z * z) / (h.b * h.b);
-    const double R = sqrt(kScanECut / 3.0);
-    if (!(Et <= kScanECut && xib <= R * h.c_f && xia >= -(R * h.c_r))) return 0.0;
+    const double Et = goldak_eterm(y, h.a) + goldak_eterm(z, h.b);
+    const double R = sqrt(ADI_SOURCE_E_CUT / 3.0);
+    if (!(Et <= ADI_SOURCE_E_CUT && xib <= R * h.c_f && xia >= -(R * h.c_r))) return 0.0;
     const double travel = vel * w;
     const double delta = travel / (h.c_f < h.c_r ? h.c_f : h.c_r);
     if (delta >= kScanDeltaMin) {
@@ -149,7 +148,7 @@ ADI_SCAN_HD void scan_box_join(const adi_scan_shape &h, const double *s, double 
                                ScanBox &B)
 {
 #pragma clang fp contract(off)
-    const double R = sqrt(kScanECut / 3.0);
+    const double R = sqrt(ADI_SOURCE_E_CUT / 3.0);
     const int da = h.depth_axis, au = scan_axis_u(da), av = scan_axis_v(da);
     const double cm = h.c_f > h.c_r ? h.c_f : h.c_r;
     for (int ax = 0; ax < 3; ++ax) {

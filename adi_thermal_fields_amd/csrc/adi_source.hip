@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "adi_cart_host.hpp"
+#include "adi_goldak_dev.hpp"
 
 namespace adi {
 
@@ -24,8 +25,6 @@ struct SrcBlock {
     unsigned long long n;
 };
 static_assert(sizeof(SrcBlock) == ADI_SOURCE_BLOCK_BYTES, "source block layout");
-
-constexpr double kECut = ADI_SOURCE_E_CUT;
 
 // centre of the source at time t (metres)
 __host__ __device__ inline void src_centre(const adi_heat_source &s, double t, double (&c)[3])
@@ -38,17 +37,11 @@ __host__ __device__ inline void src_centre(const adi_heat_source &s, double t, d
 
 __host__ __device__ inline double pick3(double v0, double v1, double v2, int a) { return a == 0 ? v0 : (a == 1 ? v1 : v2); }
 
-// exponent term of one axis for offset o: 3 o^2 / L^2 with L the half-length of that axis (role- and side-dependent)
+// the half-length L of an axis for offset o (role- and side-dependent), for the exponent term goldak_eterm(o, L)
 __host__ __device__ inline double src_len(const adi_heat_source &s, int axis, double o)
 {
     if (axis == s.travel_axis) return ((double)s.travel_sign * o >= 0.0) ? s.c_f : s.c_r;
     return axis == s.depth_axis ? s.b : s.a;
-}
-
-__host__ __device__ inline double src_eterm(double o, double len)
-{
-#pragma clang fp contract(off)
-    return 3.0 * (o * o) / (len * len);
 }
 
 // q [W/m^3] at the point (x0, x1, x2) for centre c.  Exponent summed in the order travel, transverse, depth (the NumPy
@@ -62,16 +55,15 @@ __host__ __device__ inline double goldak_q(const adi_heat_source &s, const doubl
     const bool front = (double)s.travel_sign * xi >= 0.0;
     const double f = front ? s.f_f : 2.0 - s.f_f;
     const double cl = front ? s.c_f : s.c_r;
-    const double E = (src_eterm(xi, cl) + src_eterm(y, s.a)) + src_eterm(z, s.b);
-    if (!(E <= kECut)) return 0.0;
-    const double amp = (6.0 * sqrt(3.0) * f * s.eta * s.power) / (s.a * s.b * cl * pow(M_PI, 1.5));
-    return amp * exp(-E);
+    const double E = (goldak_eterm(xi, cl) + goldak_eterm(y, s.a)) + goldak_eterm(z, s.b);
+    if (!(E <= ADI_SOURCE_E_CUT)) return 0.0;
+    return goldak_amp(f, s.eta, s.power, s.a, s.b, cl) * exp(-E);
 }
 
 // half-extents of the support along `axis` below / above the centre
 __host__ __device__ inline void src_extent(const adi_heat_source &s, int axis, double &lo, double &hi)
 {
-    const double R = sqrt(kECut / 3.0);
+    const double R = sqrt(ADI_SOURCE_E_CUT / 3.0);
     if (axis == s.travel_axis) {
         const double fr = R * s.c_f, re = R * s.c_r;
         lo = s.travel_sign > 0 ? re : fr;
@@ -98,14 +90,8 @@ __device__ inline int src_box_first(const adi_heat_source &s, const double (&c)[
     return first > -2 ? first : -2;
 }
 
-// t_n + dt/2 from the block: t_n = t0 + n*dt, computed from the integer counter (no accumulation, no fused multiply-add:
-// the host's t0 + i*dt gives the same double)
-__device__ inline double src_tmid(const SrcBlock &B)
-{
-#pragma clang fp contract(off)
-    const double tn = B.t0 + (double)B.n * B.dt;
-    return tn + 0.5 * B.dt;
-}
+// t_n + dt/2 from the block
+__device__ inline double src_tmid(const SrcBlock &B) { return goldak_tmid(B.t0, B.dt, B.n); }
 
 __global__ __launch_bounds__(256) void k_source_sample(adi_heat_source s, const uint8_t *__restrict__ flags, Lay L,
                                                        double dx, double t, double *__restrict__ out)
@@ -180,9 +166,9 @@ __device__ inline bool lines0_line(const SrcBlock &B, const Lay &L, const LinesA
     k = src_box_first(s, c, 2, A.dx) + kb;
     if (!(j >= 0 && j < L.ny && k >= 0 && k < L.nz && jb < A.nj && kb < A.nk)) return false;
     const double yj = (j + 0.5) * A.dx, zk = (k + 0.5) * A.dx;
-    const double e1 = src_eterm(yj - c[1], src_len(s, 1, yj - c[1]));
-    const double e2 = src_eterm(zk - c[2], src_len(s, 2, zk - c[2]));
-    return (e1 + e2) <= kECut;
+    const double e1 = goldak_eterm(yj - c[1], src_len(s, 1, yj - c[1]));
+    const double e2 = goldak_eterm(zk - c[2], src_len(s, 2, zk - c[2]));
+    return (e1 + e2) <= ADI_SOURCE_E_CUT;
 }
 
 // Row i of A0 w = s on the line at `base` = j*nz + k, assembled as adi_sweep(axis 0) assembles it (assemble_row): b the

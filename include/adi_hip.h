@@ -533,6 +533,35 @@ int adi_cyl_plan_create_annular(int nr, int nphi, int nz, long plane_stride, dou
                                 double Tinf_bot, double Tinf_top, double T_bot, double T_top,
                                 adi_cyl_plan **out);
 int adi_cyl_plan_destroy(adi_cyl_plan *plan);
+/* The tables a plan holds, on the host: the scalar arguments of adi_cyl_plan_create_annular in the same order (without
+ * plane_stride and out), the same validation with the same error texts, the same builders -- what this writes is what plan
+ * creation uploads.  Host arithmetic only: no HIP call, no device needed.  Every output is a caller-provided host array and
+ * may be NULL (skipped):
+ *   a, b, c [nr], r_add_last [1]   the r operator and the Robin increment of the last row's right-hand side
+ *   phi_fac [nr], zt [nr*nphi], smden [nr]   f_i; the Sherman-Morrison vector A'^-1 u per radius and 1 / (1 + v.z), with
+ *        A' the tridiagonal (-f, b0, -f), b0 = 1 + 2f, whose first / last diagonal is 2 b0 / b0 + f^2/b0: the phi sweep
+ *        solves A' y = d and returns x = y - zt (y_0 + (f/b0) y_{n-1}) smden.  nphi <= 2: zt = 0, smden = 1.
+ *   zclosure [ADI_CYL_ZCLOSURE_LEN]   f, b0, bN, aN, c0, add0, addN, T0, TN, dir0, dirN: the interior row is (-f, 1+2f, -f),
+ *        row 0 (0, b0, c0) with add0 added to its right-hand side, row n-1 (aN, bN, 0) with addN; dir0 / dirN = 1: the
+ *        row's right-hand side is T0 / TN instead
+ *   fast [3]   r_M, r_nseg, phi_M: rows per thread and segments of the FAST r kernel, rows per thread of the FAST phi
+ *        kernel; 0 where the axis length has none
+ *   rfac [r_nseg * ADI_CYL_RF_STRIDE]   the tabulated factorisation of the r operator, per segment: four arrays of
+ *        ADI_CYL_RF_MAXM - 1 doubles (forward multipliers wf, backward multipliers wb, inverse pivots ip, the c of the
+ *        interior rows), ten scalars (ipl jpf aF cF aL cL a0 aS cS bS), then the PCR multipliers pk1[6], pk2[6] and the
+ *        inverse diagonal of the reduced separator system.  rfac_capacity: doubles available at rfac; too few is
+ *        ADI_ERR_ARG. */
+#define ADI_CYL_ZCLOSURE_LEN 11
+#define ADI_CYL_RF_MAXM 16
+#define ADI_CYL_RF_STRIDE 83
+int adi_cyl_plan_tables(int nr, int nphi, int nz, double dr, double dphi, double dz,
+                        double r_in, double rho, double cp, double k, double dt,
+                        double robin_h, double robin_Tinf,
+                        int kind_bot, int kind_top, double h_bot, double h_top,
+                        double Tinf_bot, double Tinf_top, double T_bot, double T_top,
+                        double *a, double *b, double *c, double *r_add_last,
+                        double *phi_fac, double *zt, double *smden, double *zclosure, int *fast,
+                        double *rfac, long rfac_capacity);
 /* adi_step (BE): T_in is not modified and must differ from T_out.  d_tmp_a / d_tmp_b are unused since ABI v13 (may be
  * NULL): the r sweep writes T_out and the phi and z sweeps run in place on it. */
 int adi_cyl_step(const adi_cyl_plan *plan, const double *d_T_in, double *d_T_out,

@@ -1,5 +1,5 @@
 """Cases of tests/test_cyl_switches_gpu.py and tests/test_cyl_ref_cpu.py: one deterministic cylindrical case per dispatch
-decision of csrc/adi_cyl.hip (adi_cyl_plan_create_annular, cyl_sweep_r / phi / z, strided_rows, contig_rows), and the
+decision of csrc/adi_cyl.hip (cyl_sweep_r / phi / z, strided_rows, contig_rows) and csrc/adi_cyl_plan.hpp (cyl_pick_fast), and the
 time-step sweep against the extended-precision reference tests/cyl_ref_ld.py.  Reference-free."""
 import functools
 import types

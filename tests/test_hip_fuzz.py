@@ -113,7 +113,7 @@ def test_random_case_device_resident_and_staged(seed):
 
 
 # ---- cylindrical BE step -------------------------------------------------------------------------------------------------
-# shapes on both sides of every condition of the FAST kernels (adi_cyl.hip: r -- nr >= 64 with a power-of-two count of at
+# shapes on both sides of every condition of the FAST kernels (cyl_pick_fast of adi_cyl_plan.hpp and cyl_sweep_r / phi / z of adi_cyl.hip: r -- nr >= 64 with a power-of-two count of at
 # most 16 segments of 8 or 16 rows, and the (phi, z) plane a multiple of 64 lines; phi -- nphi >= 64 with a power-of-two count
 # of at most 32 segments of 8 (16 from nphi = 128) rows, and nz a multiple of 32; z -- no Dirichlet closure, nz >= 128 a multiple
 # of 16 with a power-of-two segment count, and nphi % (64 / (nz / 16)) == 0: a wave's lines lie in one radius plane), up to the
