@@ -90,6 +90,7 @@ SIGNATURES = {
     'adi_interface_solve': (c_int, [c_void_p, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p]),
     'adi_interface_pair': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     'adi_axis0_deferred_setup': (c_int, [c_int, c_double, c_double, c_double, c_void_p, c_double_p, c_int_p, c_void_p]),
+    'adi_axis0_weights_host': (c_int, [c_int, c_double, c_double, c_int, c_double, c_void_p, c_int_p]),
     'adi_interface_deferred': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_long, c_void_p, c_void_p, c_void_p]),
     'adi_deferred_exact_setup': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_double,
                                          c_long, c_void_p, c_void_p, c_void_p]),

@@ -16,7 +16,7 @@ struct PhaseCell {
 };
 
 // 16-byte access needs even row and plane strides and 16-byte aligned arrays (host: `vec`); then a pair never straddles the
-// end of a row.  Otherwise cell by cell.
+// end of a row (pair_vec, adi_cart_host.hpp).  Otherwise cell by cell.
 template <bool VEC>
 __device__ __forceinline__ void load_pair(const double *__restrict__ a, const PhaseCell &c, double &v0, double &v1)
 {
@@ -75,12 +75,6 @@ inline int make_phase_launch(const char *who, int nx, int ny, int nz, long plane
     ADI_REQUIRE(g->nby <= 65535 && nbx <= 65535, "%s: box of %d x %d x %d is too large", who, nx, ny, nz);
     g->grid = dim3((unsigned)g->nbz, (unsigned)g->nby, (unsigned)nbx);
     return ADI_OK;
-}
-
-// 16-byte loads of the fields and 2-byte loads of the flags: pairs start on even offsets of aligned arrays
-inline bool phase_vec(const Lay &L, const void *a, const void *b, const void *flags)
-{
-    return L.nz % 2 == 0 && L.sx % 2 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && ((uintptr_t)flags & 1) == 0;
 }
 
 }  // namespace adi

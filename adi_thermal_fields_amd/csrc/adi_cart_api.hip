@@ -1,6 +1,6 @@
 // adi_cart_api.hip -- the C-ABI entry points of the Cartesian step (include/adi_hip.h): argument checks, the choice of
 // kernel family per axis and line length, and adi_step = adi_step_numba_coeff (adi3d_numba_coeff.py:290-302).
-// The kernels live in adi_explicit.hip, adi_sweep_contig.hip, adi_sweep_strided.hip and adi_condense.hip.
+// The kernels live in adi_explicit.hip, adi_sweep_contig.hip, adi_sweep_strided.hip, adi_condense.hip and adi_interface.hip.
 #include "adi_cart_host.hpp"
 
 using namespace adi;

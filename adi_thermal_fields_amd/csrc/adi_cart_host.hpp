@@ -3,6 +3,8 @@
 // (adi_cart_api.hip).  The tiling constants are the measured optima of round 1; the run-time
 // tuning knobs they were swept with are gone.
 #pragma once
+#include <math.h>
+
 #include "adi_cart_dev.hpp"
 
 namespace adi {
@@ -213,6 +215,33 @@ inline bool condense_is_tiled(int axis, int n)
 }
 
 inline int dots_ichunk(int np) { return np >= 512 ? 32 : (np / 16 < 4 ? 4 : np / 16); }
+// chunks of partial sums of a line of n_line rows
+inline int dots_nchunk(int n_line) { return (n_line + dots_ichunk(n_line) - 1) / dots_ichunk(n_line); }
+
+// 16-byte accesses to the fields a, b, c (null: absent) and 2-byte accesses to the flags: pairs of cells start on even
+// offsets of aligned arrays.  The marching explicit kernel, the brick passes and the history kernels ask the same thing.
+inline bool pair_vec(const Lay &L, const void *flags, const void *a = nullptr, const void *b = nullptr, const void *c = nullptr)
+{
+    return L.nz % 2 == 0 && L.sx % 2 == 0 && ((uintptr_t)flags & 1) == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
+// planes [begin, end) of an axis of n planes (`who` names the entry in the error text)
+inline int check_plane_range(const char *who, int begin, int end, int n)
+{
+    ADI_REQUIRE(begin >= 0 && end <= n && begin <= end, "%s: bad plane range [%d, %d)", who, begin, end);
+    return ADI_OK;
+}
+
+// face area and heat capacity of a cell.  A = dx*dx, V = dx**3 (CPython float_pow -> libm pow), Ccell = rho*cp*V:
+// adi3d_numba_coeff.py:66-68.  The one definition behind (h * A) / Ccell of k_build_coeffs, adi_face_constants and
+// k_surface_loss, whose packs must agree bit for bit.
+inline void cell_constants(double dx, double rho, double cp, double *A, double *Ccell)
+{
+#pragma clang fp contract(off)
+    const double V = pow(dx, 3.0);
+    *A = dx * dx;
+    *Ccell = rho * cp * V;
+}
 
 // ---- launchers exported by the kernel translation units ----------------------------------------------------------
 // The arrays a variant does not read (has_dir / has_q false) may be null.
@@ -237,7 +266,5 @@ void generic_sweep(bool has_dir, bool has_q, const SweepArgs &a, const LineGeom 
 // adi_condense.hip: pass A of a sweep whose lines span several slabs
 int condense_sweep(bool has_dir, bool has_q, int axis, const SweepArgs &a, const Lay &L, const SweepScal &s, double *cond,
                    void *work, size_t work_bytes, hipStream_t st, const Fuse *fz);
-void condense_generic_lines(bool has_dir, bool has_q, const SweepArgs &a, const Lay &L, const SweepScal &s, double *cond,
-                            const unsigned *list, long line_begin, long nsel, hipStream_t st);
 
 }  // namespace adi

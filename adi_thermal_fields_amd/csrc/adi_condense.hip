@@ -1,9 +1,13 @@
 // adi_condense.hip -- K5: slab decomposition along memory axis 0 (BASELINE.json: "2/4/8-GPU runs exchange one ghost plane
-// per sweep").  Pass A of a sweep whose lines continue on neighbouring GPUs condenses every local line to six numbers;
-// k_interface / k_interface_pair solve the reduced interface system; pass B is the ordinary sweep with the two boundary
+// per sweep").  Pass A of a sweep whose lines continue on neighbouring GPUs condenses every local line to six numbers:
+//   k_condense_strided, k_condense_strided_fast   the tiled kernels (whole segments), GENERAL and FAST
+//   k_condense_generic                            one thread per line, any n; also the listed lines of the dot-product form
+//   k_classify_lines0, k_dots_finish              pass A from the dot products the marching explicit kernel accumulated
+//                                                 (adi_explicit_rhs_dots, adi_explicit.hip)
+// The interface kernels solve the reduced system (adi_interface.hip); pass B is the ordinary sweep with the two boundary
 // values injected (adi_sweep_strided.hip).  No counterpart in the reference (single process); the per-line algebra is
 // thomas_solve's (adi3d_numba_coeff.py:121-130) block elimination.
-#include <vector>
+#include <type_traits>
 
 #include "adi_cart_host.hpp"
 #include "adi_strided_dev.hpp"
@@ -248,153 +252,159 @@ __global__ __launch_bounds__(256) void k_condense_generic(
     cond[3 * ostr + oid] = gL; cond[4 * ostr + oid] = aL; cond[5 * ostr + oid] = cL;
 }
 
-// K5c: interface solve.  cond_all: [nranks][6][nlines] (all-gathered).  For this rank, merge the slabs below
-// and above it, solve the 2x2 system for its own first/last unknown and emit the neighbours' boundary
-// values: xlo = last unknown of the slab below, xhi = first unknown of the slab above.
-__global__ __launch_bounds__(256) void k_interface(const double *__restrict__ cond_all, int nranks, int rank,
-                                                   long nlines, double *__restrict__ xlo, double *__restrict__ xhi)
+// ---- pass A from the dot products (slab decomposition) -----------------------------------------------------------------
+// A line is "uniform" for the axis-0 sweep when its rows 1..n-2 are in the mask with both axis neighbours and are not
+// Dirichlet, its end rows are in the mask (not Dirichlet) with their inward neighbour, and at most one end row differs
+// from the interior row (line start/end, Robin coefficient).  cls[line] = 1 for those; the others are appended to
+// list[1..] (list[0] = count) and condensed by k_condense_generic from the stored R0.
+__global__ __launch_bounds__(256) void k_classify_lines0(const uint8_t *__restrict__ flags,
+                                                         const uint8_t *__restrict__ dmask, Lay L,
+                                                         uint8_t *__restrict__ cls, unsigned *__restrict__ list)
 {
-    const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= nlines) return;
-    auto ld = [&](int r) {
-        const double *q = cond_all + (long)r * 6 * nlines + id;
-        Cond k;
-        k.gF = q[0]; k.aF = q[nlines]; k.cF = q[2 * nlines]; k.gL = q[3 * nlines]; k.aL = q[4 * nlines];
-        k.cL = q[5 * nlines];
-        return k;
-    };
-    const Cond C = ld(rank);
-    Cond P = {0, 0, 0, 0, 0, 0}, S = {0, 0, 0, 0, 0, 0};   // empty neighbours: decoupled zeros
-    if (rank > 0) {
-        P = ld(0);
-        for (int r = 1; r < rank; ++r) P = merge_cond(P, ld(r));
+    const long nlines = (long)L.ny * L.nz;
+    const long lid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (lid >= nlines) return;
+    const int n = L.nx;
+    bool ok = n >= 2;
+    unsigned f0 = 0, fn = 0;
+    for (int r = 0; r < n; ++r) {
+        const long p = (long)r * L.sx + lid;
+        const unsigned f = flags[p];
+        if (dmask != nullptr && dmask[p] != 0) ok = false;
+        if (r == 0) { f0 = f; ok = ok && ((f & 5u) == 5u); }                 // in mask, next row in mask
+        else if (r == n - 1) { fn = f; ok = ok && ((f & 3u) == 3u); }        // in mask, previous row in mask
+        else ok = ok && ((f & 7u) == 7u);
     }
-    if (rank < nranks - 1) {
-        S = ld(nranks - 1);
-        for (int r = nranks - 2; r > rank; --r) S = merge_cond(ld(r), S);
-    }
-    // unknowns f = x_first(C), l = x_last(C);  x_last(P) = P.gL - P.cL f ;  x_first(S) = S.gF - S.aF l
-    //   f = C.gF - C.aF (P.gL - P.cL f) - C.cF (S.gF - S.aF l)
-    //   l = C.gL - C.aL (P.gL - P.cL f) - C.cL (S.gF - S.aF l)
-    const double m00 = 1.0 - C.aF * P.cL, m01 = -C.cF * S.aF;
-    const double m10 = -C.aL * P.cL, m11 = 1.0 - C.cL * S.aF;
-    const double r0 = C.gF - C.aF * P.gL - C.cF * S.gF;
-    const double r1 = C.gL - C.aL * P.gL - C.cL * S.gF;
-    const double idet = 1.0 / (m00 * m11 - m01 * m10);
-    const double f = (r0 * m11 - m01 * r1) * idet;
-    const double l = (m00 * r1 - m10 * r0) * idet;
-    xlo[id] = P.gL - P.cL * f;
-    xhi[id] = S.gF - S.aF * l;
+    // an end row without its outward neighbour is a modified row (b = 1 + tg + dt*coeff): at most one per line
+    if (ok && !(f0 & 2u) && !(fn & 4u)) ok = false;
+    cls[lid] = ok ? 1 : 0;
+    if (!ok) list[1 + atomicAdd(&list[0], 1u)] = (unsigned)lid;
 }
 
-// The same solve for the deferred form without decay: only the right-hand sides (gF, gL) = (plane 0, plane n-1 of x0) are
-// gathered every step, g_all [nranks][2][nlines]; the matrix entries are constants of the plan -- per line on the first and
-// the last rank (their global end rows: mat_all [nranks][4][nlines] = aF, cF, aL, cL, gathered once), the same two numbers
-// (-w0, -wn) for every line of a middle rank (scal_all [nranks][2]).  A third of the per-step payload and of this kernel's reads.
-__global__ __launch_bounds__(256) void k_interface_uniform(const double *__restrict__ g_all, const double *__restrict__ mat_all,
-                                                           const double *__restrict__ scal_all, int nranks, int rank,
-                                                           long nlines, double *__restrict__ xlo, double *__restrict__ xhi)
+// cond[6][nsel] of the lines [lb, le) from the partial dot products (uniform lines only; the others keep what
+// k_condense_generic wrote).  Formulas: condense_uniform (adi_core.hpp) applied to the whole line.
+template <bool HAS_Q>
+__global__ __launch_bounds__(256) void k_dots_finish(const double *__restrict__ part, int nchunk,
+                                                     const double *__restrict__ wu, const uint8_t *__restrict__ cls,
+                                                     const uint8_t *__restrict__ flags, const double *__restrict__ coeff,
+                                                     const double *__restrict__ qf, Lay L, SweepScal s, long lb, long le,
+                                                     double *__restrict__ cond)
 {
+    const long nlines = (long)L.ny * L.nz, nsel = le - lb;
     const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= nlines) return;
-    auto ld = [&](int r) {
-        const double *g = g_all + (long)r * 2 * nlines + id;
-        Cond k;
-        k.gF = g[0]; k.gL = g[nlines];
-        if (r == 0 || r == nranks - 1) {
-            const double *m = mat_all + (long)r * 4 * nlines + id;
-            k.aF = m[0]; k.cF = m[nlines]; k.aL = m[2 * nlines]; k.cL = m[3 * nlines];
-        } else {
-            const double w0 = scal_all[2 * r], wn = scal_all[2 * r + 1];
-            k.aF = -w0; k.cF = -wn; k.aL = -wn; k.cL = -w0;
-        }
-        return k;
-    };
-    const Cond C = ld(rank);
-    Cond P = {0, 0, 0, 0, 0, 0}, S = {0, 0, 0, 0, 0, 0};
-    if (rank > 0) {
-        P = ld(0);
-        for (int r = 1; r < rank; ++r) P = merge_cond(P, ld(r));
+    if (id >= nsel) return;
+    const long lid = lb + id;
+    if (!cls[lid]) return;
+    const int n = L.nx;
+    double gu = 0.0, gv = 0.0;
+    for (int c = 0; c < nchunk; ++c) {                      // fixed order: deterministic
+        gu += part[(long)c * 2 * nlines + lid];
+        gv += part[((long)c * 2 + 1) * nlines + lid];
     }
-    if (rank < nranks - 1) {
-        S = ld(nranks - 1);
-        for (int r = nranks - 2; r > rank; --r) S = merge_cond(ld(r), S);
+    const long pF = lid, pL = (long)(n - 1) * L.sx + lid;
+    const unsigned fF = flags[pF], fL = flags[pL];
+    const bool loF = (fF & 2u) != 0, hiL = (fL & 4u) != 0;   // the line continues below / above the slab
+    const double p0 = wu[0], pn = wu[n - 1];
+    const double bu = 1.0 + 2.0 * s.tg;
+    // right-hand side terms of the end rows beyond R0 (assemble_row): dt*q + dt*coeff*Tinf on axis-exposed cells
+    const double coF = loF ? 0.0 : coeff[pF], coL = hiL ? 0.0 : coeff[pL];
+    double xF = s.dt * coF * s.Tinf, xL = s.dt * coL * s.Tinf;
+    if (HAS_Q) { if (!loF) xF += s.dt * qf[pF]; if (!hiL) xL += s.dt * qf[pL]; }
+    gu += p0 * xF + pn * xL;                                 // (U^-1 d)_0
+    gv += pn * xF + p0 * xL;                                 // (U^-1 d)_{n-1}
+    const double a0 = loF ? -s.tg : 0.0, cn = hiL ? -s.tg : 0.0;
+    double gF, aF, cF, gL, aL, cL;
+    if (!loF) {            // row 0 modified: b0 = 1 + tg + dt*coF
+        const double delta = (1.0 + s.tg + s.dt * coF) - bu;
+        const double kappa = delta / (1.0 + delta * p0);
+        const double f1 = 1.0 - kappa * p0, kpl = kappa * pn;
+        gF = gu * f1;            gL = gv - kpl * gu;
+        aF = 0.0;                aL = 0.0;
+        cF = cn * (pn - kpl * p0); cL = cn * (p0 - kpl * pn);
+    } else if (!hiL) {     // row n-1 modified
+        const double delta = (1.0 + s.tg + s.dt * coL) - bu;
+        const double kappa = delta / (1.0 + delta * p0);
+        const double f1 = 1.0 - kappa * p0, kpl = kappa * pn;
+        gL = gv * f1;            gF = gu - kpl * gv;
+        cL = 0.0;                cF = 0.0;
+        aL = a0 * (pn - kpl * p0); aF = a0 * (p0 - kpl * pn);
+    } else {
+        gF = gu; gL = gv;
+        aF = a0 * p0; cF = cn * pn; aL = a0 * pn; cL = cn * p0;
     }
-    const double m00 = 1.0 - C.aF * P.cL, m01 = -C.cF * S.aF;      // (as in k_interface)
-    const double m10 = -C.aL * P.cL, m11 = 1.0 - C.cL * S.aF;
-    const double r0 = C.gF - C.aF * P.gL - C.cF * S.gF;
-    const double r1 = C.gL - C.aL * P.gL - C.cL * S.gF;
-    const double idet = 1.0 / (m00 * m11 - m01 * m10);
-    const double f = (r0 * m11 - m01 * r1) * idet;
-    const double l = (m00 * r1 - m10 * r0) * idet;
-    xlo[id] = P.gL - P.cL * f;
-    xhi[id] = S.gF - S.aF * l;
+    cond[id] = gF; cond[nsel + id] = aF; cond[2 * nsel + id] = cF;
+    cond[3 * nsel + id] = gL; cond[4 * nsel + id] = aL; cond[5 * nsel + id] = cL;
 }
-
-// Neighbour-only form of the interface system, valid when the far-side couplings of the boundary windows
-// (aL of the window that ends a slab, cF of the window that starts one) have decayed below rounding:
-//   x_last(r)    = gL  - cL  * x_first(r+1)        (window = last rows of slab r)
-//   x_first(r+1) = gF' - aF' * x_last(r)           (window = first rows of slab r+1)
-// my_lo / my_hi: [6][nlines] condensations of this slab's first / last window; prev_hi: rows (gL,aL,cL) of the
-// slab below; next_lo: rows (gF,aF) of the slab above.  NULL neighbour -> 0.
-__global__ __launch_bounds__(256) void k_interface_pair(const double *__restrict__ my_lo, const double *__restrict__ my_hi,
-                                                        const double *__restrict__ prev_hi, const double *__restrict__ next_lo,
-                                                        long nlines, double *__restrict__ xlo, double *__restrict__ xhi)
-{
-    const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= nlines) return;
-    double lo = 0.0, hi = 0.0;
-    if (prev_hi) {
-        const double gLp = prev_hi[id], cLp = prev_hi[2 * nlines + id];
-        const double gF = my_lo[id], aF = my_lo[nlines + id];
-        lo = (gLp - cLp * gF) / (1.0 - cLp * aF);
-    }
-    if (next_lo) {
-        const double gFn = next_lo[id], aFn = next_lo[nlines + id];
-        const double gL = my_hi[3 * nlines + id], cL = my_hi[5 * nlines + id];
-        hi = (gFn - aFn * gL) / (1.0 - aFn * cL);
-    }
-    xlo[id] = lo;
-    xhi[id] = hi;
-}
-
 
 // ------------------------------------------------------------------------------------------------
 // host-side launch logic
 // ------------------------------------------------------------------------------------------------
+// The four builds of a pass-A body, chosen in one place: fn(HAS_DIR, HAS_Q as std::bool_constant, the arrays) with the arrays
+// the build does not read set to null.
+template <class F>
+static int by_variant(bool has_dir, bool has_q, SweepArgs a, F fn)
+{
+    if (!has_dir) { a.dmask = nullptr; a.dval = nullptr; }
+    if (!has_q) a.qf = nullptr;
+    if (has_dir && has_q) return fn(std::true_type(), std::true_type(), a);
+    if (has_q) return fn(std::false_type(), std::true_type(), a);
+    if (has_dir) return fn(std::true_type(), std::false_type(), a);
+    return fn(std::false_type(), std::false_type(), a);
+}
+
 template <int MF, bool HAS_DIR, bool HAS_Q, bool FUSE>
-static void launch_condense_fast(const StridedPlan &P, const double *in, const uint8_t *flags, const double *coeff,
-                                 const uint8_t *dmask, const double *dval, const double *qf, double *cond, long nlines,
-                                 const LineGeom &g, SweepScal s, unsigned *queue, hipStream_t st, const Fuse &fz)
+static void launch_condense_fast(const StridedPlan &P, const SweepArgs &a, double *cond, long nlines, const LineGeom &g,
+                                 SweepScal s, unsigned *queue, hipStream_t st, const Fuse &fz)
 {
     hipLaunchKernelGGL((k_condense_strided_fast<MF, HAS_DIR, HAS_Q, FUSE>), dim3((unsigned)P.ntiles_f),
-                       dim3(P.lines_f * P.Lpf), P.lds_f, st, in, flags, coeff, dmask, dval, qf, cond, nlines, g, P.Lpf,
-                       P.lines_f, P.tiles_inner_f, P.ntiles_f, s, queue, make_unic<MF>(s.tg), fz);
+                       dim3(P.lines_f * P.Lpf), P.lds_f, st, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, cond, nlines, g,
+                       P.Lpf, P.lines_f, P.tiles_inner_f, P.ntiles_f, s, queue, make_unic<MF>(s.tg), fz);
 }
 
 template <int M, bool HAS_DIR, bool HAS_Q, bool FUSE>
-static void launch_condense(const StridedPlan &P, const double *in, const uint8_t *flags, const double *coeff,
-                            const uint8_t *dmask, const double *dval, const double *qf, double *cond, long nlines,
-                            const LineGeom &g, SweepScal s, unsigned *queue, hipStream_t st, const Fuse &fz)
+static void launch_condense(const StridedPlan &P, const SweepArgs &a, double *cond, long nlines, const LineGeom &g,
+                            SweepScal s, unsigned *queue, hipStream_t st, const Fuse &fz)
 {
     unsigned ggrid = (unsigned)P.ntiles_g;
     if (queue != nullptr) {
         (void)hipMemsetAsync(queue, 0, sizeof(unsigned), st);
         // (the 32-row wide tiling is not built with the fused loader: the host plans fused passes without it)
-        if (P.Mf == 32) launch_condense_fast<32, HAS_DIR, HAS_Q, false>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz);
-        else if (P.Mf == 16) launch_condense_fast<16, HAS_DIR, HAS_Q, FUSE>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz);
-        else launch_condense_fast<8, HAS_DIR, HAS_Q, FUSE>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz);
+        if (P.Mf == 32) launch_condense_fast<32, HAS_DIR, HAS_Q, false>(P, a, cond, nlines, g, s, queue, st, fz);
+        else if (P.Mf == 16) launch_condense_fast<16, HAS_DIR, HAS_Q, FUSE>(P, a, cond, nlines, g, s, queue, st, fz);
+        else launch_condense_fast<8, HAS_DIR, HAS_Q, FUSE>(P, a, cond, nlines, g, s, queue, st, fz);
         ggrid = P.ntiles_g < 1024 ? (unsigned)P.ntiles_g : 1024u;
     }
     hipLaunchKernelGGL((k_condense_strided<M, HAS_DIR, HAS_Q, FUSE>), dim3(ggrid), dim3(P.lines_g * P.Lpg), P.lds_g, st,
-                       in, flags, coeff, dmask, dval, qf, cond, nlines, g, P.Lpg, P.lines_g, P.tiles_inner_g, P.ntiles_g,
-                       s, queue, P.ratio, P.tiles_inner_f, fz);
+                       a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, cond, nlines, g, P.Lpg, P.lines_g, P.tiles_inner_g,
+                       P.ntiles_g, s, queue, P.ratio, P.tiles_inner_f, fz);
+}
+
+// the tiled kernels by rows per thread of the GENERAL kernel
+template <bool HAS_DIR, bool HAS_Q, bool FUSE>
+static void launch_condense_rows(const StridedPlan &P, const SweepArgs &a, double *cond, long nlines, const LineGeom &g,
+                                 SweepScal s, unsigned *queue, hipStream_t st, const Fuse &fz)
+{
+    switch (P.Mg) {
+        case 2: launch_condense<2, HAS_DIR, HAS_Q, FUSE>(P, a, cond, nlines, g, s, queue, st, fz); break;
+        case 4: launch_condense<4, HAS_DIR, HAS_Q, FUSE>(P, a, cond, nlines, g, s, queue, st, fz); break;
+        case 8: launch_condense<8, HAS_DIR, HAS_Q, FUSE>(P, a, cond, nlines, g, s, queue, st, fz); break;
+        default: launch_condense<16, HAS_DIR, HAS_Q, FUSE>(P, a, cond, nlines, g, s, queue, st, fz); break;
+    }
+}
+
+// the serial two-recurrence condensation: of every line (list == nullptr), or of the lines in `list` that fall into
+// [lb, lb + nsel) (grid sized for all lines, the kernel returns beyond the list's count)
+template <bool HAS_DIR, bool HAS_Q>
+static void launch_condense_generic(const SweepArgs &a, double *cond, long nlines, const LineGeom &g, long inner_stride,
+                                    SweepScal s, const unsigned *list, long lb, long nsel, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_condense_generic<HAS_DIR, HAS_Q>), dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, st, a.in,
+                       a.flags, a.coeff, a.dmask, a.dval, a.qf, cond, nlines, g, inner_stride, s, list, lb, nsel);
 }
 
 template <bool HAS_DIR, bool HAS_Q>
-static int condense_dispatch(int axis, const double *in, const uint8_t *flags, const double *coeff,
-                             const uint8_t *dmask, const double *dval, const double *qf, const Lay &L, SweepScal s,
-                             double *cond, void *work, size_t work_bytes, hipStream_t st, const Fuse *fzp = nullptr)
+static int condense_dispatch(int axis, const SweepArgs &a, const Lay &L, SweepScal s, double *cond, void *work,
+                             size_t work_bytes, hipStream_t st, const Fuse *fzp)
 {
     long inner_stride;
     const LineGeom g = line_geom(axis, L, &inner_stride);
@@ -408,32 +418,20 @@ static int condense_dispatch(int axis, const double *in, const uint8_t *flags, c
     }
     if (fzp != nullptr && (axis != 0 || !tiled))
         return set_err(ADI_ERR_UNSUPPORTED, "fused explicit + condensation: axis 0, whole segments only (n = %d)", n);
-    if (tiled) {
-        unsigned *queue = nullptr;
-        if (P.Mf && use_fast(s, work, work_bytes, P.ntiles_f)) queue = (unsigned *)work;
-        else if (P.Mf) P = strided_plan(g, false, false);
-        if (fzp != nullptr) {
-            Fuse fz = *fzp;
-            if (queue != nullptr && !fuse_fast_ok(P, L, fz)) { queue = nullptr; P = strided_plan(g, false, false); }
-            fuse_tile_order(fz, P, L);
-            switch (P.Mg) {
-                case 2: launch_condense<2, HAS_DIR, HAS_Q, true>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz); break;
-                case 4: launch_condense<4, HAS_DIR, HAS_Q, true>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz); break;
-                case 8: launch_condense<8, HAS_DIR, HAS_Q, true>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz); break;
-                default: launch_condense<16, HAS_DIR, HAS_Q, true>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz); break;
-            }
-            return ADI_OK;
-        }
-        const Fuse fz = Fuse();
-        switch (P.Mg) {
-            case 2: launch_condense<2, HAS_DIR, HAS_Q, false>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz); break;
-            case 4: launch_condense<4, HAS_DIR, HAS_Q, false>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz); break;
-            case 8: launch_condense<8, HAS_DIR, HAS_Q, false>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz); break;
-            default: launch_condense<16, HAS_DIR, HAS_Q, false>(P, in, flags, coeff, dmask, dval, qf, cond, nlines, g, s, queue, st, fz); break;
-        }
+    if (!tiled) {
+        launch_condense_generic<HAS_DIR, HAS_Q>(a, cond, nlines, g, inner_stride, s, nullptr, 0, 0, st);
+        return ADI_OK;
+    }
+    unsigned *queue = nullptr;
+    if (P.Mf && use_fast(s, work, work_bytes, P.ntiles_f)) queue = (unsigned *)work;
+    else if (P.Mf) P = strided_plan(g, false, false);
+    if (fzp != nullptr) {
+        Fuse fz = *fzp;
+        if (queue != nullptr && !fuse_fast_ok(P, L, fz)) { queue = nullptr; P = strided_plan(g, false, false); }
+        fuse_tile_order(fz, P, L);
+        launch_condense_rows<HAS_DIR, HAS_Q, true>(P, a, cond, nlines, g, s, queue, st, fz);
     } else {
-        hipLaunchKernelGGL((k_condense_generic<HAS_DIR, HAS_Q>), dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0,
-                           st, in, flags, coeff, dmask, dval, qf, cond, nlines, g, inner_stride, s);
+        launch_condense_rows<HAS_DIR, HAS_Q, false>(P, a, cond, nlines, g, s, queue, st, Fuse());
     }
     return ADI_OK;
 }
@@ -441,167 +439,9 @@ static int condense_dispatch(int axis, const double *in, const uint8_t *flags, c
 int condense_sweep(bool has_dir, bool has_q, int axis, const SweepArgs &a, const Lay &L, const SweepScal &s, double *cond,
                    void *work, size_t work_bytes, hipStream_t st, const Fuse *fz)
 {
-    if (has_dir && has_q) return condense_dispatch<true, true>(axis, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, L, s, cond, work, work_bytes, st, fz);
-    if (has_q) return condense_dispatch<false, true>(axis, a.in, a.flags, a.coeff, nullptr, nullptr, a.qf, L, s, cond, work, work_bytes, st, fz);
-    if (has_dir) return condense_dispatch<true, false>(axis, a.in, a.flags, a.coeff, a.dmask, a.dval, nullptr, L, s, cond, work, work_bytes, st, fz);
-    return condense_dispatch<false, false>(axis, a.in, a.flags, a.coeff, nullptr, nullptr, nullptr, L, s, cond, work, work_bytes, st, fz);
-}
-
-// the serial two-recurrence condensation of the lines in `list` (axis 0; grid sized for all lines, the kernel returns
-// beyond the list's count)
-void condense_generic_lines(bool has_dir, bool has_q, const SweepArgs &a, const Lay &L, const SweepScal &s, double *cond,
-                            const unsigned *list, long line_begin, long nsel, hipStream_t st)
-{
-    long inner_stride;
-    const LineGeom g = line_geom(0, L, &inner_stride);
-    const long nlines = (long)L.ny * L.nz;
-    const dim3 gl((unsigned)((nlines + 255) / 256)), block(256);
-    if (has_dir && has_q) hipLaunchKernelGGL((k_condense_generic<true, true>), gl, block, 0, st, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, cond, nlines, g, inner_stride, s, list, line_begin, nsel);
-    else if (has_q) hipLaunchKernelGGL((k_condense_generic<false, true>), gl, block, 0, st, a.in, a.flags, a.coeff, nullptr, nullptr, a.qf, cond, nlines, g, inner_stride, s, list, line_begin, nsel);
-    else if (has_dir) hipLaunchKernelGGL((k_condense_generic<true, false>), gl, block, 0, st, a.in, a.flags, a.coeff, a.dmask, a.dval, nullptr, cond, nlines, g, inner_stride, s, list, line_begin, nsel);
-    else hipLaunchKernelGGL((k_condense_generic<false, false>), gl, block, 0, st, a.in, a.flags, a.coeff, nullptr, nullptr, nullptr, cond, nlines, g, inner_stride, s, list, line_begin, nsel);
-}
-
-// ------------------------------------------------------------------------------------------------
-// K5c: interface values of the DEFERRED form.  Every rank has solved its part of every sharded-axis line with zero
-// boundary values: x0.  By linearity the solution of the whole line is, inside the slab,
-//     x[i] = x0[i] + xlo * w[i] + xhi * w[n-1-i],     w = theta*gamma * tridiag(-tg, 1+2tg, -tg)^-1 e_0,
-// with xlo / xhi the unknowns adjacent to the slab on the neighbouring ranks.  Where w has decayed below rounding
-// across a slab (the caller checks it, as for adi_interface_pair) the interface system splits into one 2 x 2 system per
-// boundary: with L the last unknown of the slab below, F the first unknown of this slab and om = w[0],
-//     L = x0_last(below) + om * F,    F = x0_first(mine) + om * L.
-// first / last: planes 0 and n-1 of this rank's x0; prev_last / next_first: the adjacent planes of the neighbours' x0
-// (null: no neighbour).  ulo = L of the boundary below, uhi = F of the boundary above; 0 where there is no neighbour.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_interface_deferred(const double *__restrict__ first, const double *__restrict__ last,
-                                                            const double *__restrict__ prev_last,
-                                                            const double *__restrict__ next_first, double om, double idet,
-                                                            long nlines, double *__restrict__ ulo, double *__restrict__ uhi)
-{
-    const long l = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= nlines) return;
-    double lo = 0.0, hi = 0.0;
-    if (prev_last != nullptr) {
-        const double gL = prev_last[l];
-        const double F = __builtin_fma(om, gL, first[l]) * idet;
-        lo = __builtin_fma(om, F, gL);
-    }
-    if (next_first != nullptr) hi = __builtin_fma(om, last[l], next_first[l]) * idet;
-    ulo[l] = lo;
-    uhi[l] = hi;
-}
-
-// The same for lines that are NOT uniform (curved solids, voids, Dirichlet cells): every line has its own decaying
-// homogeneous solutions, computed once per plan by two ordinary axis-0 sweeps with zero right-hand sides and unit boundary
-// values.  om_*: their value in the plane next to the interface -- om_lo_own / om_hi_own of this rank's lines, om_hi_prev /
-// om_lo_next received from the neighbours at plan time.  Per line and boundary a 2 x 2 system, as above with two weights.
-__global__ __launch_bounds__(256) void k_interface_deferred_lines(
-    const double *__restrict__ first, const double *__restrict__ last, const double *__restrict__ prev_last,
-    const double *__restrict__ next_first, const double *__restrict__ om_lo_own, const double *__restrict__ om_hi_prev,
-    const double *__restrict__ om_hi_own, const double *__restrict__ om_lo_next, long nlines, double *__restrict__ ulo,
-    double *__restrict__ uhi, const uint8_t *__restrict__ uni_lo, const uint8_t *__restrict__ uni_hi,
-    double *__restrict__ ulo_uni, double *__restrict__ uhi_uni)
-{
-    const long l = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= nlines) return;
-    double lo = 0.0, hi = 0.0;
-    if (prev_last != nullptr) {
-        const double gL = prev_last[l], wl = om_lo_own[l], wh = om_hi_prev[l];
-        const double F = __builtin_fma(wl, gL, first[l]) / (1.0 - wl * wh);     // this rank's first unknown
-        lo = __builtin_fma(wh, F, gL);                                          // the neighbour's last one: what w_lo multiplies
-    }
-    if (next_first != nullptr) {
-        const double wh = om_hi_own[l], wl = om_lo_next[l];
-        hi = __builtin_fma(wl, last[l], next_first[l]) / (1.0 - wl * wh);       // the neighbour's first unknown
-    }
-    ulo[l] = lo;
-    uhi[l] = hi;
-    // the same values on the lines whose rows within reach of the interface are uniform (they take the scalar weights inside
-    // the axis-1 sweep); the others get their own weights from k_deferred_lines_apply, or none (lines outside the mask)
-    if (ulo_uni != nullptr) ulo_uni[l] = (uni_lo != nullptr && uni_lo[l] != 0) ? lo : 0.0;
-    if (uhi_uni != nullptr) uhi_uni[l] = (uni_hi != nullptr && uni_hi[l] != 0) ? hi : 0.0;
-}
-
-// x[i][cell[q]] += wc[r][q] * u[cell[q]]: the rank-one update of the flagged lines of one side of the slab (the lines that
-// cross a void, the surface or a Dirichlet cell within reach of the interface).  Thread = one flagged line, blockIdx.y strides
-// the K rows; consecutive q are mostly consecutive cells (runs along the contiguous axis), the compact weights are read
-// coalesced.  The same fma as corr_apply: a line gives the same bits whichever way its correction is applied.
-__global__ __launch_bounds__(256) void k_deferred_lines_apply(double *__restrict__ x, int nx, long sx, const int *__restrict__ cells,
-                                                              long nflag, const double *__restrict__ wc, int K,
-                                                              const double *__restrict__ u, int from_hi,
-                                                              const int *__restrict__ nrows)
-{
-    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nflag) return;
-    const long cell = cells[q];
-    const double uu = u[cell];
-    const int Kq = (nrows != nullptr && nrows[q] < K) ? nrows[q] : K;     // rows beyond carry exact zeros: not read
-    for (int r = blockIdx.y; r < Kq; r += gridDim.y) {
-        // a flagged line's weights are exact zeros beyond its first row outside the mask (identity rows cut the coupling): a
-        // line through a cavity 150 planes from the interface carries 150 weights, not K; x + 0 * u = x is skipped unread
-        const double w = wc[(long)r * nflag + q];
-        if (w != 0.0) {
-            const long i = from_hi ? (long)(nx - 1 - r) : (long)r;
-            double *p = x + i * sx + cell;
-            *p = __builtin_fma(w, uu, *p);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// K5d: the deferred form WITHOUT decay (thin slabs, strong scaling).  x = x0 + xlo * psi_lo + xhi * psi_hi still holds;
-// what changes is that (1) the interface system couples all ranks -- the all-gather + k_interface of the `exact` form, fed
-// with gF = x0_first, gL = x0_last (planes of x0) and the matrix entries below -- and (2) on the first / last rank the
-// homogeneous solutions feel the global end row, whose diagonal differs from the uniform one by delta = dt * coeff - tg
-// (a line start / end with its Robin coefficient).  Sherman-Morrison on the uniform matrix U (p0 = w0 / tg = (U^-1)_00,
-// pn = wn / tg = (U^-1)_0,n-1), kappa = delta / (1 + delta p0):
-//     first rank (row 0 modified):   psi_hi[i] = w[n-1-i] - kappa pn w[i]      (no psi_lo: nothing below)
-//     last rank (row n-1 modified):  psi_lo[i] = w[i] - kappa pn w[n-1-i]      (no psi_hi)
-// so the correction keeps the form  c_lo * w[i] + c_hi * w[n-1-i]  that adi_sweep_corrected applies, with per-line c_lo / c_hi.
-// k_deferred_exact_setup: once per plan -- matrix entries mat [4][nlines] = (aF, cF, aL, cL) of this rank and kappa * pn per
-// line and end (0 where the end row is an ordinary interior row).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_deferred_exact_setup(const uint8_t *__restrict__ flags_first,
-                                                              const uint8_t *__restrict__ flags_last,
-                                                              const double *__restrict__ coeff_first,
-                                                              const double *__restrict__ coeff_last, double tg, double dt,
-                                                              double w0, double wn, long nlines, double *__restrict__ mat,
-                                                              double *__restrict__ kap)
-{
-    const long l = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= nlines) return;
-    const bool has_lo = (flags_first[l] & 2u) != 0, has_hi = (flags_last[l] & 4u) != 0;   // the line continues below / above
-    const double p0 = w0 / tg, pn = wn / tg;
-    double aF = 0.0, cF = 0.0, aL = 0.0, cL = 0.0, klo = 0.0, khi = 0.0;
-    if (has_lo && has_hi) {                       // a middle rank: psi_lo = w, psi_hi = reversed w
-        aF = -w0; cF = -wn; aL = -wn; cL = -w0;
-    } else if (has_hi) {                          // first rank: row 0 is the global line start
-        const double delta = dt * coeff_first[l] - tg;
-        const double kappa = delta / (1.0 + delta * p0);
-        klo = kappa * pn;                         // psi_hi = rev(w) - klo * w
-        cF = -(wn - klo * w0);
-        cL = -(w0 - klo * wn);
-    } else if (has_lo) {                          // last rank: row n-1 is the global line end
-        const double delta = dt * coeff_last[l] - tg;
-        const double kappa = delta / (1.0 + delta * p0);
-        khi = kappa * pn;                         // psi_lo = w - khi * rev(w)
-        aF = -(w0 - khi * wn);
-        aL = -(wn - khi * w0);
-    }
-    mat[l] = aF; mat[nlines + l] = cF; mat[2 * nlines + l] = aL; mat[3 * nlines + l] = cL;
-    kap[l] = klo; kap[nlines + l] = khi;
-}
-
-// per step, after the interface solve: the coefficients of w[i] and w[n-1-i] in the correction of every line
-__global__ __launch_bounds__(256) void k_deferred_exact_coef(const double *__restrict__ xlo, const double *__restrict__ xhi,
-                                                             const double *__restrict__ kap, long nlines,
-                                                             double *__restrict__ clo, double *__restrict__ chi)
-{
-    const long l = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= nlines) return;
-    const double lo = xlo[l], hi = xhi[l];        // (0 where there is no neighbour: k_interface)
-    clo[l] = __builtin_fma(-kap[l], hi, lo);            // first rank: xlo = 0, c_lo = -klo * xhi
-    chi[l] = __builtin_fma(-kap[nlines + l], lo, hi);   // last rank:  xhi = 0, c_hi = -khi * xlo
+    return by_variant(has_dir, has_q, a, [&](auto dir, auto q, const SweepArgs &v) {
+        return condense_dispatch<decltype(dir)::value, decltype(q)::value>(axis, v, L, s, cond, work, work_bytes, st, fz);
+    });
 }
 
 }  // namespace adi
@@ -610,130 +450,56 @@ using namespace adi;
 
 extern "C" {
 
-int adi_interface_solve(const double *d_cond_all, int nranks, int rank, long nlines, double *d_xlo, double *d_xhi,
-                        void *stream)
+int adi_axis0_classify(const uint8_t *d_flags, const uint8_t *d_dir_mask, int nx, int ny, int nz, long plane_stride,
+                       uint8_t *d_cls, unsigned *d_list, void *stream)
 {
-    ADI_REQUIRE(d_cond_all && d_xlo && d_xhi && nranks >= 1 && rank >= 0 && rank < nranks && nlines > 0,
-                "adi_interface_solve: bad argument");
-    hipLaunchKernelGGL(k_interface, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, as_stream(stream), d_cond_all,
-                       nranks, rank, nlines, d_xlo, d_xhi);
+    ADI_REQUIRE(d_flags && d_cls && d_list, "adi_axis0_classify: null argument");
+    Lay L;
+    if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
+    hipStream_t st = as_stream(stream);
+    ADI_HIP_TRY(hipMemsetAsync(d_list, 0, sizeof(unsigned), st));
+    const long nlines = (long)ny * nz;
+    hipLaunchKernelGGL(k_classify_lines0, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, st, d_flags, d_dir_mask, L,
+                       d_cls, d_list);
     ADI_CHECK_LAUNCH();
     return ADI_OK;
 }
 
-int adi_interface_pair(const double *d_my_lo, const double *d_my_hi, const double *d_prev_hi, const double *d_next_lo,
-                       long nlines, double *d_xlo, double *d_xhi, void *stream)
+int adi_axis0_dots_finish(int variant, const double *d_part, const double *d_weights, const uint8_t *d_cls,
+                          const unsigned *d_list, const double *d_R0, const uint8_t *d_flags, const double *d_coeff,
+                          const uint8_t *d_dir_mask, const double *d_dir_val, const double *d_qflux, int nx, int ny,
+                          int nz, long plane_stride, double theta, double gam, double dt, double Tinf, long line_begin,
+                          long line_end, double *d_cond, void *stream)
 {
-    ADI_REQUIRE(d_xlo && d_xhi && nlines > 0, "adi_interface_pair: bad argument");
-    ADI_REQUIRE((!d_prev_hi || d_my_lo) && (!d_next_lo || d_my_hi), "adi_interface_pair: missing own window");
-    hipLaunchKernelGGL(k_interface_pair, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, as_stream(stream), d_my_lo,
-                       d_my_hi, d_prev_hi, d_next_lo, nlines, d_xlo, d_xhi);
-    ADI_CHECK_LAUNCH();
-    return ADI_OK;
-}
-int adi_axis0_deferred_setup(int n, double theta, double gam, double tol, double *d_w, double *h_omega, int *h_reach,
-                             void *stream)
-{
-    ADI_REQUIRE(n >= 2 && d_w && h_omega && h_reach && tol >= 0.0, "adi_axis0_deferred_setup: bad argument");
-    // w = tg * tridiag(-tg, 1+2tg, -tg)^-1 e_0 (n x n): Thomas in long double; the closure of the far end does not
-    // matter where w has decayed there, which is the condition the caller tests (*h_reach < n)
-    const long double tg = (long double)theta * (long double)gam, b = 1.0L + 2.0L * tg;
-    std::vector<long double> cp(n), x(n);
-    std::vector<double> w(n);
-    long double piv = b;
-    cp[0] = -tg / piv; x[0] = tg / piv;
-    for (int i = 1; i < n; ++i) {
-        piv = b + tg * cp[i - 1];
-        cp[i] = -tg / piv;
-        x[i] = (tg * x[i - 1]) / piv;
-    }
-    for (int i = n - 2; i >= 0; --i) x[i] -= cp[i] * x[i + 1];
-    int reach = 0;
-    for (int i = 0; i < n; ++i) {
-        w[i] = (double)x[i];
-        if (w[i] > tol) reach = i + 1; else w[i] = 0.0;      // (w decreases monotonically: exactly 0 beyond its reach)
-    }
-    *h_omega = w[0];
-    *h_reach = reach;
-    ADI_HIP_TRY(hipMemcpyAsync(d_w, w.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, as_stream(stream)));
-    ADI_HIP_TRY(hipStreamSynchronize(as_stream(stream)));      // w lives on this stack frame
-    return ADI_OK;
-}
-
-int adi_interface_deferred(const double *d_first, const double *d_last, const double *d_prev_last,
-                           const double *d_next_first, double omega, long nlines, double *d_ulo, double *d_uhi,
-                           void *stream)
-{
-    ADI_REQUIRE(d_ulo && d_uhi && nlines > 0, "adi_interface_deferred: bad argument");
-    ADI_REQUIRE((!d_prev_last || d_first) && (!d_next_first || d_last), "adi_interface_deferred: missing own plane");
-    ADI_REQUIRE(omega >= 0.0 && omega < 1.0, "adi_interface_deferred: omega = %g is not a decaying weight", omega);
-    const double idet = 1.0 / (1.0 - omega * omega);
-    hipLaunchKernelGGL(k_interface_deferred, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, as_stream(stream),
-                       d_first, d_last, d_prev_last, d_next_first, omega, idet, nlines, d_ulo, d_uhi);
-    ADI_CHECK_LAUNCH();
-    return ADI_OK;
-}
-int adi_interface_deferred_lines(const double *d_first, const double *d_last, const double *d_prev_last,
-                                 const double *d_next_first, const double *d_om_lo_own, const double *d_om_hi_prev,
-                                 const double *d_om_hi_own, const double *d_om_lo_next, long nlines, double *d_ulo,
-                                 double *d_uhi, const uint8_t *d_uni_lo, const uint8_t *d_uni_hi, double *d_ulo_uni,
-                                 double *d_uhi_uni, void *stream)
-{
-    ADI_REQUIRE(d_first && d_last && d_ulo && d_uhi && nlines > 0, "adi_interface_deferred_lines: bad argument");
-    ADI_REQUIRE(!d_prev_last || (d_om_lo_own && d_om_hi_prev), "adi_interface_deferred_lines: lower boundary without its weights");
-    ADI_REQUIRE(!d_next_first || (d_om_hi_own && d_om_lo_next), "adi_interface_deferred_lines: upper boundary without its weights");
-    hipLaunchKernelGGL(k_interface_deferred_lines, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, as_stream(stream),
-                       d_first, d_last, d_prev_last, d_next_first, d_om_lo_own, d_om_hi_prev, d_om_hi_own, d_om_lo_next,
-                       nlines, d_ulo, d_uhi, d_uni_lo, d_uni_hi, d_ulo_uni, d_uhi_uni);
+    bool has_dir, has_q;
+    if (int rc = variant_flags(variant, &has_dir, &has_q)) return rc;
+    ADI_REQUIRE(d_part && d_weights && d_cls && d_list && d_R0 && d_flags && d_coeff && d_cond,
+                "adi_axis0_dots_finish: null argument");
+    ADI_REQUIRE(!has_dir || (d_dir_mask && d_dir_val), "adi_axis0_dots_finish: variant needs Dirichlet arrays");
+    ADI_REQUIRE(!has_q || d_qflux, "adi_axis0_dots_finish: variant needs the flux array");
+    Lay L;
+    if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
+    const long nlines = (long)ny * nz;
+    ADI_REQUIRE(line_begin >= 0 && line_end <= nlines && line_begin < line_end, "adi_axis0_dots_finish: bad line range");
+    SweepScal s;
+    s.tg = theta * gam; s.dt = dt; s.Tinf = Tinf; s.sparse = 0; s.box = 0;
+    hipStream_t st = as_stream(stream);
+    const long nsel = line_end - line_begin;
+    const auto finish = has_q ? k_dots_finish<true> : k_dots_finish<false>;
+    hipLaunchKernelGGL(finish, dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, st, d_part, dots_nchunk(nx), d_weights, d_cls,
+                       d_flags, d_coeff, d_qflux, L, s, line_begin, line_end, d_cond);
+    // the lines that are not uniform: the serial two-recurrence condensation from the stored R0
+    long inner_stride;
+    const LineGeom g = line_geom(0, L, &inner_stride);
+    const SweepArgs a = {d_R0, d_flags, d_coeff, d_dir_mask, d_dir_val, d_qflux};
+    by_variant(has_dir, has_q, a, [&](auto dir, auto q, const SweepArgs &v) {
+        launch_condense_generic<decltype(dir)::value, decltype(q)::value>(v, d_cond, nlines, g, inner_stride, s, d_list, line_begin,
+                                                                          nsel, st);
+        return ADI_OK;
+    });
     ADI_CHECK_LAUNCH();
     return ADI_OK;
 }
 
-int adi_deferred_lines_apply(double *d_x, int nx, long plane_stride, long plane_cells, const int *d_cells, long nflag,
-                             const double *d_wc, int K, const double *d_u, int from_high_end, const int *d_nrows, void *stream)
-{
-    ADI_REQUIRE(d_x && d_u && nx > 0 && plane_cells > 0 && plane_stride >= plane_cells && K >= 0 && K <= nx && nflag >= 0,
-                "adi_deferred_lines_apply: bad argument");
-    if (nflag == 0 || K == 0) return ADI_OK;
-    ADI_REQUIRE(d_cells && d_wc, "adi_deferred_lines_apply: flagged lines without their cells / weights");
-    const unsigned gy = (unsigned)(K < 64 ? K : 64);
-    hipLaunchKernelGGL(k_deferred_lines_apply, dim3((unsigned)((nflag + 255) / 256), gy), dim3(256), 0, as_stream(stream), d_x, nx,
-                       plane_stride, d_cells, nflag, d_wc, K, d_u, from_high_end, d_nrows);
-    ADI_CHECK_LAUNCH();
-    return ADI_OK;
-}
-
-int adi_deferred_exact_setup(const uint8_t *d_flags_first, const uint8_t *d_flags_last, const double *d_coeff_first,
-                             const double *d_coeff_last, double theta, double gam, double dt, double w0, double wn,
-                             long nlines, double *d_mat, double *d_kap, void *stream)
-{
-    ADI_REQUIRE(d_flags_first && d_flags_last && d_coeff_first && d_coeff_last && d_mat && d_kap && nlines > 0,
-                "adi_deferred_exact_setup: bad argument");
-    ADI_REQUIRE(theta * gam > 0.0 && w0 > 0.0, "adi_deferred_exact_setup: needs theta*gam > 0");
-    hipLaunchKernelGGL(k_deferred_exact_setup, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, as_stream(stream),
-                       d_flags_first, d_flags_last, d_coeff_first, d_coeff_last, theta * gam, dt, w0, wn, nlines, d_mat, d_kap);
-    ADI_CHECK_LAUNCH();
-    return ADI_OK;
-}
-
-int adi_interface_solve_uniform(const double *d_g_all, const double *d_mat_all, const double *d_scal_all, int nranks, int rank,
-                                long nlines, double *d_xlo, double *d_xhi, void *stream)
-{
-    ADI_REQUIRE(d_g_all && d_mat_all && d_scal_all && d_xlo && d_xhi && nranks >= 2 && rank >= 0 && rank < nranks && nlines > 0,
-                "adi_interface_solve_uniform: bad argument");
-    hipLaunchKernelGGL(k_interface_uniform, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, as_stream(stream), d_g_all,
-                       d_mat_all, d_scal_all, nranks, rank, nlines, d_xlo, d_xhi);
-    ADI_CHECK_LAUNCH();
-    return ADI_OK;
-}
-
-int adi_deferred_exact_coef(const double *d_xlo, const double *d_xhi, const double *d_kap, long nlines, double *d_clo,
-                            double *d_chi, void *stream)
-{
-    ADI_REQUIRE(d_xlo && d_xhi && d_kap && d_clo && d_chi && nlines > 0, "adi_deferred_exact_coef: bad argument");
-    hipLaunchKernelGGL(k_deferred_exact_coef, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, as_stream(stream), d_xlo,
-                       d_xhi, d_kap, nlines, d_clo, d_chi);
-    ADI_CHECK_LAUNCH();
-    return ADI_OK;
-}
 }  // extern "C"
+

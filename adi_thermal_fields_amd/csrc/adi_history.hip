@@ -261,11 +261,6 @@ static int make_hist_launch(const char *who, int nx, int ny, int nz, long plane_
     return ADI_OK;
 }
 
-static bool aligned16(const void *a) { return ((uintptr_t)a & 15) == 0; }
-
-// 16-byte loads of the fields and 2-byte loads of the flags: pairs start on even offsets of aligned arrays
-static bool hist_vec(const Lay &L, const void *flags) { return L.nz % 2 == 0 && L.sx % 2 == 0 && ((uintptr_t)flags & 1) == 0; }
-
 }  // namespace adi
 
 using namespace adi;
@@ -288,7 +283,7 @@ int adi_history_record(const adi_history_levels *h_levels, const void *d_block, 
     HistLaunch g;
     if (int rc = make_hist_launch("adi_history_record", nx, ny, nz, plane_stride, &g)) return rc;
     const HistBlock *blk = (const HistBlock *)d_block;
-    if (hist_vec(g.L, d_flags) && aligned16(d_T_in) && aligned16(d_T_out) && aligned16(d_peak))
+    if (pair_vec(g.L, d_flags, d_T_in, d_T_out, d_peak))
         hipLaunchKernelGGL(k_history_record<true>, g.grid, dim3(256), 0, as_stream(stream), *h_levels, blk, d_T_in, d_T_out,
                            d_peak, d_t_hi, d_t_lo, (int *)d_log, d_flags, (const unsigned *)d_bricks, g.L);
     else
@@ -324,7 +319,7 @@ int adi_history_seed(const double *d_T, double *d_peak, double *d_t_hi, double *
     ADI_REQUIRE(d_peak != d_t_hi && d_peak != d_t_lo && d_t_hi != d_t_lo, "adi_history_seed: the state arrays alias");
     HistLaunch g;
     if (int rc = make_hist_launch("adi_history_seed", nx, ny, nz, plane_stride, &g)) return rc;
-    if (hist_vec(g.L, d_flags) && aligned16(d_T))
+    if (pair_vec(g.L, d_flags, d_T))
         hipLaunchKernelGGL(k_history_seed<true>, g.grid, dim3(256), 0, as_stream(stream), d_T, d_peak, d_t_hi, d_t_lo, d_flags,
                            (const unsigned *)d_bricks, d_sel, g.L);
     else

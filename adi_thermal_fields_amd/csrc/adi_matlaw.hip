@@ -127,7 +127,7 @@ int adi_matlaw_theta(const adi_material_law *h_law, const double *d_T, double *d
     if (int rc = check_matlaw("adi_matlaw_theta", *h_law)) return rc;
     PhaseLaunch g;
     if (int rc = make_phase_launch("adi_matlaw_theta", nx, ny, nz, plane_stride, &g)) return rc;
-    if (phase_vec(g.L, d_T, d_theta, d_flags))
+    if (pair_vec(g.L, d_flags, d_T, d_theta))
         hipLaunchKernelGGL(k_matlaw_theta<true>, g.grid, dim3(256), 0, as_stream(stream), *h_law, d_T, d_theta, d_flags,
                            d_bricks, g.L);
     else
@@ -146,7 +146,7 @@ int adi_matlaw_recover(const adi_material_law *h_law, const double *d_T, double 
     if (int rc = check_matlaw("adi_matlaw_recover", *h_law)) return rc;
     PhaseLaunch g;
     if (int rc = make_phase_launch("adi_matlaw_recover", nx, ny, nz, plane_stride, &g)) return rc;
-    if (phase_vec(g.L, d_T, d_out, d_flags))
+    if (pair_vec(g.L, d_flags, d_T, d_out))
         hipLaunchKernelGGL(k_matlaw_recover<true>, g.grid, dim3(256), 0, as_stream(stream), *h_law, d_T, d_out, d_flags,
                            d_bricks, d_dir_mask, g.L);
     else

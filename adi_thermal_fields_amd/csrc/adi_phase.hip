@@ -169,7 +169,7 @@ int adi_phase_apply(const adi_phase_change *h_law, double cp, double *d_T, doubl
     if (int rc = make_phase_law("adi_phase_apply", *h_law, cp, &w)) return rc;
     PhaseLaunch g;
     if (int rc = make_phase_launch("adi_phase_apply", nx, ny, nz, plane_stride, &g)) return rc;
-    if (phase_vec(g.L, d_T, d_f, d_flags))
+    if (pair_vec(g.L, d_flags, d_T, d_f))
         hipLaunchKernelGGL(k_phase_apply<true>, g.grid, dim3(256), 0, as_stream(stream), w, d_T, d_f, d_flags, d_bricks,
                            d_dir_mask, (unsigned *)d_summary, g.L, g.nby, g.nbz);
     else
@@ -189,7 +189,7 @@ int adi_phase_seed(const adi_phase_change *h_law, const double *d_T, double *d_f
     if (int rc = make_phase_law("adi_phase_seed", *h_law, 1.0, &w)) return rc;
     PhaseLaunch g;
     if (int rc = make_phase_launch("adi_phase_seed", nx, ny, nz, plane_stride, &g)) return rc;
-    if (phase_vec(g.L, d_T, d_f, d_flags))
+    if (pair_vec(g.L, d_flags, d_T, d_f))
         hipLaunchKernelGGL(k_phase_seed<true>, g.grid, dim3(256), 0, as_stream(stream), w, d_T, d_f, d_flags, d_bricks, d_sel,
                            (unsigned *)d_summary, g.L, g.nby, g.nbz);
     else

@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "adi_cart_host.hpp"
+#include "adi_cell_dev.hpp"
 #include "adi_goldak_dev.hpp"
 
 namespace adi {
@@ -109,7 +110,8 @@ __global__ __launch_bounds__(256) void k_source_sample(adi_heat_source s, const 
     out[p] = (flags[p] & 1u) ? goldak_q(s, c, (i + 0.5) * dx, (j + 0.5) * dx, (k + 0.5) * dx) : 0.0;
 }
 
-// k_explicit_cell (adi_explicit.hip) with the source field added last: R0 = (T + f*((L0 + L1) + L2)) + scale*S
+// k_explicit_cell (adi_explicit.hip; explicit_cell of adi_cell_dev.hpp is the value both store) with the source field
+// added last: R0 = (T + f*((L0 + L1) + L2)) + scale*S
 __global__ __launch_bounds__(256) void k_explicit_src(const double *__restrict__ T, const double *__restrict__ S,
                                                       const uint8_t *__restrict__ flags, double *__restrict__ R0, Lay L,
                                                       double invdx2, double f, double scale)
@@ -121,18 +123,9 @@ __global__ __launch_bounds__(256) void k_explicit_src(const double *__restrict__
     const int i = (int)(q / plane);
     const long r = q - (long)i * plane;
     const long p = (long)i * L.sx + r;
-    const long sx = L.sx, sy = L.nz;
-    const double t = T[p];
-    const unsigned fl = flags[p];
-    double L0 = 0.0, L1 = 0.0, L2 = 0.0;
+    unsigned fl;
     double src = 0.0;
-    if (fl & 1u) {
-        L0 = lap_axis(fl & 2u, fl & 4u, (fl & 2u) ? T[p - sx] : 0.0, (fl & 4u) ? T[p + sx] : 0.0, t, invdx2);
-        L1 = lap_axis(fl & 8u, fl & 16u, (fl & 8u) ? T[p - sy] : 0.0, (fl & 16u) ? T[p + sy] : 0.0, t, invdx2);
-        L2 = lap_axis(fl & 32u, fl & 64u, (fl & 32u) ? T[p - 1] : 0.0, (fl & 64u) ? T[p + 1] : 0.0, t, invdx2);
-        src = scale * S[p];
-    }
-    const double r0 = t + f * ((L0 + L1) + L2);
+    const double r0 = explicit_cell(T, flags, p, L, invdx2, f, fl, [&] { src = scale * S[p]; });
     R0[p] = (fl & 1u) ? r0 + src : r0;
 }
 

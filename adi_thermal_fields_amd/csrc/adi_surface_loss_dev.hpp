@@ -6,7 +6,7 @@
 //                           the cell is not exposed along the axis
 // One workgroup per 16 x 16 x 16 brick of the flags summary; thread (di, dj) owns the 16 cells of row (i, j) along axis 2 and
 // reads their flags bytes in one 16-byte load.  Arithmetic: the law of the header, then (h * A) / Ccell accumulated '-' face
-// first -- the expressions of k_build_coeffs (adi_explicit.hip) fed with the six h fields, contraction off.  No existing
+// first -- the expressions of k_build_coeffs (adi_fields.hip) fed with the six h fields, contraction off.  No existing
 // kernel changes: the sweeps read the arrays as they read any pack built from per-voxel h.
 // A header, because adi_matlaw.hip launches the same kernel with a ratio multiplied into every h (RATIO below).
 #pragma once
@@ -154,7 +154,7 @@ int launch_surface_loss(const char *who, const RATIO &ratio, const adi_surface_l
     for (int a = 0; a < 3; ++a) ADI_REQUIRE(d_coeff[a], "%s: null output", who);
     Lay L;
     if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
-    ADI_REQUIRE(k_begin >= 0 && k_end <= nz && k_begin <= k_end, "%s: bad plane range [%d, %d)", who, k_begin, k_end);
+    if (int rc = check_plane_range(who, k_begin, k_end, nz)) return rc;
     ADI_REQUIRE(dx > 0.0 && rho > 0.0 && cp > 0.0, "%s: dx, rho and cp must be > 0", who);
     if (int rc = check_law(*h_law, Tinf)) return rc;
     if (k_begin == k_end) return ADI_OK;
@@ -177,8 +177,8 @@ int launch_surface_loss(const char *who, const RATIO &ratio, const adi_surface_l
         w.slope[m] = 0.0;
     }
     for (int m = 0; m + 1 < h_law->n_knots; ++m) w.slope[m] = (w.fp[m + 1] - w.fp[m]) / (w.xp[m + 1] - w.xp[m]);
-    // A = dx*dx, V = dx**3 (CPython float_pow -> libm pow), Ccell = rho*cp*V: adi3d_numba_coeff.py:66-68
-    const double A = dx * dx, V = pow(dx, 3.0), Ccell = rho * cp * V;
+    double A, Ccell;
+    cell_constants(dx, rho, cp, &A, &Ccell);
     const int nbx = (nx + kBrick - 1) / kBrick, nby = (ny + kBrick - 1) / kBrick, nbz = (nz + kBrick - 1) / kBrick;
     const int bwx = (nbx + 31) >> 5;
     const int bk0 = k_begin / kBrick, bk1 = (k_end + kBrick - 1) / kBrick;

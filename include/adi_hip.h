@@ -322,6 +322,13 @@ int adi_axis0_deferred_setup(int n, double theta, double gam, double tol, double
 int adi_interface_deferred(const double *d_first, const double *d_last, const double *d_prev_last,
                            const double *d_next_first, double omega, long nlines, double *d_ulo, double *d_uhi,
                            void *stream);
+/* The weights adi_axis0_dots_setup (kind DOTS: c = 1) and adi_axis0_deferred_setup (kind DEFERRED: c = theta*gam) upload,
+ * on the host: h_w[n] = c * first column of tridiag(-tg, 1+2tg, -tg)^-1, entries <= tol stored as exactly 0,
+ * *h_reach = number of entries kept (tol = 0 cuts nothing).  The same builder as those entries; host arithmetic only: no
+ * HIP call, no device needed.  n < 2, tol < 0, an unknown kind or a NULL pointer is ADI_ERR_ARG. */
+#define ADI_AXIS0_WEIGHTS_DOTS     0
+#define ADI_AXIS0_WEIGHTS_DEFERRED 1
+int adi_axis0_weights_host(int n, double theta, double gam, int kind, double tol, double *h_w, int *h_reach);
 /* The deferred form WITHOUT decay (ABI v15: thin slabs / strong scaling, e.g. 512^3 over 8 GPUs = 64 planes at cfl 200).
  * x = x0 + c_lo w[i] + c_hi w[n-1-i] still holds (adi_axis0_deferred_setup with tol = 0: no weight is cut); the interface
  * system now couples all ranks, as in the two-pass `exact` form, but only its right-hand sides change from step to step:
