@@ -189,6 +189,10 @@ SIGNATURES = {
     'adi_history_seed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_long, c_void_p]),
     'adi_history_reset_log': (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
+    'adi_solid_record': (c_int, [c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    'adi_solid_seed': (c_int, [c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                               c_int, c_int, c_long, c_void_p]),
     'adi_cyl_source_set': (c_int, [c_void_p, c_void_p, c_double, c_double, ctypes.c_longlong, c_void_p]),
     'adi_cyl_source_sample': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double, c_double,
                                       c_void_p, c_void_p, c_void_p]),
@@ -219,6 +223,7 @@ SURFACE_LOSS_SIGMA = 5.670374419e-8   # ADI_SURFACE_LOSS_SIGMA (Stefan-Boltzmann
 MATLAW_MAX_KNOTS = 16        # ADI_MATLAW_MAX_KNOTS
 HISTORY_BLOCK_BYTES = 40     # ADI_HISTORY_BLOCK_BYTES: { double t0, dt; int64 n, slot, capacity }
 HISTORY_LOG_INTS = 8         # ADI_HISTORY_LOG_INTS: { cells, lo[3], hi[3], pad }
+BRICK = 16                   # kBrick (csrc/adi_cart_dev.hpp): the edge of a brick of the flags summary
 STLCORR_DROPPED = (1 << 63) - 1   # ADI_STLCORR_DROPPED
 STLCORR_MAX_SUBDIV = 4096    # ADI_STLCORR_MAX_SUBDIV
 

@@ -3,94 +3,19 @@
 //   k_history_record   every step: T_peak, t_hi, t_lo in place, one row of the log
 //   k_history_seed     T_peak = T, times NaN on selected in-mask cells, NaN off the mask (reset, newborn cells)
 //   k_history_clock, k_history_tick, k_history_reset_log   the device block (t0, dt, n, slot, capacity) and the log rows
-// One workgroup of 256 threads per 16 x 16 x 16 brick of the flags summary, with the cell ownership of adi_phase.hip: lane l
-// of a wave owns cells 2(l & 7), 2(l & 7) + 1 of row (l >> 3), so one 16-byte load instruction of a wave covers eight whole
-// 128-byte row pieces, and the eight loads of a thread cover the 256 rows of the brick.  The loads of a thread are issued
+// One workgroup of 256 threads per 16 x 16 x 16 brick of the flags summary, with the cell ownership and the load forms of
+// adi_history_dev.hpp (shared with adi_solidify.hip).  The loads of a thread are issued
 // together ahead of the arithmetic; stores go cell by cell (8 bytes) so that a cell no rule touches is never written.  The
 // crossing rules only ever store t_hi and t_lo, so neither is loaded.  The pool of a brick is three words per thread (the
 // count, the set of local i and j, the set of local k), OR- / add-reduced over the wave by shuffles and over the four waves
 // through LDS; one thread of a brick that holds pool cells issues seven integer atomics.  No existing kernel changes.
 #include <math.h>
 
-#include "adi_cart_host.hpp"
+#include "adi_history_dev.hpp"
 
 namespace adi {
 
-struct HistBlock {
-    double t0, dt;
-    long long n, slot, capacity;
-};
-static_assert(sizeof(HistBlock) == ADI_HISTORY_BLOCK_BYTES, "history block layout");
-
-constexpr int kHistIter = 8;      // row groups of a brick per thread: 256 rows / (256 threads / 8 lanes per row)
 constexpr int kHistEmptyLo = 0x7fffffff;
-
-struct HistCell {
-    long p;          // offset of the pair's first cell
-    unsigned in;     // bit c: cell c of the pair lies inside the box
-    unsigned m;      // bit c: ... and in the mask
-};
-
-// 16-byte access needs even row and plane strides and 16-byte aligned arrays (host: `vec`); then a pair never straddles the
-// end of a row.  Otherwise cell by cell.
-template <bool VEC>
-__device__ __forceinline__ void hist_load_pair(const double *a, const HistCell &c, double &v0, double &v1)
-{
-    if (VEC) {
-        const double2 v = *reinterpret_cast<const double2 *>(a + c.p);
-        v0 = v.x; v1 = v.y;
-    } else {
-        v0 = a[c.p];
-        v1 = (c.in & 2u) ? a[c.p + 1] : 0.0;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ unsigned hist_mask_pair(const uint8_t *__restrict__ flags, const HistCell &c)
-{
-    if (VEC) {
-        const unsigned v = *reinterpret_cast<const unsigned short *>(flags + c.p);
-        return (v & 1u) | ((v >> 7) & 2u);
-    }
-    unsigned m = flags[c.p] & 1u;
-    if (c.in & 2u) m |= (flags[c.p + 1] & 1u) << 1;
-    return m;
-}
-
-// the pair of cells thread `tid` owns in row group `it` of brick (bi, bj, bk): local (i, j, k) = (2 it + (tid >> 7),
-// (tid >> 3) & 15, 2 (tid & 7))
-__device__ __forceinline__ HistCell hist_cell(const Lay &L, int bi, int bj, int bk, int it, unsigned tid)
-{
-    const int row = it * 32 + (int)(tid >> 3);
-    const int i = bi * kBrick + (row >> 4), j = bj * kBrick + (row & 15), k = bk * kBrick + 2 * (int)(tid & 7u);
-    HistCell c;
-    c.p = (long)i * L.sx + (long)j * L.nz + k;
-    c.in = (i < L.nx && j < L.ny && k < L.nz) ? ((k + 1 < L.nz) ? 3u : 1u) : 0u;
-    c.m = 0u;
-    return c;
-}
-
-__device__ __forceinline__ bool hist_all_solid(const unsigned *__restrict__ bricks, const Lay &L, int bi, int bj, int bk)
-{
-    if (bricks == nullptr) return false;
-    const int nbx = (L.nx + kBrick - 1) / kBrick, nbz = (L.nz + kBrick - 1) / kBrick;
-    return (bricks[brick_word(bi * kBrick, bj * kBrick, bk * kBrick, nbz, (nbx + 31) >> 5)] & brick_bit(bi * kBrick)) != 0u;
-}
-
-__device__ __forceinline__ double hist_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-__device__ __forceinline__ unsigned wave_or(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_add(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_history_record(adi_history_levels w, const HistBlock *__restrict__ blk,
@@ -245,20 +170,6 @@ __global__ __launch_bounds__(256) void k_history_reset_log(HistBlock *blk, int *
     r[1] = kHistEmptyLo; r[2] = kHistEmptyLo; r[3] = kHistEmptyLo;
     r[4] = -1; r[5] = -1; r[6] = -1;
     r[7] = 0;
-}
-
-struct HistLaunch {
-    Lay L;
-    dim3 grid;
-};
-
-static int make_hist_launch(const char *who, int nx, int ny, int nz, long plane_stride, HistLaunch *g)
-{
-    if (int rc = make_lay(nx, ny, nz, plane_stride, &g->L)) return rc;
-    const int nbx = (nx + kBrick - 1) / kBrick, nby = (ny + kBrick - 1) / kBrick, nbz = (nz + kBrick - 1) / kBrick;
-    ADI_REQUIRE(nby <= 65535 && nbx <= 65535, "%s: box of %d x %d x %d is too large", who, nx, ny, nz);
-    g->grid = dim3((unsigned)nbz, (unsigned)nby, (unsigned)nbx);
-    return ADI_OK;
 }
 
 }  // namespace adi

@@ -12,7 +12,7 @@ from .packs import _fc_arg
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .surface_loss import LossPacks
 from .phase import PhaseField, NonlinearPacks
-from .history import ThermalHistory
+from .history import ThermalHistory, SolidificationRecord
 
 
 def _gam(grid, mat, params):
@@ -128,7 +128,7 @@ def _ensure_general(pack):
         pack.d_qflux = L.empty(zero=True)
 
 
-def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material=None):
+def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material=None, solidification=None):
     """TypeError / ValueError for an optional argument of the step that is of the wrong kind or was made for other packs, another
     grid or another cp: once per adi_step_hip_coeff call and once per StagedStepper, before anything is launched"""
     if material is not None:
@@ -168,6 +168,12 @@ def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history
             raise TypeError("history must be a ThermalHistory")
         if history.grid is not grid:
             raise ValueError("history: the ThermalHistory belongs to another grid")
+    if solidification is not None:
+        if not isinstance(solidification, SolidificationRecord):
+            raise TypeError("solidification must be a SolidificationRecord")
+        if solidification.grid is not grid:
+            raise ValueError("solidification: the SolidificationRecord belongs to another grid")
+        solidification._check_mask()
 
 
 def _no_mark():
@@ -175,19 +181,21 @@ def _no_mark():
 
 
 def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, source=None, owner=None, t_set=None,
-                 surface_loss=None, phase=None, history=None, captured=False, mark=_no_mark, material=None):
+                 surface_loss=None, phase=None, history=None, captured=False, mark=_no_mark, material=None,
+                 solidification=None):
     """THE launch sequence of one step t_in -> out (fp64 tensors in the grid's layout; nothing is allocated): the surface-loss
     update from t_in, the explicit stage and sweep 0 (one launch when `fused`), the moving source's correction of sweep 0's
-    output, sweeps 1 and 2, the latent-heat correction of `out`, the history record.  With `material` (a NonlinearPacks): its
+    output, sweeps 1 and 2, the latent-heat correction of `out`, the history record, the solidification record.  With `material` (a NonlinearPacks): its
     `begin(t_in)` first, the launches above on its Kirchhoff field with Theta(Tinf) as the ambient, its `recover(t_in, out)`
-    after sweep 2, and the history on (t_in, out) as ever.  Every form of the step calls it --
+    after sweep 2, and the history and the solidification record on (t_in, out) as ever.  Every form of the step calls it --
     adi_step_hip_coeff with or without a source field, StagedStepper.step, and what StagedStepper.run captures -- with
     arguments that _check_extras has passed.
     d_S: a source FIELD in the grid's layout; the explicit stage takes it (adi_explicit_rhs_src), never fused.
     source, owner: a GoldakSource and the object that holds its device block and workspace; t_set: the step's start time if the
     block is to be set here, just ahead of the correction (None: the caller has set it).
     captured: a graph may replay these launches and the caller keeps the clocks: the source's block is ticked after the
-    correction, and the history launches its record without moving its host clock.  Otherwise no tick, and history.record.
+    correction, and the history and the solidification record launch their records without moving their host clocks.  Otherwise
+    no tick, and history.record / solidification.record.
     mark: called at the stage boundaries of per-stage timing: before the explicit stage, between it and sweep 0 when they are
     two launches, after sweep 0 with the source's correction, after sweep 1 and after sweep 2."""
     (ta, tb), _, _ = grid.scratch(2)
@@ -228,10 +236,15 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
             history._launch_record(t_in, out)
         else:
             history.record(t_in, out, params.dt)
+    if solidification is not None:
+        if captured:
+            solidification._launch_record(t_in, out)
+        else:
+            solidification.record(t_in, out, params.dt)
 
 
 def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None, phase=None, history=None,
-                       material=None):
+                       material=None, solidification=None):
     """adi3d_numba_coeff.py:290-302 / adi3d_gpu_coeff.py:213-230: explicit stage, then the three
     implicit sweeps in the order axis 0, 1, 2.  Returns a NEW array of the kind it was given;
     `Tn` is never modified.
@@ -256,12 +269,16 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     enthalpy is put back on its curve afterwards (adi_matlaw_theta first, adi_matlaw_recover after sweep 2); the
     ambient is the NonlinearPacks' own, `Tinf` here is not used.  Combines with S= in either form and history=, not with phase=
     or surface_loss=; params.theta must reach law.min_theta().  None: no such launch.
+    solidification: a SolidificationRecord of the grid: the cells that freeze in the step Tn -> result (after the correction of
+    `phase` or the recovery of `material`) get their crossing time, cooling rate and squared gradient at the recorder's own
+    clock, which moves on by dt (adi_solid_record and adi_history_tick on its block, the last launches, after `history`'s).
+    None: no such launch.
     Every optional argument is checked before the first launch (_check_extras); the launches are _launch_step's."""
     if isinstance(S, (ScanPath, ScanPathSource)):
         raise TypeError("adi_step_hip_coeff: a scan path enters the step as its field: S=path.sample_step(grid, t, dt) from the "
                         "host, or S=path.on_device().sample_step_device(grid, t, dt) evaluated on the device")
     source = S if isinstance(S, GoldakSource) else None
-    _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material)
+    _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification)
     if history is not None:
         history._check_mask()
     t_in, kind = _as_state(Tn, grid)
@@ -272,7 +289,7 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
         d_S = grid.layout.to_layout(S, torch.float64)
     out = grid.layout.empty()
     _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused_supported(grid), d_S=d_S, source=source, owner=grid, t_set=t,
-                 surface_loss=surface_loss, phase=phase, history=history, material=material)
+                 surface_loss=surface_loss, phase=phase, history=history, material=material, solidification=solidification)
     return _wrap(out, kind)
 
 
@@ -307,11 +324,13 @@ class StagedStepper:
     of the grid) the latent-heat correction is the last launch of every step, after the last of the five marks: the stage
     times stay those of the stage kernels.  With `history=` (a ThermalHistory of the grid) the record launch and its tick follow,
     the last launches of every step; `run` sets the recorder's block from the recorder's own clock `history.t` (not from `t0`,
-    which stays the source's time origin) and moves that clock on by nsteps*dt."""
+    which stays the source's time origin) and moves that clock on by nsteps*dt.  With `solidification=` (a SolidificationRecord
+    of the grid) its record launch and tick come after those, the last launches of every step, on the recorder's own clock in
+    the same way."""
 
     def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None, surface_loss=None, phase=None,
-                 history=None, material=None):
-        _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material)
+                 history=None, material=None, solidification=None):
+        _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification)
         self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
         # temperature-dependent surface loss: the packs' Robin coefficients rewritten from the step's INPUT buffer, the first
         # launch of every step -- captured with it (X -> Y reads X, Y -> X reads Y); the law travels by value in that launch,
@@ -323,6 +342,9 @@ class StagedStepper:
         # thermal history: the record of the step input -> output and the tick of its block, the last launches of every step
         # -- captured with it; the levels travel by value and the five buffers by pointer, so all are part of run()'s graph key
         self.history = history
+        # solidification record: the record of the step input -> output and the tick of its block, after the history's --
+        # captured with them; T_freeze and dx travel by value and the five buffers by pointer: part of run()'s graph key
+        self.solidification = solidification
         # k(T), cp(T): the Kirchhoff transform of the step's INPUT buffer (with the loss update, the first launches) and the
         # recovery of its OUTPUT buffer after sweep 2 -- captured with it; the laws and the ambient travel by value, the
         # Kirchhoff field by pointer, so all are part of run()'s graph key.  Stateless: the warm-up steps need no snapshot
@@ -351,7 +373,7 @@ class StagedStepper:
         """one step t -> out (both native-layout device tensors), no allocation: what a HIP graph captures"""
         _launch_step(t, out, self.grid, self.mat, self.params, self.packs, self.Tinf, self.fused, source=self.source, owner=self,
                      surface_loss=self.surface_loss, phase=self.phase, history=self.history, captured=captured, mark=mark,
-                     material=self.material)
+                     material=self.material, solidification=self.solidification)
 
     def run(self, T, nsteps, graph=True, t0=0.0):
         """The drivers' `nsub` loop (quick_compare_dirichlet_robin.py:169-178, waam_from_stl_v7_mm.py:525-528): `nsteps`
@@ -371,9 +393,11 @@ class StagedStepper:
                None if self.surface_loss is None else self.surface_loss.loss.key(),
                None if self.phase is None else self.phase.graph_key(),
                None if self.history is None else self.history.graph_key(),
-               None if self.material is None else self.material.graph_key())
-        if self.history is not None:
-            self.history._check_mask()
+               None if self.material is None else self.material.graph_key(),
+               None if self.solidification is None else self.solidification.graph_key())
+        clocked = [x for x in (self.history, self.solidification) if x is not None]   # the recorders: each its own clock
+        for x in clocked:
+            x._check_mask()
         st = getattr(self, '_graph', None)
         if st is None or st['key'] != key:
             # (zeroed where the box is padded, as Layout.to_layout does: the cells outside the logical grid are identity rows of
@@ -386,10 +410,10 @@ class StagedStepper:
             self.source.set_block(_source_block(self), t0, prm.dt)
         if graph and nsteps >= 2 and st['g'] is None:
             g.scratch(2)                                   # every buffer exists before the capture
-            stateful = [x for x in (self.phase, self.history) if x is not None]
-            held = [x.snapshot() for x in stateful]        # (the warm-up steps would advance f, the history, its log and clock)
-            if self.history is not None:
-                self.history.set_clock(prm.dt)
+            stateful = [x for x in (self.phase, self.history, self.solidification) if x is not None]
+            held = [x.snapshot() for x in stateful]        # (the warm-up steps would advance f, the recorders, log and clocks)
+            for x in clocked:
+                x.set_clock(prm.dt)
             self._step_into(X, Y); self._step_into(Y, X)   # warm-up outside the capture (lazy module loads, and the
             self._step_into(X, Y); self._step_into(Y, X)   # no-fallback promise is learnt on the third step); harmless:
             X.copy_(g.layout.to_layout(T, torch.float64))  # X is restored
@@ -404,8 +428,8 @@ class StagedStepper:
             self.captures += 1
         if self.source is not None:
             self.source.set_block(_source_block(self), t0, prm.dt)   # (after the warm-up: the counter starts at 0)
-        if self.history is not None:
-            self.history.set_clock(prm.dt)                 # (likewise; the recorder's own clock, not t0)
+        for x in clocked:
+            x.set_clock(prm.dt)                            # (likewise; the recorder's own clock, not t0)
         done = 0
         if graph and st['g'] is not None:
             for _ in range(nsteps // 2):
@@ -415,8 +439,8 @@ class StagedStepper:
         for _ in range(nsteps - done):
             self._step_into(cur, oth)
             cur, oth = oth, cur
-        if self.history is not None:
-            self.history.advance_clock(self.history.t, float(prm.dt), nsteps)
+        for x in clocked:
+            x.advance_clock(x.t, float(prm.dt), nsteps)
         out = g.layout.empty()
         out.copy_(cur)
         return DeviceField(out)

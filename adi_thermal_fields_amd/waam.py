@@ -96,6 +96,16 @@ def history_result(hist):
                 t_lo=np.asarray(hist.t_lo), melt_pool=hist.melt_pool())
 
 
+def solidification_result(rec):
+    """what the loops return of a SolidificationRecord: t_solid, cooling_rate, G and R as NumPy arrays (NaN off the mask and
+    where the cell never froze; G = sqrt(g2) and R = cooling_rate / G formed here, R = inf where G = 0)"""
+    rate = np.asarray(rec.cooling_rate)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        G = np.sqrt(np.asarray(rec.g2))
+        R = rate / G
+    return dict(t_solid=np.asarray(rec.t_solid), cooling_rate=rate, G=G, R=R)
+
+
 def _is_device_backend(backend):
     return hasattr(backend, 'to_device')
 
@@ -103,19 +113,21 @@ def _is_device_backend(backend):
 def _require_device_loop(who, backend, dev_loop, **asked):
     """ValueError for an option (name = value) that is set where the loop cannot serve it"""
     for name, cls in (('surface_loss', 'LossPacks'), ('phase_change', 'PhaseField'), ('history', 'ThermalHistory'),
-                      ('material_law', 'NonlinearPacks')):
+                      ('material_law', 'NonlinearPacks'), ('solidification', 'SolidificationRecord')):
         if asked.get(name) is not None and not (dev_loop and hasattr(backend, cls)):
             raise ValueError("%s: %s needs the device loop of a backend with %s" % (who, name, cls))
 
 
-def _extras_kw(lpacks, ph, hist, nm=None):
+def _extras_kw(lpacks, ph, hist, nm=None, sol=None):
     """the keywords of a step / a stepper for the extras that are present"""
-    return {k: v for k, v in (('surface_loss', lpacks), ('phase', ph), ('history', hist), ('material', nm)) if v is not None}
+    return {k: v for k, v in (('surface_loss', lpacks), ('phase', ph), ('history', hist), ('material', nm),
+                              ('solidification', sol)) if v is not None}
 
 
-def _sync_extras(T, ph, hist):
-    """after a birth / a new column: the newborn cells at f_eq(T) and at T_peak = T"""
-    for x in (ph, hist):
+def _sync_extras(T, ph, hist, sol=None):
+    """after a birth / a new column: the newborn cells at f_eq(T), at T_peak = T and "never froze" (cells born above T_freeze
+    set their brick's word)"""
+    for x in (ph, hist, sol):
         if x is not None:
             x.sync_mask(T)
 
@@ -136,7 +148,8 @@ def _birth(backend, T, grid, newborn, Ts):
 
 
 def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, layers, times_birth, times_out,
-                    on_frame=None, device_resident=True, device_loop=True, surface_loss=None, phase_change=None, history=None):
+                    on_frame=None, device_resident=True, device_loop=True, surface_loss=None, phase_change=None, history=None,
+                    solidification=None):
     """The event loop of waam_from_stl_v7_mm.py:515-550.  Returns (T_final as NumPy, number of ADI steps).
     surface_loss (a SurfaceLoss of the backend): the surface loses heat by that law, evaluated at the temperature at the start
     of every sub-step, in place of the constant `h` (which is then not used); device loop only.  None: the reference's loop.
@@ -146,7 +159,10 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     history (a HistoryLevels of the backend): peak temperature, cooling time and melt pool; one ThermalHistory lives through the
     run, sized from the schedule, every sub-step is recorded at the global time (which runs through the recorder's clock, idle
     intervals included), newborn cells are seeded at Ts; device loop only.  The return value gains a last element, the result
-    dict of history_result.  None: the loop without it, unchanged."""
+    dict of history_result.  None: the loop without it, unchanged.
+    solidification (T_freeze, a number): the conditions at the freezing front; one SolidificationRecord of the backend lives
+    through the run on the global time like the history, and sync_mask(T) follows every birth; device loop only.  The return
+    value gains a last element (after history's), the dict of solidification_result.  None: the loop without it, unchanged."""
     nx, ny, nz = mask_full.shape
     mask_act = np.zeros_like(mask_full, dtype=bool)
     grid = backend.Grid3D(nx, ny, nz, dx, mask_act)
@@ -169,7 +185,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         nonlocal T, nsteps
         nsub = max(1, int(math.ceil(seg / dt_cap)))
         params.dt = max(seg / nsub, 1e-15)
-        kw = _extras_kw(None if surface_loss is None else bpacks, ph, hist)
+        kw = _extras_kw(None if surface_loss is None else bpacks, ph, hist, sol=sol)
         if nsub >= GRAPH_MIN_NSUB and hasattr(backend, 'StagedStepper') and hasattr(T, 'fill_where'):
             # a long segment on the device backend: the nsub launches of this segment replayed from a HIP graph
             T = backend.StagedStepper(grid, mat, params, packs, Tinf, **kw).run(T, nsub)
@@ -188,8 +204,8 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     # output times and nothing waits for the device between births
     dev_loop = device_loop and device_resident and hasattr(backend, 'BirthPacks') and hasattr(T, 'fill_where')
     _require_device_loop('run_layer_birth', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
-                         history=history)
-    ph = hist = None
+                         history=history, solidification=solidification)
+    ph = hist = sol = None
     if dev_loop:
         import torch
         d_full = grid.layout.to_layout(mask_full, torch.uint8)
@@ -208,6 +224,8 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
             rows = sum(max(1, int(math.ceil(a / dt_cap))) for w, a in layer_birth_schedule(times_birth, times_out)
                        if w == 'advance')
             hist = backend.ThermalHistory(grid, history, capacity=max(1, rows), T=T)
+        if solidification is not None:
+            sol = backend.SolidificationRecord(grid, solidification, T=T)
     else:
         packs = build_packs()
     n_active = 0
@@ -224,7 +242,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
                 packs = bpacks.update(ks - 1, ke + 2)                             # :534, the planes that changed
             else:
                 packs = bpacks.rebuild(T, ks - 1, ke + 2)
-            _sync_extras(T, ph, hist)
+            _sync_extras(T, ph, hist, sol)
             return
         born = np.zeros_like(mask_full, dtype=bool)
         born[:, :, ks:ke + 1] = mask_full[:, :, ks:ke + 1]
@@ -240,14 +258,17 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         if what == 'advance':
             if n_active > 0:                           # no ADI steps while nothing is active (:524)
                 advance(arg)
-            elif hist is not None:
-                hist.t = hist.t + arg                  # (the global time moves on all the same)
+            else:
+                for x in (hist, sol):
+                    if x is not None:
+                        x.t = x.t + arg                # (the global time moves on all the same)
         elif what == 'birth':
             birth(*layers[arg])
         elif on_frame is not None:
             on_frame(arg, np.asarray(T), d_act.cpu().contiguous().numpy().astype(bool) if dev_loop else mask_act.copy())
     res = (np.asarray(T), nsteps) + (() if ph is None else (np.asarray(ph.liquid_fraction),))
-    return res if hist is None else res + (history_result(hist),)
+    res = res if hist is None else res + (history_result(hist),)
+    return res if sol is None else res + (solidification_result(sol),)
 
 
 def track_source(heat_source, track_box, dx, yi, t_step):
@@ -263,7 +284,7 @@ def track_source(heat_source, track_box, dx, yi, t_step):
 
 def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_track, theta, dt, t_step,
                      device_resident=True, heat_source=None, surface_loss=None, phase_change=None, history=None,
-                     material_law=None):
+                     material_law=None, solidification=None):
     """single_track_on_plate.py:150-177: the deposit advances one column per t_step along axis 1; packs are
     rebuilt after every column.  track_box = (x0, x1, z0, z1, n_columns).
     heat_source (a GoldakSource of the backend): the arc / laser as a moving volumetric source (track_source) during the
@@ -282,15 +303,19 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     material_law (a MaterialLaw of the backend): temperature-dependent k(T) and cp(T), with the law's latent heat; one
     NonlinearPacks lives through the run and is rebuilt after every column.  rho comes from mat_args, whose cp and k are not
     used; the scalar `h` becomes SurfaceLoss(h=h) unless surface_loss is given; device loop only; not together with
-    phase_change (ValueError).  None: the loop without it, unchanged."""
+    phase_change (ValueError).  None: the loop without it, unchanged.
+    solidification (T_freeze, a number): the conditions at the freezing front; one SolidificationRecord of the backend lives
+    through the run on the global time like the history, and sync_mask(T) follows every column; device loop only; the track
+    box must not overlap the plate either.  The return value gains a last element (after history's), the dict of
+    solidification_result.  None: the loop without it, unchanged."""
     x0, x1, z0, z1, ncol = track_box
     if material_law is not None and phase_change is not None:
         raise ValueError("run_single_track: phase_change cannot be combined with material_law (the MaterialLaw carries the "
                          "latent heat)")
-    if history is not None and np.asarray(plate_mask)[x0:x1, :ncol, z0:z1].any():
+    if (history is not None or solidification is not None) and np.asarray(plate_mask)[x0:x1, :ncol, z0:z1].any():
         n = int(np.asarray(plate_mask)[x0:x1, :ncol, z0:z1].sum())
         raise ValueError("run_single_track: the track box [%d:%d, 0:%d, %d:%d] overlaps the plate in %d cells; T_track is written "
-                         "onto those live cells without a seed, so the history recorder would miss it (a peak below the field, "
+                         "onto those live cells without a seed, so the history / solidification recorder would miss it (a peak below the field, "
                          "crossings skipped)" % (x0, x1, ncol, z0, z1, n))
     nx, ny, nz = plate_mask.shape
     mask = plate_mask.copy()
@@ -303,7 +328,7 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     robin = {f: h for f in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')}
     dev_loop = device_resident and hasattr(grid, 'set_mask_device') and hasattr(T, 'fill_where')
     _require_device_loop('run_single_track', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
-                         history=history, material_law=material_law)
+                         history=history, material_law=material_law, solidification=solidification)
     if dev_loop:                                    # the mask lives in HBM: a new column is two slice assignments
         import torch
         d_mask = grid.layout.to_layout(mask, torch.uint8)
@@ -317,7 +342,8 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     hist = None
     if history is not None:
         hist = backend.ThermalHistory(grid, history, capacity=ncol * max(1, int(math.ceil(t_step / dt))), T=T)
-    kw = _extras_kw(lpacks, ph, hist, nm)
+    sol = backend.SolidificationRecord(grid, solidification, T=T) if solidification is not None else None
+    kw = _extras_kw(lpacks, ph, hist, nm, sol)
     for yi in range(ncol):
         if dev_loop:
             d_mask[x0:x1, yi:yi + 1, z0:z1] = 1
@@ -330,7 +356,7 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         T[x0:x1, yi:yi + 1, z0:z1] = T_track
         if lpacks is not None or nm is not None:
             packs = (nm or lpacks).rebuild(T)        # the column changed the exposure: every cell, stale ones zeroed
-        _sync_extras(T, ph, hist)
+        _sync_extras(T, ph, hist, sol)
         n_sub = max(1, int(math.ceil(t_step / dt)))
         dt_orig = params.dt
         params.dt = t_step / n_sub
@@ -351,7 +377,9 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         params.dt = dt_orig
     res = (np.asarray(T),) + (() if ph is None else (np.asarray(ph.liquid_fraction),))
     if hist is not None:
-        return res + (history_result(hist),)
+        res = res + (history_result(hist),)
+    if sol is not None:
+        res = res + (solidification_result(sol),)
     return res if len(res) > 1 else res[0]
 
 

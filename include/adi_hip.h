@@ -881,6 +881,42 @@ int adi_history_seed(const double *d_T, double *d_peak, double *d_t_hi, double *
 int adi_history_reset_log(void *d_block, int32_t *d_log, long capacity, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Solidification record of the Cartesian step (no counterpart in the reference; like the thermal history, rules applied to
+ * the pair of fields around one of its steps).  State per cell (fp64, box layout, NaN off the mask and where the cell never
+ * froze), taken at the moment the cell last froze: the crossing time t_solid, the cooling rate and the SQUARE of the thermal
+ * gradient, g2 = |grad T|^2 -- every stored number comes from + - * / alone; the square root is the caller's.  For a step
+ * A (the field at t_n) -> B (the step's final result at t_n + dt), an in-mask cell freezes exactly when
+ * A > T_freeze and B <= T_freeze, and then
+ *     den = A - B;  num = A - T_freeze;  fr = num / den;  off = dt * fr;  t_solid = t_n + off
+ *     cooling_rate = den / dt
+ *     per axis a, for F in (A, B), with lo / hi = the minus / plus neighbour along a is in the mask (bits 1 + 2a / 2 + 2a
+ *     of the cell's flags byte; a box face counts as absent):
+ *         both:     d = F[+1] - F[-1];  g = d / (2.0*dx)          hi only:  d = F[+1] - F[0];  g = d / dx
+ *         lo only:  d = F[0] - F[-1];   g = d / dx                neither:  g = 0.0
+ *       dg = gB - gA;  sg = fr * dg;  g_a = gA + sg               (the gradient at the crossing time)
+ *     xx = gx*gx;  yy = gy*gy;  zz = gz*gz;  s = xx + yy;  g2 = s + zz
+ * every operation IEEE fp64 in this order, no contraction; 2.0*dx is formed once on the host.  A cell that does not freeze in
+ * the step is not written; a cell that freezes again is overwritten.  Off-mask cells are never written by the record.
+ * One workgroup owns a 16 x 16 x 16 brick (the bricks of adi_build_flag_bricks) and its word of d_hot (nbx*nby*nbz 32-bit
+ * words, brick (bi, bj, bk) at (bi*nby + bj)*nbz + bk): "some in-mask B of the brick is above T_freeze", rewritten by every
+ * record.  A is loaded only in bricks whose word from the previous record is set.  Precondition, under which that skip is
+ * exact: this step's A is the previous record's B on the mask (the recorder follows every step, and adi_solid_seed follows
+ * every outside edit of T).  The clock is a block of the thermal history's layout (ADI_HISTORY_BLOCK_BYTES), driven by
+ * adi_history_set_clock and adi_history_tick; the record reads it through the pointer.  T_freeze and dx travel by value.
+ * Valid: finite T_freeze, dx > 0, no state array aliasing a field or another state array.  Everything else is ADI_ERR_ARG,
+ * checked before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+int adi_solid_record(double T_freeze, double dx, const void *d_block, const double *d_T_in, const double *d_T_out,
+                     double *d_t_solid, double *d_rate, double *d_g2, uint32_t *d_hot, const uint8_t *d_flags,
+                     const uint32_t *d_bricks, int nx, int ny, int nz, long plane_stride, void *stream);
+/* all three fields NaN on the in-mask cells d_sel selects (uint8, box layout; NULL: every in-mask cell) and off the mask;
+ * in-mask cells not selected keep their state.  The word of a brick is set where a seeded in-mask cell of it has
+ * T > T_freeze; a word that is set stays set (zero d_hot once, before the first seed). */
+int adi_solid_seed(double T_freeze, const double *d_T, double *d_t_solid, double *d_rate, double *d_g2, uint32_t *d_hot,
+                   const uint8_t *d_flags, const uint32_t *d_bricks, const uint8_t *d_sel, int nx, int ny, int nz,
+                   long plane_stride, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Moving heat source of the cylindrical step.  For a step t_n -> t_n + dt:
  *     R0 = Tn + dt * q(x_c, t_n + dt/2) / (rho*cp)
  * and the three sweeps run unchanged.  Cell centres r_i = r_in + (i+1/2) dr, phi_j = (j+1/2) dphi, z_k = (k+1/2) dz (z from
