@@ -131,12 +131,10 @@ def cells(c):
     return mask, dirc
 
 
-@functools.lru_cache(maxsize=None)
-def dt_reference(key):
-    """cart_ref_ld after one step, computed once per session and kept on the in-mask cells only (off the mask the step
-    leaves T0): (longdouble values W[mask], inc, max|W|); read-only"""
+def reference_of(c):
+    """cart_ref_ld after the steps of the case dict c, kept on the in-mask cells only (off the mask the step leaves T0):
+    (longdouble values W[mask], inc, max|W|); read-only.  (tests/slab_dt_cases.py measures the slab-decomposed step with it.)"""
     from helpers import run_cart_case
-    c = case(key)
     W = run_cart_case(cart_ref_ld, c)['T_final']
     mask, dirc = cells(c)
     assert W.dtype == np.longdouble and np.array_equal(W[~mask].astype(np.float64), c['T0'][~mask])
@@ -146,27 +144,41 @@ def dt_reference(key):
     return Wm, inc, float(np.max(np.abs(Wm)))
 
 
-def figures(X, key):
-    """abs_err, inc, max|W| of a float64 result X, and abs_err in units of eps64 max|W| ('ulp') and of inc"""
-    Wm, inc, wmax = dt_reference(key)
+@functools.lru_cache(maxsize=None)
+def dt_reference(key):
+    """reference_of the case of `key`, computed once per session"""
+    return reference_of(case(key))
+
+
+def figures_of(X, c, ref):
+    """abs_err, inc, max|W| of a float64 result X of the case dict c against ref = reference_of(...), and abs_err in units of
+    eps64 max|W| ('ulp') and of inc"""
+    Wm, inc, wmax = ref
     X = np.asarray(X)
     assert X.dtype == np.float64
-    err = float(np.max(np.abs(X[case(key)['mask']] - Wm)))
+    err = float(np.max(np.abs(X[c['mask']] - Wm)))
     return dict(abs_err=err, inc=inc, wmax=wmax, ulp=err / (EPS64 * wmax), of_inc=err / inc)
+
+
+def figures(X, key):
+    return figures_of(X, case(key), dt_reference(key))
 
 
 def bar(fig, a):
     return a * EPS64 * fig['wmax'] + 1e-10 * fig['inc']
 
 
-def untouched_cells_are_exact(X, key):
+def untouched_exact(X, c):
     """off-mask cells bit-equal to T0, Dirichlet cells bit-equal to dir_value"""
-    c = case(key)
     mask, dirc = cells(c)
     ok = np.array_equal(X[~mask], c['T0'][~mask])
     if dirc.any():
         ok = ok and np.array_equal(X[dirc], np.broadcast_to(c['dir_value'], X.shape)[dirc])
     return ok
+
+
+def untouched_cells_are_exact(X, key):
+    return untouched_exact(X, case(key))
 
 
 # ---- the cylinder: the same metric on the sweep of cyl_switch_cases.dt_params (two steps) ----------------------------------

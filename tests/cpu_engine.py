@@ -286,6 +286,9 @@ class CpuEngine:
             if xhi is not None:
                 dd[-1] -= c[l, -1] * float(xhi[l])
             x[l] = np.linalg.solve(_dense(a[l], b[l], c[l]), dd)
+            # identity rows (off-mask and Dirichlet cells) are x = d exactly; pivoting in the dense solve may round them
+            ident = (a[l] == 0.0) & (c[l] == 0.0) & (b[l] == 1.0)
+            x[l][ident] = dd[ident]
         t_out.copy_(torch.from_numpy(np.moveaxis(x.reshape(shp), -1, axis).copy()))
 
     def condense(self, axis, variant, Li, t_in, flags, pack, theta, gam, dt, Tinf, cond):

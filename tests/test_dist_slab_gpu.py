@@ -1,7 +1,5 @@
 """GPU: the slab decomposition with the HIP engine, several ranks inside one process on one GPU
 (dist_slab.LocalComm, one thread per rank), against the single-domain HIP step and the oracle."""
-import threading
-
 import numpy as np
 import pytest
 
@@ -12,62 +10,14 @@ pytestmark = pytest.mark.gpu
 
 
 def _run_slabs(c, world, sizes, nsteps, opts=None, modes=None):
-    import torch
-    from adi_thermal_fields_amd import dist_slab
+    """nsteps of case c on `world` in-process ranks with the HIP engine (the runner: slab_dt_cases.run_slabs) -> assembled field"""
     import adi_thermal_fields_amd.adi3d_hip_coeff as hip
-    comms = dist_slab.LocalComm.make(world)
-    out = [None] * world
-    errs = []
-
-    def work(rank):
-        try:
-            torch.cuda.set_device(0)
-            i0 = sum(sizes[:rank]); i1 = i0 + sizes[rank]
-
-            def loc(a):
-                return a if (a is None or np.isscalar(a)) else np.asarray(a)[i0:i1]
-            neumann = None if c['neumann'] is None else {f: loc(v) for f, v in c['neumann'].items()}
-            robin_h = {f: loc(v) for f, v in c['robin_h'].items()} if isinstance(c['robin_h'], dict) else loc(c['robin_h'])
-            o = opts or {}
-            engine = dist_slab.HipEngine()
-            if o.get('no_pad'):                        # the caller's planes as they are (ragged lines on the GENERAL kernels)
-                engine.plane_dims = lambda ny, nz: (ny, nz)
-            st = dist_slab.SlabStepper(c['mask'][i0:i1], c['dx'], hip.Material(**c['mat']),
-                                       hip.Params(c['dt'], c['theta']), c['Tinf'], dir_mask=loc(c['dir_mask']),
-                                       dir_value=loc(c['dir_value']), neumann=neumann, robin_h=robin_h,
-                                       comm=comms[rank], engine=engine)
-            st._force_exact = bool(o.get('force_exact', False))
-            st._allow_window = bool(o.get('allow_window', True))
-            st._allow_fused = bool(o.get('allow_fused', True))
-            st._allow_dots = bool(o.get('allow_dots', True))
-            st._keep_r0 = bool(o.get('keep_r0', True))
-            st._allow_deferred = bool(o.get('allow_deferred', True))
-            st._allow_deferred_exact = bool(o.get('allow_deferred_exact', True))
-            # (off unless a test asks for it: most cases here were written for the two-pass forms it would otherwise replace)
-            st._allow_deferred_lines = bool(o.get('allow_deferred_lines', False))
-            # (solids riddled with voids: every line is flagged -- the sparse pass at its fullest; the product's cost rule would
-            # leave them to the window form unless a case asks for the rule with 'cost_rule')
-            st._deferred_lines_cost_ratio = 1.0 if o.get('cost_rule') else float('inf')
-            if 'dots_max' in o:
-                st.DOTS_MAX_NONUNIFORM = o['dots_max']
-            T = hip.to_device(np.ascontiguousarray(c['T0'][i0:i1]))
-            for s in range(nsteps):
-                T = st.step(T, prefetch_halo=bool(o.get('prefetch', False)) and s + 1 < nsteps)
-            out[rank] = T.get()
-            if modes is not None:
-                modes.add(st.axis0_mode)
-        except Exception as e:   # surface the failure and release the other ranks
-            errs.append(e)
-            comms[rank].sh.barrier.abort()
-
-    ths = [threading.Thread(target=work, args=(r,)) for r in range(world)]
-    for t in ths:
-        t.start()
-    for t in ths:
-        t.join(timeout=120)
-    if errs:
-        raise errs[0]
-    return np.concatenate(out, axis=0)
+    import slab_dt_cases as sd
+    assert world == len(sizes)
+    run = sd.run_slabs(sd.hip_engine, hip, c, sizes, opts, nsteps=nsteps)
+    if modes is not None:
+        modes |= run.modes
+    return run.T
 
 
 # pass-A forms: dot products inside the explicit stage (default), fused strided pass A (with / without R0 kept for
