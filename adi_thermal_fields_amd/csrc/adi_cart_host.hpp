@@ -1,13 +1,66 @@
 // adi_cart_host.hpp -- host-side planning shared by the Cartesian translation units of libadi_hip.so: line geometry of
-// a sweep, the tiling of the strided kernels, and the launchers each translation unit exports to the C-ABI layer
-// (adi_cart_api.hip).  The tiling constants are the measured optima of round 1; the run-time
+// a sweep, the tiling of the strided kernels, the rows per thread each sweep unit instantiates with the helpers that dispatch
+// over them, the call records the sweep launchers pass on, and the launchers each translation unit exports to the C-ABI
+// layer (adi_cart_api.hip).  The tiling constants are the measured optima of round 1; the run-time
 // tuning knobs they were swept with are gone.
 #pragma once
 #include <math.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "adi_cart_dev.hpp"
 
 namespace adi {
+
+// ---- run-time choice of a compiled build --------------------------------------------------------------------------
+// Each helper hands the chosen template arguments to a generic callable as std::integral_constant objects.
+template <class F>
+inline auto by_bool(bool b, F fn)
+{
+    if (b) return fn(std::true_type());
+    return fn(std::false_type());
+}
+// the four sweep variants: fn(HAS_DIR, HAS_Q)
+template <class F>
+inline auto by_variant(bool has_dir, bool has_q, F fn)
+{
+    return by_bool(has_dir, [&](auto dir) { return by_bool(has_q, [&](auto q) { return fn(dir, q); }); });
+}
+// rows per thread out of a compile-time list: fn(M).  A count that is not in the list takes the last entry.
+template <class F, int M0, int... Ms>
+inline auto by_rows(std::integer_sequence<int, M0, Ms...>, int m, F fn)
+{
+    if constexpr (sizeof...(Ms) != 0) {
+        if (m != M0) return by_rows(std::integer_sequence<int, Ms...>(), m, fn);
+    }
+    return fn(std::integral_constant<int, M0>());
+}
+template <int... Ms>
+constexpr bool in_rows(std::integer_sequence<int, Ms...>, int m) { return ((m == Ms) || ...); }
+// the first entry of a list that pred(M) accepts; 0: none
+template <class P, int... Ms>
+constexpr int find_rows(std::integer_sequence<int, Ms...>, P pred)
+{
+    int found = 0;
+    ((found = (found == 0 && pred(Ms)) ? Ms : found), ...);
+    return found;
+}
+
+// Rows per thread of the strided kernels, each group named once: the planner (strided_plan) offers a group's counts, the
+// front dispatcher (adi_sweep_strided.hip) picks the translation unit by membership and the unit its instantiation from the
+// same list.  The last entry of a list is what its ladder's final `else` was.
+using RowsGeneral = std::integer_sequence<int, 2, 4, 8, 16>;      // GENERAL kernel (strided_rows_per_thread)
+using RowsGeneralBuilt = std::integer_sequence<int, 8, 16>;      // ... those with FCM / CORR compiled in or out (_gc, _gk)
+using RowsFast = std::integer_sequence<int, 32, 16, 8>;          // FAST kernel: adi_sweep_strided.hip, FC builds in _fc
+using RowsFastX = std::integer_sequence<int, 20, 24, 28>;        // exact fits, adi_sweep_strided_x.hip
+using RowsFastY = std::integer_sequence<int, 18, 22, 26, 30>;    // exact fits, adi_sweep_strided_y.hip
+using RowsFusedX = std::integer_sequence<int, 10, 12, 14>;       // exact fits of the fused kernel, adi_sweep_strided_fx.hip
+using RowsFusedY = std::integer_sequence<int, 9, 11, 13, 15>;    // ... adi_sweep_strided_fy.hip
+constexpr int kFuseMaxRows = 16;                                 // the fused FAST kernel holds at most 16 rows per thread
+// rows per lane of the contiguous kernels
+using RowsContig = std::integer_sequence<int, 2, 4, 8, 16>;      // GENERAL and FAST kernels, adi_sweep_contig.hip
+using RowsContigX = std::integer_sequence<int, 20, 24, 28>;      // exact fits of the FAST kernel, adi_sweep_contig_x.hip
 
 inline LineGeom line_geom(int axis, const Lay &L, long *inner_stride)
 {
@@ -67,17 +120,16 @@ inline StridedPlan strided_plan(const LineGeom &g, bool want_fast, bool wide_ok,
         // exact fits first: 20 / 24 / 28 rows per thread where they cut the line into exactly 16 or 32 segments (n = 320, 384,
         // 448, 640, 768, 896) -- with 16 or 32 rows those lines fill 20 - 28 of 32 segment slots of every workgroup
         int exact = 0;
+        const auto fits = [n](int m) { return n % m == 0 && (n / m == 16 || n / m == 32); };
         // (late round 3: 18 / 22 / 26 / 30 rows too -- 288, 352, 416, 480 and 576 ... 960 rows; adi_sweep_strided_y.hip)
         if (!fused && !wide_ok && n >= 288 && !(n % 16 == 0 && ((n / 16) & (n / 16 - 1)) == 0))
-            for (int m = 18; m <= 30 && !exact; m += 2)
-                if (n % m == 0 && (n / m == 16 || n / m == 32)) exact = m;
+            if (!(exact = find_rows(RowsFastX(), fits))) exact = find_rows(RowsFastY(), fits);   // (no line fits two counts)
         // ... and for the fused explicit + sweep kernel, which holds at most 16 rows per thread, 10 / 12 / 14 rows where they cut
         // the line into exactly 16 or 32 segments (n = 160, 192, 224, 320, 384, 448; adi_sweep_strided_fx.hip, round 3)
         // (... and 9 / 11 / 13 / 15 rows: 144, 176, 208, 240 and 288, 352, 416, 480; adi_sweep_strided_fy.hip -- every multiple of 16
         // up to 256 rows and of 32 up to 512 is an exact fit, which is what the padded extents round ragged lines up to)
         if (fused && fused_exact && n >= 144 && !(n % 16 == 0 && ((n / 16) & (n / 16 - 1)) == 0))
-            for (int m = 9; m <= 15 && !exact; ++m)
-                if (n % m == 0 && (n / m == 16 || n / m == 32)) exact = m;
+            if (!(exact = find_rows(RowsFusedX(), fits))) exact = find_rows(RowsFusedY(), fits);
         if (exact) { mf = exact; lf = 16; }
         else if (wide_ok && n % 16 == 0 && (n / 16 == 8 || n / 16 == 16 || n / 16 == 32)) { mf = n / 16; lf = 32; }   // Lpf = 16
         else if (n >= 512 && n % 32 == 0 && n / 32 <= 32 && !fused && g.stride <= 131072) {
@@ -123,7 +175,7 @@ inline StridedPlan strided_plan(const LineGeom &g, bool want_fast, bool wide_ok,
 // the fused FAST kernels shuffle k-neighbours inside 16-lane DPP rows: 16 lines per tile, at most 16 rows per thread
 inline bool fuse_fast_ok(const StridedPlan &P, const Lay &L, const Fuse &fz)
 {
-    return P.Mf != 0 && P.lines_f == 16 && P.Mf <= 16 && L.nz % 16 == 0 && fz.wbytes != 0;
+    return P.Mf != 0 && P.lines_f == 16 && P.Mf <= kFuseMaxRows && L.nz % 16 == 0 && fz.wbytes != 0;
 }
 
 inline void fuse_tile_order(Fuse &fz, const StridedPlan &P, const Lay &L)
@@ -157,9 +209,9 @@ inline int make_lay(int nx, int ny, int nz, long plane_stride, Lay *L)
 inline int contig_fast_rows(int n, int m_general)
 {
     const auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    const auto fits = [&](int m) { return n % m == 0 && pow2(n / m) && n / m >= 8 && n / m <= 64; };
     if (n >= 256 && !(n % 16 == 0 && pow2(n / 16)))
-        for (int m = 20; m <= 28; m += 4)
-            if (n % m == 0 && pow2(n / m) && n / m >= 8 && n / m <= 64) return m;
+        if (const int m = find_rows(RowsContigX(), fits)) return m;
     if (n >= 128 && n % 16 == 0 && n / 16 <= 64) return 16;
     if (n >= 64 && n % 8 == 0 && n / 8 <= 64 && m_general < 8) return 8;
     return m_general;
@@ -252,6 +304,29 @@ struct SweepArgs {
     const uint8_t *dmask;
     const double *dval;
     const double *qf;
+};
+// What a launch of the strided family needs besides its StridedPlan.  A host-side record: it is never passed to a kernel,
+// and only the hipLaunchKernelGGL calls spell its members out.
+struct StridedCall {
+    SweepArgs a;
+    double *out;
+    LineGeom g;
+    const double *xlo, *xhi;
+    SweepScal s;
+    unsigned *queue;     // unit queue of a FAST kernel (null: none -- the GENERAL kernel takes every tile)
+    hipStream_t st;
+    Fuse fz;
+};
+// ... and of the contiguous family
+struct ContigCall {
+    SweepArgs a;
+    double *out;
+    Lay L;
+    SweepScal s;
+    bool vec;            // arrays and plane stride allow 16-byte accesses (for kernels whose rows per lane divide the line)
+    long nunits_f;       // wave-units of the FAST kernel
+    unsigned *queue;
+    hipStream_t st;
 };
 // adi_sweep_contig.hip: memory axis 2
 void contig_sweep(bool has_dir, bool has_q, const SweepArgs &a, const Lay &L, const SweepScal &s, double *out, void *work,

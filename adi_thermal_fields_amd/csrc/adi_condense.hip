@@ -339,17 +339,12 @@ __global__ __launch_bounds__(256) void k_dots_finish(const double *__restrict__ 
 // ------------------------------------------------------------------------------------------------
 // host-side launch logic
 // ------------------------------------------------------------------------------------------------
-// The four builds of a pass-A body, chosen in one place: fn(HAS_DIR, HAS_Q as std::bool_constant, the arrays) with the arrays
-// the build does not read set to null.
-template <class F>
-static int by_variant(bool has_dir, bool has_q, SweepArgs a, F fn)
+// Pass A hands its kernels null for the arrays their build (by_variant, adi_cart_host.hpp) does not read.
+static SweepArgs read_arrays(bool has_dir, bool has_q, SweepArgs a)
 {
     if (!has_dir) { a.dmask = nullptr; a.dval = nullptr; }
     if (!has_q) a.qf = nullptr;
-    if (has_dir && has_q) return fn(std::true_type(), std::true_type(), a);
-    if (has_q) return fn(std::false_type(), std::true_type(), a);
-    if (has_dir) return fn(std::true_type(), std::false_type(), a);
-    return fn(std::false_type(), std::false_type(), a);
+    return a;
 }
 
 template <int MF, bool HAS_DIR, bool HAS_Q, bool FUSE>
@@ -439,8 +434,9 @@ static int condense_dispatch(int axis, const SweepArgs &a, const Lay &L, SweepSc
 int condense_sweep(bool has_dir, bool has_q, int axis, const SweepArgs &a, const Lay &L, const SweepScal &s, double *cond,
                    void *work, size_t work_bytes, hipStream_t st, const Fuse *fz)
 {
-    return by_variant(has_dir, has_q, a, [&](auto dir, auto q, const SweepArgs &v) {
-        return condense_dispatch<decltype(dir)::value, decltype(q)::value>(axis, v, L, s, cond, work, work_bytes, st, fz);
+    const SweepArgs v = read_arrays(has_dir, has_q, a);
+    return by_variant(has_dir, has_q, [&](auto dir, auto q) {
+        return condense_dispatch<dir.value, q.value>(axis, v, L, s, cond, work, work_bytes, st, fz);
     });
 }
 
@@ -491,11 +487,9 @@ int adi_axis0_dots_finish(int variant, const double *d_part, const double *d_wei
     // the lines that are not uniform: the serial two-recurrence condensation from the stored R0
     long inner_stride;
     const LineGeom g = line_geom(0, L, &inner_stride);
-    const SweepArgs a = {d_R0, d_flags, d_coeff, d_dir_mask, d_dir_val, d_qflux};
-    by_variant(has_dir, has_q, a, [&](auto dir, auto q, const SweepArgs &v) {
-        launch_condense_generic<decltype(dir)::value, decltype(q)::value>(v, d_cond, nlines, g, inner_stride, s, d_list, line_begin,
-                                                                          nsel, st);
-        return ADI_OK;
+    const SweepArgs v = read_arrays(has_dir, has_q, {d_R0, d_flags, d_coeff, d_dir_mask, d_dir_val, d_qflux});
+    by_variant(has_dir, has_q, [&](auto dir, auto q) {
+        launch_condense_generic<dir.value, q.value>(v, d_cond, nlines, g, inner_stride, s, d_list, line_begin, nsel, st);
     });
     ADI_CHECK_LAUNCH();
     return ADI_OK;

@@ -1,6 +1,7 @@
-// adi_contig_dev.hpp -- device code shared by the translation units of the contiguous-axis sweep (adi_sweep_contig.hip: the
-// GENERAL kernel and the FAST kernel with 2 / 4 / 8 / 16 rows per lane; adi_sweep_contig_x.hip: the FAST kernel with 20 / 24 /
-// 28 rows per lane for lines those row counts cut into a power-of-two number of segments).
+// adi_contig_dev.hpp -- device code and the FAST kernel's launcher shared by the translation units of the contiguous-axis
+// sweep (adi_sweep_contig.hip: the GENERAL kernel and the FAST kernel with RowsContig = 2 / 4 / 8 / 16 rows per lane;
+// adi_sweep_contig_x.hip: the FAST kernel with RowsContigX = 20 / 24 / 28 rows per lane for lines those row counts cut into a
+// power-of-two number of segments; the lists are in adi_cart_host.hpp).
 #pragma once
 #include "adi_cart_host.hpp"
 
@@ -218,14 +219,13 @@ __global__ __launch_bounds__(256) void k_sweep_contig_fast(
 
 
 template <int MF, bool HAS_DIR, bool HAS_Q>
-inline void launch_contig_fast(const double *in, const uint8_t *flags, const double *coeff, const uint8_t *dmask,
-                               const double *dval, const double *qf, double *out, const Lay &L, SweepScal s, bool vec,
-                               long nunits_f, unsigned *queue, hipStream_t st)
+inline void launch_contig_fast(const ContigCall &c)
 {
+    const Lay &L = c.L;
     const int Lpf = next_pow2(L.nz / MF);
-    const unsigned grid = (unsigned)((nunits_f + 3) / 4);
-    const UniC<MF> U = make_unic<MF>(s.tg);
+    const unsigned grid = (unsigned)((c.nunits_f + 3) / 4);
     const int lwf = 64 / Lpf;
+    const bool vec = c.vec && (L.nz % MF == 0);
     // coalesced + LDS-transposed access: whole units of contiguous lines (full last unit, no plane straddling)
     const bool coal = vec && MF >= 4 && Lpf * MF == L.nz && (L.ny % lwf == 0) &&
                       (((long)L.nx * L.ny) % lwf == 0);
@@ -235,26 +235,21 @@ inline void launch_contig_fast(const double *in, const uint8_t *flags, const dou
     // kernel is bound by the serial work of those lanes, not by its loads, and the extra index arithmetic of this mode costs
     // more than the coalescing gains (256 x 256 x 257 on a 272-row box: 170 Gcell/s with lane-owned chunks, 148 with this mode;
     // solid 256 x 256 x 496: 227 -> 283).
-    const bool coal_r = s.box != 0 && vec && MF == 16 && L.nz % MF == 0 && Lpf * MF != L.nz && (L.ny % lwf == 0) &&
+    const bool coal_r = c.s.box != 0 && vec && MF == 16 && L.nz % MF == 0 && Lpf * MF != L.nz && (L.ny % lwf == 0) &&
                         (((long)L.nx * L.ny) % lwf == 0);
-    if (coal)
-        hipLaunchKernelGGL((k_sweep_contig_fast<(MF >= 4 ? MF : 4), 2, HAS_DIR, HAS_Q>), dim3(grid), dim3(256), 0, st, in, flags, coeff,
-                           dmask, dval, qf, out, L, Lpf, s, nunits_f, queue, make_unic<(MF >= 4 ? MF : 4)>(s.tg));
+    const auto launch = [&](auto kernel, auto U) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, c.st, c.a.in, c.a.flags, c.a.coeff, c.a.dmask, c.a.dval, c.a.qf,
+                           c.out, L, Lpf, c.s, c.nunits_f, c.queue, U);
+    };
+    constexpr int MC = MF >= 4 ? MF : 4;               // (the coalesced mode moves at least 4 rows per lane)
+    if (coal) launch(k_sweep_contig_fast<MC, 2, HAS_DIR, HAS_Q>, make_unic<MC>(c.s.tg));
     else if (coal_r) {
-        if constexpr (MF == 16)
-            hipLaunchKernelGGL((k_sweep_contig_fast<16, 3, HAS_DIR, HAS_Q>), dim3(grid), dim3(256), 0, st, in, flags, coeff,
-                               dmask, dval, qf, out, L, Lpf, s, nunits_f, queue, U);
-    } else if (vec)
-        hipLaunchKernelGGL((k_sweep_contig_fast<MF, 1, HAS_DIR, HAS_Q>), dim3(grid), dim3(256), 0, st, in, flags, coeff,
-                           dmask, dval, qf, out, L, Lpf, s, nunits_f, queue, U);
-    else
-        hipLaunchKernelGGL((k_sweep_contig_fast<MF, 0, HAS_DIR, HAS_Q>), dim3(grid), dim3(256), 0, st, in, flags,
-                           coeff, dmask, dval, qf, out, L, Lpf, s, nunits_f, queue, U);
+        if constexpr (MF == 16) launch(k_sweep_contig_fast<16, 3, HAS_DIR, HAS_Q>, make_unic<16>(c.s.tg));
+    } else if (vec) launch(k_sweep_contig_fast<MF, 1, HAS_DIR, HAS_Q>, make_unic<MF>(c.s.tg));
+    else launch(k_sweep_contig_fast<MF, 0, HAS_DIR, HAS_Q>, make_unic<MF>(c.s.tg));
 }
 
-// adi_sweep_contig_x.hip: launch_contig_fast<mf, ...> for mf = 20, 24, 28
-void contig_fast_exact(int mf, bool has_dir, bool has_q, const double *in, const uint8_t *flags, const double *coeff,
-                       const uint8_t *dmask, const double *dval, const double *qf, double *out, const Lay &L, SweepScal s,
-                       bool vec, long nunits_f, unsigned *queue, hipStream_t st);
+// adi_sweep_contig_x.hip: launch_contig_fast<mf, ...> for RowsContigX
+void contig_fast_exact(int mf, bool has_dir, bool has_q, const ContigCall &c);
 
 }  // namespace adi

@@ -1,6 +1,9 @@
-// adi_strided_fast.hpp -- the FAST kernel of the strided-axis sweeps and its launcher, shared by adi_sweep_strided.hip (8 / 16 /
-// 32 rows per thread, and the form with the explicit stage folded in) and adi_sweep_strided_x.hip (20 / 24 / 28 rows per thread
-// for lines those row counts cut into 16 or 32 segments).
+// adi_strided_fast.hpp -- the FAST kernel of the strided-axis sweeps and its launchers.  Which translation unit instantiates
+// which rows per thread (the lists are in adi_cart_host.hpp, next to the planner that offers them):
+//   adi_sweep_strided.hip      RowsFast (8 / 16 / 32), the explicit stage folded in up to 16 rows; the front dispatcher
+//   adi_sweep_strided_fc.hip   RowsFast with the coefficients taken from the flags (FC), no Dirichlet cells
+//   adi_sweep_strided_x.hip    RowsFastX (20 / 24 / 28), _y.hip RowsFastY (18 / 22 / 26 / 30): unfused exact fits
+//   adi_sweep_strided_fx.hip   RowsFusedX (10 / 12 / 14), _fy.hip RowsFusedY (9 / 11 / 13 / 15): fused exact fits
 #pragma once
 #include "adi_cart_host.hpp"
 #include "adi_strided_dev.hpp"
@@ -139,56 +142,63 @@ __global__ __launch_bounds__(512, FUSE ? ADI_FUSE_OCC : 1) void k_sweep_strided_
     }
 }
 
+// All-solid box (the caller's hint): the build without surface-segment lanes (fused: no spills) -- up to 16 rows per thread.
 template <int MF, bool HAS_DIR, bool HAS_Q, bool FUSE, bool FC>
-inline void launch_strided_fast_t(const StridedPlan &P, const double *in, const uint8_t *flags, const double *coeff,
-                                  const uint8_t *dmask, const double *dval, const double *qf, double *out,
-                                  const LineGeom &g, const double *xlo, const double *xhi, SweepScal s, unsigned *queue,
-                                  hipStream_t st, const Fuse &fz)
+inline void launch_strided_fast_t(const StridedPlan &P, const StridedCall &c)
 {
-    if (s.box && MF <= 16) // all-solid box (caller's hint): the build without surface-segment lanes (fused: no spills)
-        hipLaunchKernelGGL((k_sweep_strided_fast<MF, HAS_DIR, HAS_Q, FUSE, (MF > 16), FC>), dim3((unsigned)P.ntiles_f),
-                           dim3(P.lines_f * P.Lpf), P.lds_f, st, in, flags, coeff, dmask, dval, qf, out, g, P.Lpf, P.lines_f,
-                           P.tiles_inner_f, P.ntiles_f, xlo, xhi, s, queue, make_unic<MF>(s.tg), fz);
-    else
-        hipLaunchKernelGGL((k_sweep_strided_fast<MF, HAS_DIR, HAS_Q, FUSE, true, FC>), dim3((unsigned)P.ntiles_f),
-                           dim3(P.lines_f * P.Lpf), P.lds_f, st, in, flags, coeff, dmask, dval, qf, out, g, P.Lpf, P.lines_f,
-                           P.tiles_inner_f, P.ntiles_f, xlo, xhi, s, queue, make_unic<MF>(s.tg), fz);
+    by_bool(c.s.box && MF <= 16, [&](auto box) {
+        constexpr bool MIXED = MF > 16 || !box.value;
+        hipLaunchKernelGGL((k_sweep_strided_fast<MF, HAS_DIR, HAS_Q, FUSE, MIXED, FC>), dim3((unsigned)P.ntiles_f),
+                           dim3(P.lines_f * P.Lpf), P.lds_f, c.st, c.a.in, c.a.flags, c.a.coeff, c.a.dmask, c.a.dval, c.a.qf,
+                           c.out, c.g, P.Lpf, P.lines_f, P.tiles_inner_f, P.ntiles_f, c.xlo, c.xhi, c.s, c.queue,
+                           make_unic<MF>(c.s.tg), c.fz);
+    });
 }
 
-// adi_sweep_strided_fc.hip: the FC = true instantiations (8 / 16 / 32 rows per thread, no Dirichlet cells, fused or not)
-void strided_fast_fc(int mf, bool has_q, bool fuse, const StridedPlan &P, const double *in, const uint8_t *flags,
-                     const double *coeff, const double *qf, double *out, const LineGeom &g, const double *xlo,
-                     const double *xhi, SweepScal s, unsigned *queue, hipStream_t st, const Fuse &fz);
+// The builds without Dirichlet cells (FC, fused exact fits) are handed null Dirichlet arrays, and a null flux array where
+// the variant has none.
+inline StridedCall without_dir(StridedCall c, bool has_q)
+{
+    c.a.dmask = nullptr; c.a.dval = nullptr;
+    if (!has_q) c.a.qf = nullptr;
+    return c;
+}
+
+// The satellite units.  Each instantiates the row counts of its list and nothing else.
+// adi_sweep_strided_fc.hip: FC = true for RowsFast (no Dirichlet cells, fused or not)
+void strided_fast_fc(int mf, bool has_q, bool fuse, const StridedPlan &P, const StridedCall &c);
+// adi_sweep_strided_fx.hip / _fy.hip: the fused kernel for RowsFusedX / RowsFusedY (no Dirichlet cells, FC or not)
+void strided_fast_fused_exact(int mf, bool has_q, const StridedPlan &P, const StridedCall &c);
+void strided_fast_fused_exact_odd(int mf, bool has_q, const StridedPlan &P, const StridedCall &c);
+// adi_sweep_strided_x.hip / _y.hip: launch_strided_fast<mf, ..., false> for RowsFastX / RowsFastY
+void strided_fast_exact(int mf, bool has_dir, bool has_q, const StridedPlan &P, const StridedCall &c);
+void strided_fast_exact2(int mf, bool has_dir, bool has_q, const StridedPlan &P, const StridedCall &c);
 
 template <int MF, bool HAS_DIR, bool HAS_Q, bool FUSE>
-inline void launch_strided_fast(const StridedPlan &P, const double *in, const uint8_t *flags, const double *coeff,
-                                const uint8_t *dmask, const double *dval, const double *qf, double *out,
-                                const LineGeom &g, const double *xlo, const double *xhi, SweepScal s, unsigned *queue,
-                                hipStream_t st, const Fuse &fz)
+inline void launch_strided_fast(const StridedPlan &P, const StridedCall &c)
 {
-    if (!HAS_DIR && s.fconst && (MF == 8 || MF == 16 || MF == 32))
-        strided_fast_fc(MF, HAS_Q, FUSE, P, in, flags, coeff, qf, out, g, xlo, xhi, s, queue, st, fz);
-    else
-        launch_strided_fast_t<MF, HAS_DIR, HAS_Q, FUSE, false>(P, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue,
-                                                               st, fz);
+    if (!HAS_DIR && c.s.fconst && in_rows(RowsFast(), MF)) strided_fast_fc(MF, HAS_Q, FUSE, P, c);
+    else launch_strided_fast_t<MF, HAS_DIR, HAS_Q, FUSE, false>(P, c);
 }
 
-// adi_sweep_strided_fx.hip: the fused kernel with 10 / 12 / 14 rows per thread (exact fits, no Dirichlet cells)
-void strided_fast_fused_exact(int mf, bool has_q, const StridedPlan &P, const double *in, const uint8_t *flags,
-                              const double *coeff, const double *qf, double *out, const LineGeom &g, const double *xlo,
-                              const double *xhi, SweepScal s, unsigned *queue, hipStream_t st, const Fuse &fz);
-void strided_fast_fused_exact_odd(int mf, bool has_q, const StridedPlan &P, const double *in, const uint8_t *flags,
-                              const double *coeff, const double *qf, double *out, const LineGeom &g, const double *xlo,
-                              const double *xhi, SweepScal s, unsigned *queue, hipStream_t st, const Fuse &fz);   // 9 / 11 / 13 / 15 rows (adi_sweep_strided_fy.hip)
-
-// adi_sweep_strided_x.hip: launch_strided_fast<mf, ..., false> for mf = 20, 24, 28
-void strided_fast_exact(int mf, bool has_dir, bool has_q, const StridedPlan &P, const double *in, const uint8_t *flags,
-                        const double *coeff, const uint8_t *dmask, const double *dval, const double *qf, double *out,
-                        const LineGeom &g, const double *xlo, const double *xhi, SweepScal s, unsigned *queue, hipStream_t st,
-                        const Fuse &fz);
-void strided_fast_exact2(int mf, bool has_dir, bool has_q, const StridedPlan &P, const double *in, const uint8_t *flags,
-                        const double *coeff, const uint8_t *dmask, const double *dval, const double *qf, double *out,
-                        const LineGeom &g, const double *xlo, const double *xhi, SweepScal s, unsigned *queue, hipStream_t st,
-                        const Fuse &fz);   // 18 / 22 / 26 / 30 rows (adi_sweep_strided_y.hip)
+// the fused exact fits of one list (the body of _fx and _fy)
+template <class Rows>
+inline void launch_strided_fused_exact(Rows rows, int mf, bool has_q, const StridedPlan &P, const StridedCall &c)
+{
+    const StridedCall v = without_dir(c, has_q);
+    by_rows(rows, mf, [&](auto m) {
+        by_bool(has_q, [&](auto q) {
+            by_bool(v.s.fconst != 0, [&](auto fc) { launch_strided_fast_t<m.value, false, q.value, true, fc.value>(P, v); });
+        });
+    });
+}
+// ... and the unfused ones (the body of _x and _y)
+template <class Rows>
+inline void launch_strided_exact(Rows rows, int mf, bool has_dir, bool has_q, const StridedPlan &P, const StridedCall &c)
+{
+    by_rows(rows, mf, [&](auto m) {
+        by_variant(has_dir, has_q, [&](auto dir, auto q) { launch_strided_fast<m.value, dir.value, q.value, false>(P, c); });
+    });
+}
 
 }  // namespace adi

@@ -158,50 +158,33 @@ __global__ __launch_bounds__(M <= 8 ? 1024 : 512, (M == 8 && WHOLE && !QUEUED) ?
 }
 
 
-// Launch of the GENERAL kernel on the tiles of plan P (queue == nullptr: every tile; else the units a FAST kernel queued).
+// Launch of the GENERAL kernel on the tiles of plan P (QUEUED: the units a FAST kernel queued; else every tile).
 template <int M, bool HAS_DIR, bool HAS_Q, bool FUSE, int FCM, bool CORR, bool QUEUED>
-inline void launch_strided_general_q(const StridedPlan &P, unsigned ggrid, const double *in, const uint8_t *flags,
-                                     const double *coeff, const uint8_t *dmask, const double *dval, const double *qf, double *out,
-                                     const LineGeom &g, const double *xlo, const double *xhi, const SweepScal &s,
-                                     const unsigned *queue, hipStream_t st, const Fuse &fz)
+inline void launch_strided_general_q(const StridedPlan &P, unsigned ggrid, const StridedCall &c)
 {
     // every tile whole and within 31-bit byte offsets of its base: the buffer-addressed instantiation (8 / 16 rows per thread)
-    if constexpr (!FUSE && M >= 8) {
-        const bool whole = kBufStrided && g.n_inner % P.lines_g == 0 && P.Lpg * M == g.n && (long)g.n * g.stride * 8 < 0x7fffffffL;
-        if (whole) {
-            hipLaunchKernelGGL((k_sweep_strided<M, HAS_DIR, HAS_Q, false, true, FCM, CORR, QUEUED>), dim3(ggrid),
-                               dim3(P.lines_g * P.Lpg), P.lds_g, st, in, flags, coeff, dmask, dval, qf, out, g, P.Lpg, P.lines_g,
-                               P.tiles_inner_g, P.ntiles_g, xlo, xhi, s, queue, P.ratio, P.tiles_inner_f, fz);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_sweep_strided<M, HAS_DIR, HAS_Q, FUSE, false, FCM, CORR, QUEUED>), dim3(ggrid), dim3(P.lines_g * P.Lpg),
-                       P.lds_g, st, in, flags, coeff, dmask, dval, qf, out, g, P.Lpg, P.lines_g, P.tiles_inner_g, P.ntiles_g, xlo,
-                       xhi, s, queue, P.ratio, P.tiles_inner_f, fz);
+    constexpr bool buf = !FUSE && M >= 8;
+    const LineGeom &g = c.g;
+    const bool whole = buf && kBufStrided && g.n_inner % P.lines_g == 0 && P.Lpg * M == g.n &&
+                       (long)g.n * g.stride * 8 < 0x7fffffffL;
+    by_bool(whole, [&](auto w) {
+        hipLaunchKernelGGL((k_sweep_strided<M, HAS_DIR, HAS_Q, FUSE, (buf && w.value), FCM, CORR, QUEUED>), dim3(ggrid),
+                           dim3(P.lines_g * P.Lpg), P.lds_g, c.st, c.a.in, c.a.flags, c.a.coeff, c.a.dmask, c.a.dval, c.a.qf,
+                           c.out, g, P.Lpg, P.lines_g, P.tiles_inner_g, P.ntiles_g, c.xlo, c.xhi, c.s, c.queue, P.ratio,
+                           P.tiles_inner_f, c.fz);
+    });
 }
 template <int M, bool HAS_DIR, bool HAS_Q, bool FUSE, int FCM, bool CORR>
-inline void launch_strided_general_t(const StridedPlan &P, unsigned ggrid, const double *in, const uint8_t *flags,
-                                     const double *coeff, const uint8_t *dmask, const double *dval, const double *qf, double *out,
-                                     const LineGeom &g, const double *xlo, const double *xhi, const SweepScal &s,
-                                     const unsigned *queue, hipStream_t st, const Fuse &fz)
+inline void launch_strided_general_t(const StridedPlan &P, unsigned ggrid, const StridedCall &c)
 {
-    if (queue != nullptr)
-        launch_strided_general_q<M, HAS_DIR, HAS_Q, FUSE, FCM, CORR, true>(P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi,
-                                                                           s, queue, st, fz);
-    else
-        launch_strided_general_q<M, HAS_DIR, HAS_Q, FUSE, FCM, CORR, false>(P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi,
-                                                                            s, queue, st, fz);
+    by_bool(c.queue != nullptr, [&](auto queued) {
+        launch_strided_general_q<M, HAS_DIR, HAS_Q, FUSE, FCM, CORR, queued.value>(P, ggrid, c);
+    });
 }
 
-// adi_sweep_strided_gc.hip: <FCM = 1, CORR = false> for 8 / 16 rows per thread (fused or not)
-void strided_general_fc(int m, bool has_dir, bool has_q, bool fuse, const StridedPlan &P, unsigned ggrid, const double *in,
-                        const uint8_t *flags, const double *coeff, const uint8_t *dmask, const double *dval, const double *qf,
-                        double *out, const LineGeom &g, const double *xlo, const double *xhi, const SweepScal &s,
-                        const unsigned *queue, hipStream_t st, const Fuse &fz);
-// adi_sweep_strided_gk.hip: <FCM = 0, CORR = true> for 8 / 16 rows per thread (adi_sweep_corrected: never fused)
-void strided_general_corr(int m, bool has_dir, bool has_q, const StridedPlan &P, unsigned ggrid, const double *in,
-                          const uint8_t *flags, const double *coeff, const uint8_t *dmask, const double *dval, const double *qf,
-                          double *out, const LineGeom &g, const double *xlo, const double *xhi, const SweepScal &s,
-                          const unsigned *queue, hipStream_t st, const Fuse &fz);
+// adi_sweep_strided_gc.hip: <FCM = 1, CORR = false> for RowsGeneralBuilt (fused or not)
+void strided_general_fc(int m, bool has_dir, bool has_q, bool fuse, const StridedPlan &P, unsigned ggrid, const StridedCall &c);
+// adi_sweep_strided_gk.hip: <FCM = 0, CORR = true> for RowsGeneralBuilt (adi_sweep_corrected: never fused)
+void strided_general_corr(int m, bool has_dir, bool has_q, const StridedPlan &P, unsigned ggrid, const StridedCall &c);
 
 }  // namespace adi

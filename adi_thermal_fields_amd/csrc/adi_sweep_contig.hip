@@ -122,20 +122,40 @@ __global__ __launch_bounds__(256) void k_sweep_contig(
 // ------------------------------------------------------------------------------------------------
 
 
+// GENERAL kernel on every unit, or (c.queue) on the units a FAST kernel of `ratio` times as many lines per wave queued
 template <int M, bool HAS_DIR, bool HAS_Q>
-static void launch_contig(const double *in, const uint8_t *flags, const double *coeff, const uint8_t *dmask,
-                          const double *dval, const double *qf, double *out, const Lay &L, SweepScal s,
-                          void *work, size_t work_bytes, hipStream_t st)
+static void launch_contig(const ContigCall &c, int ratio)
 {
+    const Lay &L = c.L;
     const int n = L.nz;
     const long nlines = (long)L.nx * L.ny;
     const int Lp = next_pow2((n + M - 1) / M);
     const int lw = 64 / Lp;
     const long nunits = (nlines + lw - 1) / lw;
     const unsigned grid = (unsigned)((nunits + 3) / 4);
-    const bool aligned = (((uintptr_t)in | (uintptr_t)coeff | (uintptr_t)out | (uintptr_t)dval | (uintptr_t)qf) & 15) == 0 &&
-                         (((uintptr_t)flags | (uintptr_t)dmask) & 7) == 0 && (L.sx % 8 == 0);
-    const bool vec = aligned && (n % M == 0);
+    const unsigned ggrid = (c.queue != nullptr && grid > 2048u) ? 2048u : grid;
+    const bool vec = c.vec && (n % M == 0);
+    // coalesced + LDS-transposed access with streaming loads/stores: 1.01 -> 0.92 ms on the dense general-pack sweep at
+    // 512^3 (with the default cache policy the transposition alone gained nothing)
+    const bool coal = vec && M >= 4 && Lp * M == n && (L.ny % lw == 0) && (nlines % lw == 0);
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(ggrid), dim3(256), 0, c.st, c.a.in, c.a.flags, c.a.coeff, c.a.dmask, c.a.dval, c.a.qf,
+                           c.out, L, Lp, c.s, nunits, c.queue, ratio);
+    };
+    if (coal) launch(k_sweep_contig<(M >= 4 ? M : 4), 2, HAS_DIR, HAS_Q>);
+    else if (vec) launch(k_sweep_contig<M, 1, HAS_DIR, HAS_Q>);
+    else launch(k_sweep_contig<M, 0, HAS_DIR, HAS_Q>);
+}
+
+void contig_sweep(bool has_dir, bool has_q, const SweepArgs &a, const Lay &L, const SweepScal &s, double *out, void *work,
+                  size_t work_bytes, hipStream_t st)
+{
+    const int n = L.nz, M = contig_rows_per_lane(n);
+    const long nlines = (long)L.nx * L.ny;
+    const int lw = 64 / next_pow2((n + M - 1) / M);
+    // (dval and qf count even in the builds that do not load them)
+    const uintptr_t doubles = (uintptr_t)a.in | (uintptr_t)a.coeff | (uintptr_t)out | (uintptr_t)a.dval | (uintptr_t)a.qf;
+    const bool aligned = (doubles & 15) == 0 && (((uintptr_t)a.flags | (uintptr_t)a.dmask) & 7) == 0 && (L.sx % 8 == 0);
     // FAST kernel: as many rows per lane as divide the line (16, else 8), so that one in-wave PCR serves several lines --
     // n = 512: two lines per wave, n = 256: four (with the GENERAL kernel's 4 rows per lane the PCR ran over 64 lanes per
     // line: 155 Gcell/s at 256^3 against 311 at nz = 512)
@@ -147,58 +167,18 @@ static void launch_contig(const double *in, const uint8_t *flags, const double *
     const int lwf = 64 / next_pow2((n + Mf - 1) / Mf);
     const long nunits_f = (nlines + lwf - 1) / lwf;
     const bool fast = use_fast(s, work, work_bytes, nunits_f) && (n % Mf == 0) && (lwf % lw == 0);
-    unsigned *queue = fast ? (unsigned *)work : nullptr;
-    unsigned ggrid = grid;
-    if (fast) {
-        const bool nofb = s.nofb != 0;                 // promise: no unit will be queued (see SweepScal)
-        if (nofb) queue = nullptr;
-        else (void)hipMemsetAsync(queue, 0, sizeof(unsigned), st);
-        const bool vecf = aligned && (n % Mf == 0);
-        if (Mf > 16)          // 20 / 24 / 28 rows per lane: instantiated in adi_sweep_contig_x.hip
-            contig_fast_exact(Mf, HAS_DIR, HAS_Q, in, flags, coeff, dmask, dval, qf, out, L, s, vecf, nunits_f, queue, st);
-        else if (Mf == 16 && M != 16)
-            launch_contig_fast<16, HAS_DIR, HAS_Q>(in, flags, coeff, dmask, dval, qf, out, L, s, vecf, nunits_f, queue, st);
-        else if (Mf == 8 && M != 8)
-            launch_contig_fast<8, HAS_DIR, HAS_Q>(in, flags, coeff, dmask, dval, qf, out, L, s, vecf, nunits_f, queue, st);
-        else
-            launch_contig_fast<M, HAS_DIR, HAS_Q>(in, flags, coeff, dmask, dval, qf, out, L, s, vecf, nunits_f, queue, st);
-        ggrid = grid < 2048u ? grid : 2048u;
-        if (nofb) return;
-    }
-    const int ratio = fast ? lwf / lw : 1;
-    // coalesced + LDS-transposed access with streaming loads/stores: 1.01 -> 0.92 ms on the dense general-pack sweep at
-    // 512^3 (with the default cache policy the transposition alone gained nothing)
-    const bool coal = vec && M >= 4 && Lp * M == n && (L.ny % lw == 0) && (nlines % lw == 0);
-    if (coal)
-        hipLaunchKernelGGL((k_sweep_contig<(M >= 4 ? M : 4), 2, HAS_DIR, HAS_Q>), dim3(ggrid), dim3(256), 0, st, in, flags,
-                           coeff, dmask, dval, qf, out, L, Lp, s, nunits, queue, ratio);
-    else if (vec)
-        hipLaunchKernelGGL((k_sweep_contig<M, 1, HAS_DIR, HAS_Q>), dim3(ggrid), dim3(256), 0, st, in, flags, coeff,
-                           dmask, dval, qf, out, L, Lp, s, nunits, queue, ratio);
-    else
-        hipLaunchKernelGGL((k_sweep_contig<M, 0, HAS_DIR, HAS_Q>), dim3(ggrid), dim3(256), 0, st, in, flags, coeff,
-                           dmask, dval, qf, out, L, Lp, s, nunits, queue, ratio);
-}
-
-template <bool HAS_DIR, bool HAS_Q>
-static void contig_sweep_t(const SweepArgs &a, const Lay &L, const SweepScal &s, double *out, void *work, size_t work_bytes,
-                           hipStream_t st)
-{
-    switch (contig_rows_per_lane(L.nz)) {
-        case 2: launch_contig<2, HAS_DIR, HAS_Q>(a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, L, s, work, work_bytes, st); break;
-        case 4: launch_contig<4, HAS_DIR, HAS_Q>(a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, L, s, work, work_bytes, st); break;
-        case 8: launch_contig<8, HAS_DIR, HAS_Q>(a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, L, s, work, work_bytes, st); break;
-        default: launch_contig<16, HAS_DIR, HAS_Q>(a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, L, s, work, work_bytes, st); break;
-    }
-}
-
-void contig_sweep(bool has_dir, bool has_q, const SweepArgs &a, const Lay &L, const SweepScal &s, double *out, void *work,
-                  size_t work_bytes, hipStream_t st)
-{
-    if (has_dir && has_q) contig_sweep_t<true, true>(a, L, s, out, work, work_bytes, st);
-    else if (has_q) contig_sweep_t<false, true>(a, L, s, out, work, work_bytes, st);
-    else if (has_dir) contig_sweep_t<true, false>(a, L, s, out, work, work_bytes, st);
-    else contig_sweep_t<false, false>(a, L, s, out, work, work_bytes, st);
+    ContigCall c = {a, out, L, s, aligned, nunits_f, fast ? (unsigned *)work : nullptr, st};
+    by_variant(has_dir, has_q, [&](auto dir, auto q) {
+        if (fast) {
+            const bool nofb = s.nofb != 0;                 // promise: no unit will be queued (see SweepScal)
+            if (nofb) c.queue = nullptr;
+            else (void)hipMemsetAsync(c.queue, 0, sizeof(unsigned), st);
+            if (in_rows(RowsContigX(), Mf)) contig_fast_exact(Mf, dir.value, q.value, c);
+            else by_rows(RowsContig(), Mf, [&](auto mf) { launch_contig_fast<mf.value, dir.value, q.value>(c); });
+            if (nofb) return;
+        }
+        by_rows(RowsContig(), M, [&](auto m) { launch_contig<m.value, dir.value, q.value>(c, fast ? lwf / lw : 1); });
+    });
 }
 
 }  // namespace adi

@@ -8,24 +8,11 @@
 
 namespace adi {
 
-template <int MF>
-static void exact_t(bool has_dir, bool has_q, const double *in, const uint8_t *flags, const double *coeff, const uint8_t *dmask,
-                    const double *dval, const double *qf, double *out, const Lay &L, SweepScal s, bool vec, long nunits_f,
-                    unsigned *queue, hipStream_t st)
+void contig_fast_exact(int mf, bool has_dir, bool has_q, const ContigCall &c)
 {
-    if (has_dir && has_q) launch_contig_fast<MF, true, true>(in, flags, coeff, dmask, dval, qf, out, L, s, vec, nunits_f, queue, st);
-    else if (has_q) launch_contig_fast<MF, false, true>(in, flags, coeff, dmask, dval, qf, out, L, s, vec, nunits_f, queue, st);
-    else if (has_dir) launch_contig_fast<MF, true, false>(in, flags, coeff, dmask, dval, qf, out, L, s, vec, nunits_f, queue, st);
-    else launch_contig_fast<MF, false, false>(in, flags, coeff, dmask, dval, qf, out, L, s, vec, nunits_f, queue, st);
-}
-
-void contig_fast_exact(int mf, bool has_dir, bool has_q, const double *in, const uint8_t *flags, const double *coeff,
-                       const uint8_t *dmask, const double *dval, const double *qf, double *out, const Lay &L, SweepScal s,
-                       bool vec, long nunits_f, unsigned *queue, hipStream_t st)
-{
-    if (mf == 20) exact_t<20>(has_dir, has_q, in, flags, coeff, dmask, dval, qf, out, L, s, vec, nunits_f, queue, st);
-    else if (mf == 24) exact_t<24>(has_dir, has_q, in, flags, coeff, dmask, dval, qf, out, L, s, vec, nunits_f, queue, st);
-    else exact_t<28>(has_dir, has_q, in, flags, coeff, dmask, dval, qf, out, L, s, vec, nunits_f, queue, st);
+    by_rows(RowsContigX(), mf, [&](auto m) {
+        by_variant(has_dir, has_q, [&](auto dir, auto q) { launch_contig_fast<m.value, dir.value, q.value>(c); });
+    });
 }
 
 }  // namespace adi

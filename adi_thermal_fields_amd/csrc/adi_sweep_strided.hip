@@ -55,96 +55,74 @@ __global__ __launch_bounds__(256) void k_sweep_generic(
 // host-side launch logic
 // ------------------------------------------------------------------------------------------------
 
-template <int M, bool HAS_DIR, bool HAS_Q, bool FUSE>
-static void launch_strided(const StridedPlan &P, const double *in, const uint8_t *flags, const double *coeff,
-                           const uint8_t *dmask, const double *dval, const double *qf, double *out, const LineGeom &g,
-                           const double *xlo, const double *xhi, SweepScal s, unsigned *queue, hipStream_t st,
-                           const Fuse &fz)
+// The front dispatcher of the FAST kernels: the translation unit by membership of the plan's rows per thread in its list
+// (adi_cart_host.hpp), the plain counts here.
+template <bool HAS_DIR, bool HAS_Q, bool FUSE>
+static void launch_strided_fast_any(const StridedPlan &P, const StridedCall &c)
 {
+    if (in_rows(RowsFastX(), P.Mf)) strided_fast_exact(P.Mf, HAS_DIR, HAS_Q, P, c);
+    else if (in_rows(RowsFastY(), P.Mf)) strided_fast_exact2(P.Mf, HAS_DIR, HAS_Q, P, c);
+    else if (in_rows(RowsFusedX(), P.Mf)) strided_fast_fused_exact(P.Mf, HAS_Q, P, c);       // (no Dirichlet cells)
+    else if (in_rows(RowsFusedY(), P.Mf)) strided_fast_fused_exact_odd(P.Mf, HAS_Q, P, c);
+    else
+        by_rows(RowsFast(), P.Mf, [&](auto mf) {   // (32 rows per thread are never fused)
+            launch_strided_fast<mf.value, HAS_DIR, HAS_Q, (FUSE && mf.value <= kFuseMaxRows)>(P, c);
+        });
+}
+
+// FAST kernel first where the call has a unit queue, then the GENERAL kernel on what it queued; else the GENERAL kernel on
+// every tile.
+template <int M, bool HAS_DIR, bool HAS_Q, bool FUSE>
+static void launch_strided(const StridedPlan &P, const StridedCall &call)
+{
+    StridedCall c = call;
     unsigned ggrid = (unsigned)P.ntiles_g;
-    if (queue != nullptr) {
-        const bool nofb = s.nofb != 0;                 // promise: no tile will be queued (see SweepScal)
-        if (nofb) queue = nullptr;
-        else (void)hipMemsetAsync(queue, 0, sizeof(unsigned), st);
-        if (P.Mf == 20 || P.Mf == 24 || P.Mf == 28)      // exact fits: instantiated in adi_sweep_strided_x.hip
-            strided_fast_exact(P.Mf, HAS_DIR, HAS_Q, P, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else if (P.Mf == 18 || P.Mf == 22 || P.Mf == 26 || P.Mf == 30)   // ... and adi_sweep_strided_y.hip
-            strided_fast_exact2(P.Mf, HAS_DIR, HAS_Q, P, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else if (P.Mf == 10 || P.Mf == 12 || P.Mf == 14)  // exact fits of the fused kernel (no Dirichlet cells): adi_sweep_strided_fx.hip
-            strided_fast_fused_exact(P.Mf, HAS_Q, P, in, flags, coeff, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else if (P.Mf == 9 || P.Mf == 11 || P.Mf == 13 || P.Mf == 15)   // ... and the odd row counts: adi_sweep_strided_fy.hip
-            strided_fast_fused_exact_odd(P.Mf, HAS_Q, P, in, flags, coeff, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else if (P.Mf == 32) launch_strided_fast<32, HAS_DIR, HAS_Q, false>(P, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else if (P.Mf == 16) launch_strided_fast<16, HAS_DIR, HAS_Q, FUSE>(P, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else launch_strided_fast<8, HAS_DIR, HAS_Q, FUSE>(P, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
+    if (c.queue != nullptr) {
+        const bool nofb = c.s.nofb != 0;               // promise: no tile will be queued (see SweepScal)
+        if (nofb) c.queue = nullptr;
+        else (void)hipMemsetAsync(c.queue, 0, sizeof(unsigned), c.st);
+        launch_strided_fast_any<HAS_DIR, HAS_Q, FUSE>(P, c);
         ggrid = P.ntiles_g < 1024 ? (unsigned)P.ntiles_g : 1024u;
         if (nofb) return;
     }
     // 8 / 16 rows per thread: the source of the coefficients and the deferred correction are compiled in or out (see
     // adi_strided_general.hpp); shorter segments decide both at run time
-    if constexpr (M >= 8) {
-        if (!FUSE && s.c_w != nullptr)
-            strided_general_corr(M, HAS_DIR, HAS_Q, P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else if (s.fconst)
-            strided_general_fc(M, HAS_DIR, HAS_Q, FUSE, P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else
-            launch_strided_general_t<M, HAS_DIR, HAS_Q, FUSE, 2, false>(P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi,
-                                                                        s, queue, st, fz);
+    if constexpr (in_rows(RowsGeneralBuilt(), M)) {
+        if (!FUSE && c.s.c_w != nullptr) strided_general_corr(M, HAS_DIR, HAS_Q, P, ggrid, c);
+        else if (c.s.fconst) strided_general_fc(M, HAS_DIR, HAS_Q, FUSE, P, ggrid, c);
+        else launch_strided_general_t<M, HAS_DIR, HAS_Q, FUSE, 2, false>(P, ggrid, c);
     } else {
-        launch_strided_general_t<M, HAS_DIR, HAS_Q, FUSE, 0, true>(P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s,
-                                                                   queue, st, fz);
-    }
-}
-
-template <bool HAS_DIR, bool HAS_Q>
-static void strided_sweep_t(const SweepArgs &a, const Lay &L, const LineGeom &g, const SweepScal &s, double *out,
-                            const double *xlo, const double *xhi, void *work, size_t work_bytes, hipStream_t st,
-                            const Fuse *fzp)
-{
-    StridedPlan P = strided_plan(g, s.sparse != 0 && work != nullptr, false, fzp != nullptr, fzp != nullptr && !HAS_DIR);
-    unsigned *queue = nullptr;
-    if (P.Mf && use_fast(s, work, work_bytes, P.ntiles_f)) queue = (unsigned *)work;
-    else if (P.Mf) P = strided_plan(g, false, false);
-    if (fzp != nullptr) {
-        Fuse fz = *fzp;
-        if (queue != nullptr && !fuse_fast_ok(P, L, fz)) { queue = nullptr; P = strided_plan(g, false, false); }
-        fuse_tile_order(fz, P, L);
-        switch (P.Mg) {
-            case 2: launch_strided<2, HAS_DIR, HAS_Q, true>(P, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, xlo, xhi, s, queue, st, fz); break;
-            case 4: launch_strided<4, HAS_DIR, HAS_Q, true>(P, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, xlo, xhi, s, queue, st, fz); break;
-            case 8: launch_strided<8, HAS_DIR, HAS_Q, true>(P, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, xlo, xhi, s, queue, st, fz); break;
-            default: launch_strided<16, HAS_DIR, HAS_Q, true>(P, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, xlo, xhi, s, queue, st, fz); break;
-        }
-        return;
-    }
-    const Fuse fz = Fuse();
-    switch (P.Mg) {
-        case 2: launch_strided<2, HAS_DIR, HAS_Q, false>(P, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, xlo, xhi, s, queue, st, fz); break;
-        case 4: launch_strided<4, HAS_DIR, HAS_Q, false>(P, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, xlo, xhi, s, queue, st, fz); break;
-        case 8: launch_strided<8, HAS_DIR, HAS_Q, false>(P, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, xlo, xhi, s, queue, st, fz); break;
-        default: launch_strided<16, HAS_DIR, HAS_Q, false>(P, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, xlo, xhi, s, queue, st, fz); break;
+        launch_strided_general_t<M, HAS_DIR, HAS_Q, FUSE, 0, true>(P, ggrid, c);
     }
 }
 
 void strided_sweep(bool has_dir, bool has_q, const SweepArgs &a, const Lay &L, const LineGeom &g, const SweepScal &s,
                    double *out, const double *xlo, const double *xhi, void *work, size_t work_bytes, hipStream_t st,
-                   const Fuse *fz)
+                   const Fuse *fzp)
 {
-    if (has_dir && has_q) strided_sweep_t<true, true>(a, L, g, s, out, xlo, xhi, work, work_bytes, st, fz);
-    else if (has_q) strided_sweep_t<false, true>(a, L, g, s, out, xlo, xhi, work, work_bytes, st, fz);
-    else if (has_dir) strided_sweep_t<true, false>(a, L, g, s, out, xlo, xhi, work, work_bytes, st, fz);
-    else strided_sweep_t<false, false>(a, L, g, s, out, xlo, xhi, work, work_bytes, st, fz);
+    StridedPlan P = strided_plan(g, s.sparse != 0 && work != nullptr, false, fzp != nullptr, fzp != nullptr && !has_dir);
+    StridedCall c = {a, out, g, xlo, xhi, s, nullptr, st, fzp != nullptr ? *fzp : Fuse()};
+    if (P.Mf && use_fast(s, work, work_bytes, P.ntiles_f)) c.queue = (unsigned *)work;
+    else if (P.Mf) P = strided_plan(g, false, false);
+    if (fzp != nullptr) {
+        if (c.queue != nullptr && !fuse_fast_ok(P, L, c.fz)) { c.queue = nullptr; P = strided_plan(g, false, false); }
+        fuse_tile_order(c.fz, P, L);
+    }
+    by_variant(has_dir, has_q, [&](auto dir, auto q) {
+        by_bool(fzp != nullptr, [&](auto fuse) {
+            by_rows(RowsGeneral(), P.Mg, [&](auto m) { launch_strided<m.value, dir.value, q.value, fuse.value>(P, c); });
+        });
+    });
 }
 
 void generic_sweep(bool has_dir, bool has_q, const SweepArgs &a, const LineGeom &g, long inner_stride, const SweepScal &s,
                    double *out, const double *xlo, const double *xhi, double *wc, double *wd, hipStream_t st)
 {
     const long nl = (long)g.n_inner * g.n_outer;
-    const dim3 grid((unsigned)((nl + 255) / 256)), block(256);
-    if (has_dir && has_q) hipLaunchKernelGGL((k_sweep_generic<true, true>), grid, block, 0, st, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, inner_stride, xlo, xhi, wc, wd, s);
-    else if (has_q) hipLaunchKernelGGL((k_sweep_generic<false, true>), grid, block, 0, st, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, inner_stride, xlo, xhi, wc, wd, s);
-    else if (has_dir) hipLaunchKernelGGL((k_sweep_generic<true, false>), grid, block, 0, st, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, inner_stride, xlo, xhi, wc, wd, s);
-    else hipLaunchKernelGGL((k_sweep_generic<false, false>), grid, block, 0, st, a.in, a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, inner_stride, xlo, xhi, wc, wd, s);
+    by_variant(has_dir, has_q, [&](auto dir, auto q) {
+        hipLaunchKernelGGL((k_sweep_generic<dir.value, q.value>), dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, a.in,
+                           a.flags, a.coeff, a.dmask, a.dval, a.qf, out, g, inner_stride, xlo, xhi, wc, wd, s);
+    });
 }
 
 }  // namespace adi

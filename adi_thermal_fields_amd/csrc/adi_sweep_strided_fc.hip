@@ -9,27 +9,17 @@
 
 namespace adi {
 
-template <bool HAS_Q>
-static void fc_t(int mf, bool fuse, const StridedPlan &P, const double *in, const uint8_t *flags, const double *coeff,
-                 const double *qf, double *out, const LineGeom &g, const double *xlo, const double *xhi, SweepScal s,
-                 unsigned *queue, hipStream_t st, const Fuse &fz)
+void strided_fast_fc(int mf, bool has_q, bool fuse, const StridedPlan &P, const StridedCall &c)
 {
-    if (mf == 32) launch_strided_fast_t<32, false, HAS_Q, false, true>(P, in, flags, coeff, nullptr, nullptr, qf, out, g, xlo, xhi, s, queue, st, fz);
-    else if (mf == 16) {
-        if (fuse) launch_strided_fast_t<16, false, HAS_Q, true, true>(P, in, flags, coeff, nullptr, nullptr, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else launch_strided_fast_t<16, false, HAS_Q, false, true>(P, in, flags, coeff, nullptr, nullptr, qf, out, g, xlo, xhi, s, queue, st, fz);
-    } else {
-        if (fuse) launch_strided_fast_t<8, false, HAS_Q, true, true>(P, in, flags, coeff, nullptr, nullptr, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else launch_strided_fast_t<8, false, HAS_Q, false, true>(P, in, flags, coeff, nullptr, nullptr, qf, out, g, xlo, xhi, s, queue, st, fz);
-    }
-}
-
-void strided_fast_fc(int mf, bool has_q, bool fuse, const StridedPlan &P, const double *in, const uint8_t *flags,
-                     const double *coeff, const double *qf, double *out, const LineGeom &g, const double *xlo,
-                     const double *xhi, SweepScal s, unsigned *queue, hipStream_t st, const Fuse &fz)
-{
-    if (has_q) fc_t<true>(mf, fuse, P, in, flags, coeff, qf, out, g, xlo, xhi, s, queue, st, fz);
-    else fc_t<false>(mf, fuse, P, in, flags, coeff, nullptr, out, g, xlo, xhi, s, queue, st, fz);
+    const StridedCall v = without_dir(c, has_q);
+    by_rows(RowsFast(), mf, [&](auto m) {
+        by_bool(has_q, [&](auto q) {
+            // (32 rows per thread are never fused)
+            by_bool(fuse && m.value <= kFuseMaxRows, [&](auto f) {
+                launch_strided_fast_t<m.value, false, q.value, (f.value && m.value <= kFuseMaxRows), true>(P, v);
+            });
+        });
+    });
 }
 
 }  // namespace adi

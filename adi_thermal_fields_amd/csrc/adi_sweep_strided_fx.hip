@@ -8,28 +8,9 @@
 
 namespace adi {
 
-template <int MF, bool HAS_Q>
-static void fx_t(const StridedPlan &P, const double *in, const uint8_t *flags, const double *coeff, const double *qf,
-                 double *out, const LineGeom &g, const double *xlo, const double *xhi, SweepScal s, unsigned *queue,
-                 hipStream_t st, const Fuse &fz)
+void strided_fast_fused_exact(int mf, bool has_q, const StridedPlan &P, const StridedCall &c)
 {
-    if (s.fconst) launch_strided_fast_t<MF, false, HAS_Q, true, true>(P, in, flags, coeff, nullptr, nullptr, qf, out, g, xlo, xhi, s, queue, st, fz);
-    else launch_strided_fast_t<MF, false, HAS_Q, true, false>(P, in, flags, coeff, nullptr, nullptr, qf, out, g, xlo, xhi, s, queue, st, fz);
-}
-
-void strided_fast_fused_exact(int mf, bool has_q, const StridedPlan &P, const double *in, const uint8_t *flags,
-                              const double *coeff, const double *qf, double *out, const LineGeom &g, const double *xlo,
-                              const double *xhi, SweepScal s, unsigned *queue, hipStream_t st, const Fuse &fz)
-{
-    if (has_q) {
-        if (mf == 10) fx_t<10, true>(P, in, flags, coeff, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else if (mf == 12) fx_t<12, true>(P, in, flags, coeff, qf, out, g, xlo, xhi, s, queue, st, fz);
-        else fx_t<14, true>(P, in, flags, coeff, qf, out, g, xlo, xhi, s, queue, st, fz);
-    } else {
-        if (mf == 10) fx_t<10, false>(P, in, flags, coeff, nullptr, out, g, xlo, xhi, s, queue, st, fz);
-        else if (mf == 12) fx_t<12, false>(P, in, flags, coeff, nullptr, out, g, xlo, xhi, s, queue, st, fz);
-        else fx_t<14, false>(P, in, flags, coeff, nullptr, out, g, xlo, xhi, s, queue, st, fz);
-    }
+    launch_strided_fused_exact(RowsFusedX(), mf, has_q, P, c);
 }
 
 }  // namespace adi

@@ -7,24 +7,13 @@
 
 namespace adi {
 
-template <int M>
-static void gk_m(bool has_dir, bool has_q, const StridedPlan &P, unsigned ggrid, const double *in, const uint8_t *flags,
-                 const double *coeff, const uint8_t *dmask, const double *dval, const double *qf, double *out, const LineGeom &g,
-                 const double *xlo, const double *xhi, const SweepScal &s, const unsigned *queue, hipStream_t st, const Fuse &fz)
+void strided_general_corr(int m, bool has_dir, bool has_q, const StridedPlan &P, unsigned ggrid, const StridedCall &c)
 {
-    if (has_dir && has_q) launch_strided_general_t<M, true, true, false, 0, true>(P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-    else if (has_q) launch_strided_general_t<M, false, true, false, 0, true>(P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-    else if (has_dir) launch_strided_general_t<M, true, false, false, 0, true>(P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-    else launch_strided_general_t<M, false, false, false, 0, true>(P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-}
-
-void strided_general_corr(int m, bool has_dir, bool has_q, const StridedPlan &P, unsigned ggrid, const double *in,
-                          const uint8_t *flags, const double *coeff, const uint8_t *dmask, const double *dval, const double *qf,
-                          double *out, const LineGeom &g, const double *xlo, const double *xhi, const SweepScal &s,
-                          const unsigned *queue, hipStream_t st, const Fuse &fz)
-{
-    if (m == 8) gk_m<8>(has_dir, has_q, P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
-    else gk_m<16>(has_dir, has_q, P, ggrid, in, flags, coeff, dmask, dval, qf, out, g, xlo, xhi, s, queue, st, fz);
+    by_rows(RowsGeneralBuilt(), m, [&](auto M) {
+        by_variant(has_dir, has_q, [&](auto dir, auto q) {
+            launch_strided_general_t<M.value, dir.value, q.value, false, 0, true>(P, ggrid, c);
+        });
+    });
 }
 
 }  // namespace adi
