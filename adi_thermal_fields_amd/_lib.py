@@ -170,6 +170,13 @@ SIGNATURES = {
                                      c_double, c_void_p]),
     'adi_scan_sample': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_int, c_int, c_long, c_double, c_double,
                                 c_double, c_void_p, c_void_p]),
+    'adi_bead_index_box': (c_int, [c_void_p, c_void_p, c_int, c_double, c_int, c_int, c_int, c_double, c_double, c_double,
+                                   c_int_p, c_int_p]),
+    'adi_bead_deposit_host': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_int, c_int, c_int, c_double,
+                                      c_double, c_double, c_void_p]),
+    'adi_bead_deposit': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                 c_int, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double, c_void_p,
+                                 c_void_p]),
     'adi_surface_loss_update': (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double,
                                         c_double, c_double, c_void_pp, c_int, c_int, c_int, c_void_p]),
     'adi_phase_summary_words': (ctypes.c_long, [c_int, c_int, c_int]),
@@ -239,6 +246,14 @@ class ScanShape(ctypes.Structure):
     """adi_scan_shape (include/adi_hip.h)"""
     _fields_ = [('eta', c_double), ('a', c_double), ('b', c_double), ('c_f', c_double), ('c_r', c_double), ('f_f', c_double),
                 ('depth_axis', c_int), ('reserved', c_int)]
+
+
+BEAD_PROFILES = {'box': 0, 'parabola': 1}   # adi_bead_shape.profile
+
+
+class BeadShape(ctypes.Structure):
+    """adi_bead_shape (include/adi_hip.h)"""
+    _fields_ = [('width', c_double), ('height', c_double), ('profile', c_int), ('depth_axis', c_int)]
 
 
 class SurfaceLossLaw(ctypes.Structure):

@@ -29,7 +29,7 @@ precompute_coeff_packs_unified(grid, ...) call, which is the documented synchron
 Where things live: this module defines nothing, it re-exports.  fields.py -- Layout, DeviceField, to_device, Grid3D and the
 device helpers; packs.py -- Material, Params, AxisCoeffPack, exposed_mask, precompute_coeff_packs_unified; heat_source.py --
 GoldakSource, ScanPath, ScanPathSource and the one host definition of Goldak's double ellipsoid; deposition.py -- the surface impulse, the
-perimeter ratio, birth_planes, BirthPacks; surface_loss.py -- SurfaceLoss, LossPacks; phase.py -- PhaseChange, PhaseField, MaterialLaw, NonlinearPacks;
+perimeter ratio, birth_planes, BirthPacks, BeadProfile, PathDeposit (births along a scan path); surface_loss.py -- SurfaceLoss, LossPacks; phase.py -- PhaseChange, PhaseField, MaterialLaw, NonlinearPacks;
 history.py -- HistoryLevels, ThermalHistory, SolidificationRecord; step.py -- the stage entry points, the launch sequence, adi_step_hip_coeff,
 StagedStepper.  Each imports only those before it in this list ("Module map"); code inside the package imports
 from them, drivers and tests from here.
@@ -43,7 +43,7 @@ from .fields import (_MASK_VERSIONS, _device, _stream, _p, _sweep_workspace_byte
 from .packs import Material, Params, AxisCoeffPack, exposed_mask, _fc_arg, precompute_coeff_packs_unified
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .deposition import (apply_surface_impulse_Q, exposed_faces_per_layer, count_exposed_faces, perimeter_ratio, birth_planes,
-                         BirthPacks)
+                         BirthPacks, BeadProfile, PathDeposit)
 from .surface_loss import SurfaceLoss, LossPacks
 from .phase import PhaseChange, PhaseField, MaterialLaw, NonlinearPacks
 from .history import HistoryLevels, ThermalHistory, SolidificationRecord
@@ -57,7 +57,7 @@ __all__ = ['Grid3D', 'Material', 'Params', 'AxisCoeffPack', 'exposed_mask', 'pre
            'exposed_faces_per_layer', 'count_exposed_faces', 'perimeter_ratio', 'birth_planes', 'BirthPacks',
            'GoldakSource', 'ScanPath', 'SurfaceLoss', 'LossPacks', 'PhaseChange', 'PhaseField', 'HistoryLevels',
            'ThermalHistory']
-# (ScanPathSource, MaterialLaw, NonlinearPacks and SolidificationRecord are exported like the names above but are not part of the pinned `__all__`)
+# (ScanPathSource, BeadProfile, PathDeposit, MaterialLaw, NonlinearPacks and SolidificationRecord are exported like the names above but are not part of the pinned `__all__`)
 
 # an assignment to a name above reaches the module that defined it (_facade.ReExporting)
 sys.modules[__name__].__class__ = ReExporting

@@ -4,6 +4,7 @@
 //                          the field form of the step (adi_explicit_rhs_src)
 // K travels by value and bounds every loop over segments; every segment index read lies in [0, K).
 #include "adi_cart_host.hpp"
+#include "adi_scan_check.hpp"
 #include "adi_scan_eval.hpp"
 
 namespace adi {
@@ -52,35 +53,14 @@ static int check_shape(const adi_scan_shape *h, const char *fn)
 static int check_path(const adi_scan_shape *h, int K, double t_end, const char *fn)
 {
     if (int rc = check_shape(h, fn)) return rc;
-    ADI_REQUIRE(K >= 1, "%s: a path needs at least one segment (K = %d)", fn, K);
-    ADI_REQUIRE(K <= ADI_SCAN_MAX_SEGMENTS, "%s: K = %d segments, at most %d", fn, K, ADI_SCAN_MAX_SEGMENTS);
-    ADI_REQUIRE(std::isfinite(t_end), "%s: non-finite t_end", fn);
-    return ADI_OK;
+    return scan_check_path(K, t_end, fn);
 }
 
-// ... and the host table: finite, t_begin ascending, t_end after the last begin, unit directions, speed >= 0, power >= 0
+// ... and the host table (scan_check_rows)
 static int check_table(const adi_scan_shape *h, const double *tab, int K, double t_end, const char *fn)
 {
     if (int rc = check_path(h, K, t_end, fn)) return rc;
-    ADI_REQUIRE(tab != nullptr, "%s: null segment table", fn);
-    for (int k = 0; k < K; ++k) {
-        const double *s = tab + (long)k * kScanCols;
-        for (int c = 0; c < kScanCols; ++c) ADI_REQUIRE(std::isfinite(s[c]), "%s: segment %d: non-finite entry", fn, k);
-        ADI_REQUIRE(scan_t_next(tab, K, t_end, k) > s[0],
-                    k + 1 < K ? "%s: segment %d: t_begin does not ascend" : "%s: segment %d: t_end is not after the last t_begin",
-                    fn, k);
-        ADI_REQUIRE(fabs(hypot(s[4], s[5]) - 1.0) <= 1e-12, "%s: segment %d: the direction is not a unit vector", fn, k);
-        ADI_REQUIRE(s[6] >= 0.0, "%s: segment %d: speed < 0", fn, k);
-        ADI_REQUIRE(s[7] >= 0.0, "%s: segment %d: power < 0", fn, k);
-    }
-    return ADI_OK;
-}
-
-static int check_grid(int nx, int ny, int nz, double dx, const char *fn)
-{
-    ADI_REQUIRE(nx > 0 && ny > 0 && nz > 0, "%s: bad grid %d x %d x %d", fn, nx, ny, nz);
-    ADI_REQUIRE(std::isfinite(dx) && dx > 0.0, "%s: bad dx", fn);
-    return ADI_OK;
+    return scan_check_rows(tab, K, t_end, fn);
 }
 
 }  // namespace adi
@@ -93,7 +73,7 @@ int adi_scan_sample_host(const adi_scan_shape *h_shape, const double *h_table, i
                          int nx, int ny, int nz, double dx, double t, double dt, double *h_out)
 {
     if (int rc = check_table(h_shape, h_table, K, t_end, "adi_scan_sample_host")) return rc;
-    if (int rc = check_grid(nx, ny, nz, dx, "adi_scan_sample_host")) return rc;
+    if (int rc = scan_check_grid(nx, ny, nz, dx, "adi_scan_sample_host")) return rc;
     ADI_REQUIRE(h_out, "adi_scan_sample_host: null output");
     ADI_REQUIRE(std::isfinite(t) && std::isfinite(dt) && dt > 0.0, "adi_scan_sample_host: bad t / dt (dt must be > 0)");
     scan_sample_host(*h_shape, h_table, K, t_end, h_mask, nx, ny, nz, dx, t, dt, h_out);

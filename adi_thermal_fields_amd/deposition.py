@@ -1,5 +1,5 @@
-"""Deposition helpers: the surface impulse, the perimeter ratio of a voxelised section, and layer births on the device
-(`birth_planes`, `BirthPacks`)."""
+"""Deposition helpers: the surface impulse, the perimeter ratio of a voxelised section, layer births on the device
+(`birth_planes`, `BirthPacks`), and bead-by-bead births along a scan path (`BeadProfile`, `PathDeposit`)."""
 import ctypes
 
 import numpy as np
@@ -7,7 +7,8 @@ import torch
 
 from . import _lib
 from ._lib import lib, check, ptr_array, FACES
-from .fields import DeviceField, Grid3D, _device, _p, _stream
+from .fields import DeviceField, Grid3D, _device, _native_f64, _p, _stream
+from .heat_source import ScanPath, ScanPathSource
 from .packs import AxisCoeffPack, _face_constants
 
 
@@ -127,3 +128,182 @@ class BirthPacks:
             p.mask_version = g.mask_version
             p._fractions = (g, a, g.mask_version)
         return self.packs
+
+
+# ---- bead-by-bead births along a scan path ---------------------------------------------------------------------------
+class BeadProfile:
+    """The cross-section of the bead a ScanPath lays (README, "Deposition along a path"): `width` across the leg and `height`
+    below the path point, which is the TOP of the bead [m]; profile 'box' (the full height over the whole width) or 'parabola'
+    (height * (1 - r^2 / (width/2)^2) at distance r from the path).  ValueError for anything else."""
+    PROFILES = _lib.BEAD_PROFILES
+
+    def __init__(self, width, height, profile='box'):
+        self.width, self.height, self.profile = width, height, profile
+        self.validate()
+
+    def validate(self):
+        """ValueError for a parameter adi_bead_shape rejects (include/adi_hip.h) -> (width, height) as floats"""
+        try:
+            w, h = float(self.width), float(self.height)
+        except (TypeError, ValueError):
+            raise ValueError("BeadProfile: parameters must be real numbers")
+        if not (np.isfinite(w) and np.isfinite(h)):
+            raise ValueError("BeadProfile: non-finite parameter")
+        if min(w, h) <= 0:
+            raise ValueError("BeadProfile: non-positive length (width, height must be > 0)")
+        if not isinstance(self.profile, str) or self.profile not in self.PROFILES:
+            raise ValueError("BeadProfile: profile must be 'box' or 'parabola'")
+        return w, h
+
+    def as_c(self, depth_axis):
+        w, h = self.validate()
+        return _lib.BeadShape(w, h, self.PROFILES[self.profile], int(depth_axis))
+
+
+class PathDeposit:
+    """Material laid where the torch went: the cells a scan path brings to life during a step [t, t + dt] (include/adi_hip.h,
+    "Bead deposition along a scan path"; `reference` is the definition).  `path`: a ScanPath, frozen here with on_device(), or a
+    ScanPathSource; `bead`: a BeadProfile; newborn cells get T = Ts; `within` (optional bool array or uint8 device tensor of
+    the grid's shape): the part's final shape, e.g. from voxelize_solid -- no cell outside it is born.
+    The grid's device mask is the active mask: `deposit` writes it in place and rebuilds the grid's flags and bricks on the
+    planes whose exposure can have changed; the packs are the caller's (BirthPacks.update / LossPacks.rebuild on the range it
+    returns).  Nothing is read back and nothing is synchronised.
+    `grid` may also be any object with nx, ny, nz, dx and mask (no device): then `born_host` and `index_box` work, which need
+    no GPU, and `deposit` does not."""
+
+    def __init__(self, grid, path, bead, Ts, within=None):
+        if isinstance(path, ScanPath):
+            path = path.on_device()
+        if not isinstance(path, ScanPathSource):
+            raise TypeError("PathDeposit: path must be a ScanPath or a ScanPathSource, got %s" % type(path).__name__)
+        if not isinstance(bead, BeadProfile):
+            raise TypeError("PathDeposit: bead must be a BeadProfile, got %s" % type(bead).__name__)
+        try:
+            self.Ts = float(Ts)
+        except (TypeError, ValueError):
+            raise ValueError("PathDeposit: Ts must be a real number")
+        if not np.isfinite(self.Ts):
+            raise ValueError("PathDeposit: non-finite Ts")
+        self.grid, self.path, self.bead = grid, path, bead
+        self._c_shape = bead.as_c(path.depth_axis)
+        self._n = (int(grid.nx), int(grid.ny), int(grid.nz))
+        self._on_device = isinstance(grid, Grid3D)
+        self._within, self.d_within, self._count = within, None, None
+        if within is not None:
+            shp = tuple(within.shape) if hasattr(within, 'shape') else np.shape(within)
+            if shp != self._n:
+                raise ValueError("PathDeposit: within has shape %s, the grid %s" % (shp, self._n))
+        if self._on_device:
+            if within is not None:
+                self.d_within = grid.layout.to_layout(within, torch.uint8)
+            if not getattr(grid, '_device_mask', False):         # the mask was uploaded from the host: from now on it lives here
+                grid.set_mask_device(grid.d_mask, all_solid=False)
+            self._count = torch.zeros(1, dtype=torch.int64, device=_device())
+
+    # ---- the definition
+    @staticmethod
+    def reference_terms(path, bead, shape, dx, t, dt):
+        """the terms of `reference` for every piece of the step that deposits, in segment order: (k, r2, h2, z, cap), arrays that
+        broadcast to `shape` -- r2 the squared distance from the piece of path travelled and h2 its bound, z the depth offset from
+        the path point and cap the bead's height there.  One fp64 operation per line, in the order the library performs them."""
+        p = path._path if isinstance(path, ScanPathSource) else path
+        w, h = bead.validate()
+        t, dt, dx = float(t), ScanPath._num(dt, 'dt', positive=True), float(dx)
+        x = [(np.arange(n, dtype=np.float64) + 0.5) * dx for n in shape]
+        X = (x[0][:, None, None], x[1][None, :, None], x[2][None, None, :])
+        (u, v), da = p.axes, int(p.depth_axis)
+        for k in range(len(p._seg)):
+            _, p0, _, d, vel, _ = p._seg[k]
+            pc = p._piece(k, t, t + dt)
+            if pc is None or not vel > 0.0:                  # no power (a jump, an idle dwell) or no travel (a dwell)
+                continue
+            ta, tb, _ = pc
+            ou = X[u] - p0[u]
+            ov = X[v] - p0[v]
+            z = X[da] - p0[da]
+            xi0 = ou * d[0] + ov * d[1]
+            y = ov * d[0] - ou * d[1]
+            sa = vel * ta
+            sb = vel * tb
+            xc = np.minimum(np.maximum(xi0, sa), sb)
+            e = xi0 - xc
+            r2 = e * e + y * y
+            half = 0.5 * w
+            h2 = half * half
+            cap = h * (1.0 - r2 / h2) if bead.profile == 'parabola' else np.full_like(r2, h)
+            yield k, r2, h2, z, cap
+
+    @staticmethod
+    def reference(path, bead, shape, dx, t, dt, active=None, within=None):
+        """THE DEFINITION of the cells born in the step [t, t + dt] on a grid of `shape` cells of edge dx (pure NumPy): the cells
+        whose centre ((i+1/2)dx, (j+1/2)dx, (k+1/2)dx) lies within width/2 of the piece of path travelled (round ends, closed
+        corners) and at most the bead's height below the path's depth coordinate, OR-ed over the depositing segments the step
+        overlaps (power > 0 and speed > 0), inside `within` (where given) and not in `active` (where given) -> bool array"""
+        shape = tuple(int(n) for n in shape)
+        born = np.zeros(shape, dtype=bool)
+        for _, r2, h2, z, cap in PathDeposit.reference_terms(path, bead, shape, dx, t, dt):
+            born |= (r2 <= h2) & (z <= 0.0) & (-z <= cap)
+        if within is not None:
+            born &= np.asarray(within, dtype=bool)
+        if active is not None:
+            born &= ~np.asarray(active, dtype=bool)
+        return born
+
+    # ---- the library on the host
+    def _path_args(self):
+        return (ctypes.byref(self._c_shape), self.path._h_table.ctypes.data, self.path.K, self.path.t_end)
+
+    def _host_within(self):
+        w = self._within
+        if w is None:
+            return None
+        if isinstance(w, torch.Tensor):
+            w = w.cpu().numpy()
+        return np.ascontiguousarray(np.asarray(w).astype(np.bool_, copy=False)).view(np.uint8)
+
+    def born_host(self, t, dt):
+        """the cells the step [t, t + dt] bears on the grid's mask as it is now, by the library on the CPU
+        (adi_bead_deposit_host, no GPU needed) -> bool array"""
+        active = np.ascontiguousarray(np.asarray(self.grid.mask, dtype=np.bool_)).view(np.uint8)
+        if active.shape != self._n:
+            raise ValueError("born_host: the mask has shape %s, the grid %s" % (active.shape, self._n))
+        within = self._host_within()
+        born = np.empty(self._n, dtype=np.uint8)
+        check(lib.adi_bead_deposit_host(*self._path_args(), active.ctypes.data,
+                                        None if within is None else within.ctypes.data, *self._n, float(self.grid.dx),
+                                        float(t), float(dt), born.ctypes.data))
+        return born.astype(np.bool_)
+
+    def index_box(self, t, dt):
+        """((i0, i1), (j0, j1), (k0, k1)): the index box that holds every cell the step [t, t + dt] can bear
+        (adi_bead_index_box, on the host); None when no segment deposits in the step or none of its bead meets the grid"""
+        box, dep = (ctypes.c_int * 6)(), ctypes.c_int(0)
+        check(lib.adi_bead_index_box(*self._path_args(), *self._n, float(self.grid.dx), float(t), float(dt), box,
+                                     ctypes.byref(dep)))
+        b = tuple((box[2 * a], box[2 * a + 1]) for a in range(3))
+        return None if (not dep.value or any(lo >= hi for lo, hi in b)) else b
+
+    # ---- the device
+    def deposit(self, T, t, dt, count=None):
+        """the births of the step [t, t + dt] on the device (adi_bead_deposit): T (a DeviceField in the grid's layout) gets Ts on
+        the newborn cells, the grid's device mask 1, in place; then grid.set_mask_device rebuilds flags and bricks on the planes
+        [k_lo, k_hi) of axis 2 whose exposure can have changed -- the index box's planes and one either side when the path's
+        depth axis is 2, every plane otherwise.  -> (k_lo, k_hi) for the caller's packs; None, and nothing launched, when the step
+        bears nothing.  `count`: optional int64 device tensor (1 element) that receives the number of newborn cells (0 when the
+        step bears nothing)."""
+        if not self._on_device:
+            raise TypeError("PathDeposit.deposit: the grid is not a Grid3D on the device")
+        g = self.grid
+        t_ = _native_f64(g, T, strict="PathDeposit.deposit: T must be an fp64 device field in the grid's layout")
+        box = self.index_box(t, dt)
+        if box is None and count is None:
+            return None
+        d_active = g.d_mask
+        check(lib.adi_bead_deposit(*self._path_args()[:2], _p(self.path.d_table), self.path.K, self.path.t_end, _p(t_),
+                                   _p(d_active), _p(self.d_within), *self._n, *g.layout.pd, g.dx, float(t), float(dt), self.Ts,
+                                   _p(self._count if count is None else count), _stream()))
+        if box is None:
+            return None
+        k_lo, k_hi = (max(0, box[2][0] - 1), min(g.nz, box[2][1] + 1)) if self.path.depth_axis == 2 else (0, g.nz)
+        g.set_mask_device(d_active, k_lo, k_hi, all_solid=False)
+        return k_lo, k_hi

@@ -16,7 +16,8 @@ import math
 import numpy as np
 
 __all__ = ['synthetic_head_mask', 'plan_layers', 'birth_times', 'layer_birth_schedule', 'run_layer_birth', 'run_single_track',
-           'run_layer_birth_slab', 'run_single_track_slab', 'ring_source', 'run_spiral_deposition']
+           'run_layer_birth_slab', 'run_single_track_slab', 'ring_source', 'run_spiral_deposition', 'path_steps',
+           'run_path_deposition']
 
 
 def synthetic_head_mask(nx, ny, nz):
@@ -381,6 +382,85 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     if sol is not None:
         res = res + (solidification_result(sol),)
     return res if len(res) > 1 else res[0]
+
+
+def path_steps(t_start, t_end, dt):
+    """the steps [(t, dt_n)] of run_path_deposition: from t_start in steps of dt, the last one shortened to end at t_end, the
+    time accumulated as t = t + dt_n"""
+    steps, t = [], float(t_start)
+    while t < t_end:
+        d = dt if t + dt <= t_end else t_end - t
+        if not t + d > t:
+            break
+        steps.append((t, d))
+        t = t + d
+    return steps
+
+
+def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, Ts, theta, dt, t_end=None, within=None,
+                        heat=False, surface_loss=None, phase_change=None, history=None, solidification=None, on_frame=None):
+    """Material laid along a scan path, bead by bead (README, "Deposition along a path"): from path.t_start to t_end (default
+    path.t_end) in steps of dt (path_steps), every step preceded by the births of its interval -- the bead of the step [t, t + dt]
+    is born at the step's start, at Ts, on top of `base_mask` (the plate; may be empty).  Device loop only: mask, field and packs
+    live in HBM, a deposit is one kernel on the bead's index box (backend.PathDeposit.deposit) and the rebuild of flags, bricks
+    and packs on the planes it can have changed; nothing is read back between frames.  No ADI step is taken while the base mask
+    is empty and no segment has deposited yet (known from the path on the host).
+    path: a ScanPath or ScanPathSource of the backend; bead: a BeadProfile; within: optional bool array, the part's final
+    shape -- no cell outside it is born.
+    heat: True -- every step also takes the path's step-averaged heat input, S=path.sample_step_device(grid, t, dt), so the same
+    path heats what it lays; False -- the reference's kind of deposit, newborn cells at Ts and nothing else.
+    surface_loss, phase_change, history, solidification: as in run_single_track -- the newborn cells of a step are seeded at
+    f_eq(Ts) / Ts / "never froze", the recorders run on the global time, from path.t_start, and the history's log holds one row
+    per step.
+    on_frame(t, T, active): called after every step with the time reached and NumPy copies (a download; None: none).
+    Returns (T_final, active mask, number of ADI steps), all host side, then the final liquid fraction, history_result and
+    solidification_result for those that were asked for, in this order."""
+    nx, ny, nz = base_mask.shape
+    grid = backend.Grid3D(nx, ny, nz, dx, np.array(base_mask, dtype=bool))
+    mat = backend.Material(*mat_args)
+    params = backend.Params(dt=dt, theta=theta)
+    T = np.full((nx, ny, nz), float(Tinf), dtype=np.float64)
+    if _is_device_backend(backend):
+        T = backend.to_device(T)
+    dev_loop = hasattr(backend, 'PathDeposit') and hasattr(backend, 'BirthPacks') and hasattr(T, 'fill_where')
+    if not dev_loop:
+        raise ValueError("run_path_deposition: needs the device loop of a backend with PathDeposit")
+    _require_device_loop('run_path_deposition', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
+                         history=history, solidification=solidification)
+    src = path.on_device() if hasattr(path, 'on_device') else path
+    dep = backend.PathDeposit(grid, src, bead, Ts, within=within)
+    steps = path_steps(src.t_start, src.t_end if t_end is None else float(t_end), float(dt))
+    robin = {f: h for f in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')}
+    bpacks = backend.BirthPacks(grid, mat, robin_h=robin) if surface_loss is None else \
+        backend.LossPacks(grid, mat, surface_loss, Tinf)
+    packs = bpacks.packs
+    ph = backend.PhaseField(grid, mat, phase_change, T=T) if phase_change is not None else None
+    hist = backend.ThermalHistory(grid, history, capacity=max(1, len(steps)), T=T, t=src.t_start) if history is not None else None
+    sol = backend.SolidificationRecord(grid, solidification, T=T, t=src.t_start) if solidification is not None else None
+    kw = _extras_kw(None if surface_loss is None else bpacks, ph, hist, sol=sol)
+    live = bool(np.asarray(base_mask).any())
+    nsteps = 0
+    for t, d in steps:
+        rng = dep.deposit(T, t, d)
+        if rng is not None:                            # something could have been born: the planes that changed
+            packs = bpacks.update(*rng) if surface_loss is None else bpacks.rebuild(T, *rng)
+            _sync_extras(T, ph, hist, sol)
+            live = True
+        if live:
+            params.dt = d
+            S = src.sample_step_device(grid, t, d) if heat else None
+            T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=S, t=t, **kw)
+            nsteps += 1
+        else:
+            for x in (hist, sol):
+                if x is not None:
+                    x.t = x.t + d                      # (the global time moves on all the same)
+        if on_frame is not None:
+            on_frame(t + d, np.asarray(T), grid.d_mask.cpu().contiguous().numpy().astype(bool))
+    res = (np.asarray(T), grid.d_mask.cpu().contiguous().numpy().astype(bool), nsteps)
+    res = res + (() if ph is None else (np.asarray(ph.liquid_fraction),))
+    res = res if hist is None else res + (history_result(hist),)
+    return res if sol is None else res + (solidification_result(sol),)
 
 
 def ring_source(heat_source, R_in, wall, z_top, tau):

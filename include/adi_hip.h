@@ -699,6 +699,53 @@ int adi_scan_sample(const adi_scan_shape *h_shape, const double *d_table, int K,
                     int ny, int nz, long plane_stride, double dx, double t, double dt, double *d_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Bead deposition along a scan path: the cells a path brings to life during a step [t, t + dt].  A segment of the table
+ * above DEPOSITS when its power is > 0 and its speed is > 0 (jumps, idle dwells and dwells with power lay nothing).  For the
+ * piece (ta, tb) of a depositing segment inside the step (times since the segment's start) and a cell centre x, with da the
+ * depth axis and (u, v) the in-plane axes, one fp64 operation each and no contraction:
+ *     ou = x_u - p_u;  ov = x_v - p_v;  z = x_da - p_da
+ *     xi0 = ou*d0 + ov*d1;  y = ov*d0 - ou*d1
+ *     sa = speed*ta;  sb = speed*tb;  xc = min(max(xi0, sa), sb);  e = xi0 - xc
+ *     r2 = e*e + y*y;  half = 0.5*width;  h2 = half*half
+ *     cap = height (box)  or  height*(1 - r2/h2) (parabola)
+ *     inside = r2 <= h2  and  z <= 0  and  -z <= cap
+ * the cells within width/2 of the path travelled (round ends, closed corners) and at most `cap` below the path's depth
+ * coordinate, which is the TOP of the bead.  The result of a step is
+ *     born = (OR of inside over the pieces of the step) and within (where given) and not active, inside the logical box;
+ * newborn cells get T = Ts and active = 1, every other cell of T and of the mask keeps its bits.  A cell beside a cut of the
+ * step is clamped to e = 0 by one of the two pieces, so the union of born over any partition of an interval into steps is
+ * that of one step over the whole interval.  The host definition is deposition.PathDeposit.reference; csrc/adi_bead_eval.hpp
+ * follows it operation for operation on the host and on the device.
+ *
+ * Every argument is checked before any HIP call (ADI_ERR_ARG): the shape (finite width and height > 0, profile 0 or 1,
+ * depth_axis 0..2), the host table by the rules above, the grid, finite t, dt > 0, finite Ts, the logical box inside the
+ * physical one, an active mask that is not `within`.  The index box of a step reaches width/2 (1 + 1e-9) in the plane around
+ * both ends of every piece and [p_da - height (1 + 1e-9), p_da] in depth, converted by floor / ceil(x / dx - 0.5) and clipped
+ * to the logical grid; the device entry computes it itself from the HOST table, so no caller can pass a box.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct adi_bead_shape {
+    double width, height;    /* [m] */
+    int profile;             /* 0 box, 1 parabola */
+    int depth_axis;
+} adi_bead_shape;
+
+/* host, no HIP call: index box [i0,i1) x [j0,j1) x [k0,k1) of the LOGICAL grid (box = { i0, i1, j0, j1, k0, k1 }) that holds
+ * every cell the step can bear; *deposits = 0 and an empty box when no segment deposits in [t, t + dt] */
+int adi_bead_index_box(const adi_bead_shape *shape, const double *h_table, int K, double t_end, int nx, int ny, int nz,
+                       double dx, double t, double dt, int box[6], int *deposits);
+/* the evaluator on the CPU over dense C-order (nx, ny, nz) HOST arrays (h_active, h_within: NULL for "no cell is active" /
+ * "every cell may be born"): h_born = 1 on the newborn cells, 0 elsewhere.  No HIP call. */
+int adi_bead_deposit_host(const adi_bead_shape *shape, const double *h_table, int K, double t_end, const uint8_t *h_active,
+                          const uint8_t *h_within, int nx, int ny, int nz, double dx, double t, double dt, uint8_t *h_born);
+/* the births of the step on the device: (lx, ly, lz) the logical box inside the physical (nx, ny, nz, plane_stride) of d_T,
+ * d_active and d_within (box layout; d_within NULL: every cell may be born); h_table and d_table the same K rows on the host
+ * and in device memory.  *d_newborn is zeroed here and then counted with 64-bit integer atomics, as adi_birth_planes does.  An
+ * empty index box launches nothing. */
+int adi_bead_deposit(const adi_bead_shape *shape, const double *h_table, const double *d_table, int K, double t_end, double *d_T,
+                     uint8_t *d_active, const uint8_t *d_within, int lx, int ly, int lz, int nx, int ny, int nz,
+                     long plane_stride, double dx, double t, double dt, double Ts, unsigned long long *d_newborn, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Temperature-dependent surface loss of the Cartesian step (no counterpart in the reference, which freezes robin_h when the
  * packs are built; it accepts per-voxel robin_h, so the lagged law below is a sequence of calls the reference can run).
  * Before a step the Robin coefficient of every exposed cell is rewritten from the cell's own temperature T (degrees, the
