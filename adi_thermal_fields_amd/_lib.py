@@ -205,6 +205,15 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p]),
     'adi_cyl_step_src': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p]),
     'adi_cyl_sweep_src': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p]),
+    'adi_matmap_build_coeffs': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_int, c_double_p,
+                                        c_int_p, c_double_p, c_void_pp, c_int_p, c_double_p, c_void_pp, c_void_pp, c_void_pp,
+                                        c_void_p]),
+    'adi_matmap_explicit': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_double_p,
+                                    c_double_p, c_double, c_double, c_void_p, c_void_p]),
+    'adi_matmap_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, c_long, ctypes.POINTER(c_size_t)]),
+    'adi_matmap_sweep': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                 c_int, c_int, c_long, c_int, c_double_p, c_double, c_double, c_double, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
     'adi_ctx_create': (c_int, [c_int, c_int, c_int, c_double, c_int, c_void_pp]),
     'adi_ctx_destroy': (c_int, [c_void_p]),
     'adi_ctx_set_mask': (c_int, [c_void_p, c_void_p]),
@@ -228,6 +237,7 @@ SCAN_TABLE_COLS = 8         # ADI_SCAN_TABLE_COLS: { t_begin, p[3], d[2], speed,
 SURFACE_LOSS_MAX_KNOTS = 16  # ADI_SURFACE_LOSS_MAX_KNOTS
 SURFACE_LOSS_SIGMA = 5.670374419e-8   # ADI_SURFACE_LOSS_SIGMA (Stefan-Boltzmann, CODATA 2018)
 MATLAW_MAX_KNOTS = 16        # ADI_MATLAW_MAX_KNOTS
+MATMAP_MAX = 8               # ADI_MATMAP_MAX: materials per grid
 HISTORY_BLOCK_BYTES = 40     # ADI_HISTORY_BLOCK_BYTES: { double t0, dt; int64 n, slot, capacity }
 HISTORY_LOG_INTS = 8         # ADI_HISTORY_LOG_INTS: { cells, lo[3], hi[3], pad }
 BRICK = 16                   # kBrick (csrc/adi_cart_dev.hpp): the edge of a brick of the flags summary

@@ -27,7 +27,8 @@ mask (and its neighbour-flags digest) is refreshed on every `grid.mask = ...` as
 precompute_coeff_packs_unified(grid, ...) call, which is the documented synchronisation point.
 
 Where things live: this module defines nothing, it re-exports.  fields.py -- Layout, DeviceField, to_device, Grid3D and the
-device helpers; packs.py -- Material, Params, AxisCoeffPack, exposed_mask, precompute_coeff_packs_unified; heat_source.py --
+device helpers; packs.py -- Material, Params, AxisCoeffPack, exposed_mask, precompute_coeff_packs_unified, MaterialMap (several
+materials in one grid); heat_source.py --
 GoldakSource, ScanPath, ScanPathSource and the one host definition of Goldak's double ellipsoid; deposition.py -- the surface impulse, the
 perimeter ratio, birth_planes, BirthPacks, BeadProfile, PathDeposit (births along a scan path); surface_loss.py -- SurfaceLoss, LossPacks; phase.py -- PhaseChange, PhaseField, MaterialLaw, NonlinearPacks;
 history.py -- HistoryLevels, ThermalHistory, SolidificationRecord; step.py -- the stage entry points, the launch sequence, adi_step_hip_coeff,
@@ -40,7 +41,7 @@ from ._facade import ReExporting
 from ._lib import lib, check, ptr_array
 from .fields import (_MASK_VERSIONS, _device, _stream, _p, _sweep_workspace_bytes, recommended_dims, Layout, DeviceField,
                      to_device, Grid3D, _wrap)
-from .packs import Material, Params, AxisCoeffPack, exposed_mask, _fc_arg, precompute_coeff_packs_unified
+from .packs import Material, Params, AxisCoeffPack, exposed_mask, _fc_arg, precompute_coeff_packs_unified, MaterialMap
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .deposition import (apply_surface_impulse_Q, exposed_faces_per_layer, count_exposed_faces, perimeter_ratio, birth_planes,
                          BirthPacks, BeadProfile, PathDeposit)
@@ -57,7 +58,7 @@ __all__ = ['Grid3D', 'Material', 'Params', 'AxisCoeffPack', 'exposed_mask', 'pre
            'exposed_faces_per_layer', 'count_exposed_faces', 'perimeter_ratio', 'birth_planes', 'BirthPacks',
            'GoldakSource', 'ScanPath', 'SurfaceLoss', 'LossPacks', 'PhaseChange', 'PhaseField', 'HistoryLevels',
            'ThermalHistory']
-# (ScanPathSource, BeadProfile, PathDeposit, MaterialLaw, NonlinearPacks and SolidificationRecord are exported like the names above but are not part of the pinned `__all__`)
+# (ScanPathSource, BeadProfile, PathDeposit, MaterialLaw, NonlinearPacks, SolidificationRecord and MaterialMap are exported like the names above but are not part of the pinned `__all__`)
 
 # an assignment to a name above reaches the module that defined it (_facade.ReExporting)
 sys.modules[__name__].__class__ = ReExporting

@@ -8,7 +8,7 @@ from . import _lib
 from ._lib import lib, check
 from ._ledger import PromiseLedger
 from .fields import DeviceField, _as_state, _wrap, _p, _stream
-from .packs import _fc_arg
+from .packs import _fc_arg, MaterialMap
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .surface_loss import LossPacks
 from .phase import PhaseField, NonlinearPacks
@@ -128,9 +128,26 @@ def _ensure_general(pack):
         pack.d_qflux = L.empty(zero=True)
 
 
-def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material=None, solidification=None):
+def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material=None, solidification=None,
+                  material_map=None):
     """TypeError / ValueError for an optional argument of the step that is of the wrong kind or was made for other packs, another
     grid or another cp: once per adi_step_hip_coeff call and once per StagedStepper, before anything is launched"""
+    if material_map is not None:
+        if not isinstance(material_map, MaterialMap):
+            raise TypeError("material_map must be a MaterialMap")
+        if material_map.grid is not grid:
+            raise ValueError("material_map: the MaterialMap belongs to another grid")
+        if len(packs) != 3 or any(p is not q for p, q in zip(packs, material_map.packs)):
+            raise ValueError("material_map: the step must be given the MaterialMap's own packs (material_map.packs)")
+        m = material_map.mat
+        if (float(mat.rho), float(mat.cp), float(mat.k)) != (m.rho, m.cp, m.k):
+            raise ValueError("material_map: the step must be given the MaterialMap's own material (material_map.mat)")
+        if source is not None:
+            raise ValueError("material_map: a GoldakSource object cannot be combined with it (its sweep-0 correction assumes "
+                             "uniform coupling); pass the source as a field, S=path.sample_step(grid, t, dt)")
+        if surface_loss is not None or phase is not None or material is not None:
+            raise ValueError("material_map: surface_loss= / phase= / material= cannot be combined with it; each assumes one cp")
+        material_map._check_fresh()
     if material is not None:
         if not isinstance(material, NonlinearPacks):
             raise TypeError("material must be a NonlinearPacks")
@@ -182,7 +199,7 @@ def _no_mark():
 
 def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, source=None, owner=None, t_set=None,
                  surface_loss=None, phase=None, history=None, captured=False, mark=_no_mark, material=None,
-                 solidification=None):
+                 solidification=None, material_map=None):
     """THE launch sequence of one step t_in -> out (fp64 tensors in the grid's layout; nothing is allocated): the surface-loss
     update from t_in, the explicit stage and sweep 0 (one launch when `fused`), the moving source's correction of sweep 0's
     output, sweeps 1 and 2, the latent-heat correction of `out`, the history record, the solidification record.  With `material` (a NonlinearPacks): its
@@ -197,8 +214,20 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
     correction, and the history and the solidification record launch their records without moving their host clocks.  Otherwise
     no tick, and history.record / solidification.record.
     mark: called at the stage boundaries of per-stage timing: before the explicit stage, between it and sweep 0 when they are
-    two launches, after sweep 0 with the source's correction, after sweep 1 and after sweep 2."""
+    two launches, after sweep 0 with the source's correction, after sweep 1 and after sweep 2.
+    material_map: a MaterialMap: the explicit stage (with d_S, if any) and the three sweeps are ITS four launches
+    (adi_matmap_explicit, adi_matmap_sweep), never fused; history and solidification follow as ever."""
     (ta, tb), _, _ = grid.scratch(2)
+    if material_map is not None:
+        material_map._check_fresh()
+        mark()
+        material_map._explicit_into(t_in, d_S, ta, params)
+        for axis, (a, b) in enumerate(((ta, tb), (tb, ta), (ta, out))):
+            mark()
+            material_map._sweep_into(axis, a, b, params, Tinf)
+        mark()
+        _record_step(t_in, out, params, history, solidification, captured)
+        return
     u = t_in                                               # what the linear step runs on
     if material is not None:
         u, Tinf = material.begin(t_in), material.theta_inf
@@ -231,6 +260,11 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
         material.recover(t_in, out)
     if phase is not None:
         phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
+    _record_step(t_in, out, params, history, solidification, captured)
+
+
+def _record_step(t_in, out, params, history, solidification, captured):
+    """the last launches of a step: the history record, then the solidification record (see _launch_step, `captured`)"""
     if history is not None:
         if captured:
             history._launch_record(t_in, out)
@@ -244,7 +278,7 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
 
 
 def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None, phase=None, history=None,
-                       material=None, solidification=None):
+                       material=None, solidification=None, material_map=None):
     """adi3d_numba_coeff.py:290-302 / adi3d_gpu_coeff.py:213-230: explicit stage, then the three
     implicit sweeps in the order axis 0, 1, 2.  Returns a NEW array of the kind it was given;
     `Tn` is never modified.
@@ -273,12 +307,16 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     `phase` or the recovery of `material`) get their crossing time, cooling rate and squared gradient at the recorder's own
     clock, which moves on by dt (adi_solid_record and adi_history_tick on its block, the last launches, after `history`'s).
     None: no such launch.
+    material_map: a MaterialMap of the grid, with `packs` its `.packs` and `mat` its `.mat`: several materials in one grid, a
+    material id per cell.  The step is then four launches of its own kernels -- explicit stage, sweeps 0, 1, 2 -- whose couplings
+    come from the map's pair table.  Combines with S= as a field and with history= and solidification=; not with a
+    GoldakSource object, surface_loss=, phase= or material=.  None: the launches of before.
     Every optional argument is checked before the first launch (_check_extras); the launches are _launch_step's."""
     if isinstance(S, (ScanPath, ScanPathSource)):
         raise TypeError("adi_step_hip_coeff: a scan path enters the step as its field: S=path.sample_step(grid, t, dt) from the "
                         "host, or S=path.on_device().sample_step_device(grid, t, dt) evaluated on the device")
     source = S if isinstance(S, GoldakSource) else None
-    _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification)
+    _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification, material_map)
     if history is not None:
         history._check_mask()
     t_in, kind = _as_state(Tn, grid)
@@ -289,7 +327,8 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
         d_S = grid.layout.to_layout(S, torch.float64)
     out = grid.layout.empty()
     _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused_supported(grid), d_S=d_S, source=source, owner=grid, t_set=t,
-                 surface_loss=surface_loss, phase=phase, history=history, material=material, solidification=solidification)
+                 surface_loss=surface_loss, phase=phase, history=history, material=material, solidification=solidification,
+                 material_map=material_map)
     return _wrap(out, kind)
 
 
@@ -329,8 +368,8 @@ class StagedStepper:
     the same way."""
 
     def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None, surface_loss=None, phase=None,
-                 history=None, material=None, solidification=None):
-        _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification)
+                 history=None, material=None, solidification=None, material_map=None):
+        _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification, material_map)
         self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
         # temperature-dependent surface loss: the packs' Robin coefficients rewritten from the step's INPUT buffer, the first
         # launch of every step -- captured with it (X -> Y reads X, Y -> X reads Y); the law travels by value in that launch,
@@ -349,12 +388,20 @@ class StagedStepper:
         # recovery of its OUTPUT buffer after sweep 2 -- captured with it; the laws and the ambient travel by value, the
         # Kirchhoff field by pointer, so all are part of run()'s graph key.  Stateless: the warm-up steps need no snapshot
         self.material = material
+        # several materials: the step's four launches are the MaterialMap's; its pair table travels by value in them (so dt and
+        # theta, already in run()'s graph key, cover it) and its id field by pointer: graph_key() is part of the key
+        self.material_map = material_map
         # moving source: corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step counter
         # a captured tick advances -- power, origin, velocity, eta and f_f may change between runs without a new graph
         self.source = source
         self.captures = 0              # HIP graphs captured by run() so far
         self.fused = fused_supported(grid) if fused is None else (bool(fused) and fused_supported(grid))
-        if self.fused:
+        if material_map is not None:
+            self.fused = False
+            self.stage_names = ['matmap_explicit', 'matmap_sweep_axis0', 'matmap_sweep_axis1', 'matmap_sweep_axis2']
+            per_line = [n > 1024 for n in grid.layout.pd[:3]]
+            self.stage_bytes_per_cell = [18.0] + [18.0 + (32.0 if t else 0.0) for t in per_line]
+        elif self.fused:
             # the fused kernel reads T + flags (+ the pack arrays of the axis-0 sweep) and writes U: the sweep's own
             # byte count (SURVEY.md 8(d) variant rule); R0 never reaches HBM
             self.stage_names = ['explicit+sweep_axis0', 'sweep_axis1', 'sweep_axis2_contig']
@@ -373,7 +420,7 @@ class StagedStepper:
         """one step t -> out (both native-layout device tensors), no allocation: what a HIP graph captures"""
         _launch_step(t, out, self.grid, self.mat, self.params, self.packs, self.Tinf, self.fused, source=self.source, owner=self,
                      surface_loss=self.surface_loss, phase=self.phase, history=self.history, captured=captured, mark=mark,
-                     material=self.material, solidification=self.solidification)
+                     material=self.material, solidification=self.solidification, material_map=self.material_map)
 
     def run(self, T, nsteps, graph=True, t0=0.0):
         """The drivers' `nsub` loop (quick_compare_dirichlet_robin.py:169-178, waam_from_stl_v7_mm.py:525-528): `nsteps`
@@ -394,7 +441,8 @@ class StagedStepper:
                None if self.phase is None else self.phase.graph_key(),
                None if self.history is None else self.history.graph_key(),
                None if self.material is None else self.material.graph_key(),
-               None if self.solidification is None else self.solidification.graph_key())
+               None if self.solidification is None else self.solidification.graph_key(),
+               None if self.material_map is None else self.material_map.graph_key())
         clocked = [x for x in (self.history, self.solidification) if x is not None]   # the recorders: each its own clock
         for x in clocked:
             x._check_mask()

@@ -1015,6 +1015,48 @@ int adi_cyl_sweep_src(const adi_cyl_plan *plan, int axis, void *d_block, const d
                       const uint8_t *d_active, double T_void, double T_inner, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Several materials in one grid.  Every in-mask cell carries a material id (d_ids: one uint8 per
+ * cell in the layout of the fields, < nmat on in-mask cells; an id off the mask is never read).  nmat <= ADI_MATMAP_MAX
+ * materials with C_m = rho_m cp_m (h_C: nmat doubles) and the pair table h_G: ADI_MATMAP_MAX x ADI_MATMAP_MAX doubles, row m
+ * = the cell's own material,
+ *     kf(m, m) = k_m,   kf(m, n) = (2 k_m k_n) / (k_m + k_n)   (two half-cells in series),
+ *     G[m][n] = (kf(m, n) dt) / (C_m (dx dx)),
+ * computed by the caller in fp64 and carried by value in every launch (entries beyond nmat are not read).
+ *   explicit stage, in-mask cells (off the mask R0 = T):
+ *     R0_i = T_i + (1 - theta) sum over axis 0 -, 0 +, 1 -, 1 +, 2 -, 2 + where that neighbour n is in the mask of
+ *            G[id_i][id_n] (T_n - T_i)   [ + (dt S_i) / C_{id_i} ]
+ *   sweep along `axis`, whole grid lines in the full-length identity-row form:
+ *     free cell (in the mask, not Dirichlet)   (e + p + q) x_i - p x_{i-1} - q x_{i+1} = d,
+ *         e = 1 + dt coeff_i,   d = in_i + dt qflux_i + dt coeff_i Tinf,
+ *         p = theta G[id_i][id_{i-1}] where the lower neighbour is in the mask, else 0;  q likewise with the upper one
+ *     Dirichlet cell   x = dir_value          off-mask cell   x = in
+ *   The rows either side of a material interface differ (each is divided by its own C): not symmetric, strictly row-dominant.
+ *   packs: coeff_i = sum over the exposed faces of the axis, '-' then '+', of (h (dx dx)) / (C_{id_i} (dx dx dx)); qflux alike.
+ * Every entry point validates its arguments before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADI_MATMAP_MAX 8
+/* adi_build_coeffs with the id field and the C table; the arrays are zero wherever a cell is not exposed along the axis */
+int adi_matmap_build_coeffs(const uint8_t *d_mask, const uint8_t *d_ids, int nx, int ny, int nz, long plane_stride, double dx,
+                            int nmat, const double *h_C, const int *h_mode, const double *h_scalar,
+                            const double *const *d_h_field, const int *q_mode, const double *q_scalar,
+                            const double *const *d_q_field, double *const *d_coeff, double *const *d_qflux, void *stream);
+/* R0 into d_out (must not alias d_T); d_S (optional): source field in W/m^3 */
+int adi_matmap_explicit(const double *d_T, const double *d_S, const uint8_t *d_flags, const uint8_t *d_ids, int nx, int ny,
+                        int nz, long plane_stride, int nmat, const double *h_G, const double *h_C, double dt, double theta,
+                        double *d_out, void *stream);
+/* bytes of workspace adi_matmap_sweep needs along `axis` (0: none).  Lines of at most 1024 rows are solved in registers
+ * (segments of a line per thread: tiles of adjacent lines along axes 0 and 1, the lanes of a wave along axis 2); longer lines by
+ * one thread per line with one field of doubles in the workspace. */
+int adi_matmap_workspace_bytes(int axis, int nx, int ny, int nz, long plane_stride, size_t *bytes);
+/* one sweep; `variant` as in adi_sweep (which of dir_mask / dir_val / qflux are read).  coeff / qflux are read only on free
+ * cells exposed along the axis (the arrays of adi_matmap_build_coeffs for the mask d_flags describes), dir_val on Dirichlet
+ * cells.  d_out must not alias d_in or the workspace. */
+int adi_matmap_sweep(int axis, int variant, const double *d_in, const uint8_t *d_flags, const uint8_t *d_ids,
+                     const double *d_coeff, const uint8_t *d_dir_mask, const double *d_dir_val, const double *d_qflux, int nx,
+                     int ny, int nz, long plane_stride, int nmat, const double *h_G, double dt, double theta, double Tinf,
+                     double *d_out, void *d_work, size_t work_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Context API: the library owns the device memory; callers hand over HOST arrays.
  * One context per GPU and thread; no hidden global state.
  * ---------------------------------------------------------------------------------------------- */

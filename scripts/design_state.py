@@ -35,6 +35,15 @@ FOOT = [
     ('adi::k_sweep_strided<8, true, true, true, false, 2, false, true>', 'fused GENERAL kernel draining the FAST kernel\'s queue'),
     ('adi::k_sweep_strided<8, true, true, false, true, 0, true, false>', 'axis-1 GENERAL kernel with the deferred slab correction'),
     ('adi::k_explicit_v5<2, false>', 'explicit stage as its own kernel'),
+    ('adi::k_matmap_explicit', 'several materials (section 6l): explicit stage, 18 B/cell'),
+    ('adi::k_matmap_sweep_strided<8, false, false>', 'several materials: sweep of axes 0 / 1, 8-row segments in registers, off-diagonals as table indices, 18 B/cell'),
+    ('adi::k_matmap_sweep_strided<8, true, true>', 'the same with Dirichlet cells and a flux array'),
+    ('adi::k_matmap_sweep_strided<16, true, true>', 'the same, 16 rows per thread (513 - 1024 rows): one 512-thread workgroup per CU'),
+    ('adi::k_matmap_sweep_contig<8, false, false>', 'several materials: sweep of axis 2 in registers, 8 rows per lane, 18 B/cell'),
+    ('adi::k_matmap_sweep_contig<8, true, true>', 'the same with Dirichlet cells and a flux array'),
+    ('adi::k_matmap_sweep_contig<16, true, true>', 'the same, 16 rows per lane (513 - 1024 rows): one wave per SIMD'),
+    ('adi::k_matmap_sweep_lines<true, true>', 'several materials: lines beyond 1024 rows, one thread per line, 50 B/cell'),
+    ('adi::k_matmap_build_coeffs', 'several materials: the coefficient build'),
 ]
 
 
