@@ -200,6 +200,10 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
     'adi_solid_seed': (c_int, [c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                c_int, c_int, c_long, c_void_p]),
+    'adi_monitor_record': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int,
+                                   c_int_p, c_int, c_int_p, c_void_p, c_int, c_double_p, c_void_p, c_long, c_void_p, c_long,
+                                   c_void_p]),
+    'adi_monitor_reset_log': (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p]),
     'adi_cyl_source_set': (c_int, [c_void_p, c_void_p, c_double, c_double, ctypes.c_longlong, c_void_p]),
     'adi_cyl_source_sample': (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double, c_double,
                                       c_void_p, c_void_p, c_void_p]),
@@ -240,7 +244,11 @@ MATLAW_MAX_KNOTS = 16        # ADI_MATLAW_MAX_KNOTS
 MATMAP_MAX = 8               # ADI_MATMAP_MAX: materials per grid
 HISTORY_BLOCK_BYTES = 40     # ADI_HISTORY_BLOCK_BYTES: { double t0, dt; int64 n, slot, capacity }
 HISTORY_LOG_INTS = 8         # ADI_HISTORY_LOG_INTS: { cells, lo[3], hi[3], pad }
-BRICK = 16                   # kBrick (csrc/adi_cart_dev.hpp): the edge of a brick of the flags summary
+MONITOR_MAX_REGIONS = 8      # ADI_MONITOR_MAX_REGIONS
+MONITOR_MAX_PROBES = 256     # ADI_MONITOR_MAX_PROBES
+MONITOR_REGION_WORDS = 6     # ADI_MONITOR_REGION_WORDS: { cells, T_min, T_max, sum_T, sum_wT, sum_extra }
+MONITOR_PARTIAL_WORDS = 6    # ADI_MONITOR_PARTIAL_WORDS
+BRICK = 16                # kBrick (csrc/adi_cart_dev.hpp): the edge of a brick of the flags summary
 STLCORR_DROPPED = (1 << 63) - 1   # ADI_STLCORR_DROPPED
 STLCORR_MAX_SUBDIV = 4096    # ADI_STLCORR_MAX_SUBDIV
 

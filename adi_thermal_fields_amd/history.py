@@ -231,6 +231,23 @@ class ThermalHistory(_SeededForMask):
                     volume=cells * dx ** 3, dropped=max(0, slot - self.capacity))
 
 
+# ---- what the step asks of a monitor (monitor.py: FieldMonitor) ------------------------------------------
+class _StepMonitor:
+    """The part of a monitor the step drives, kept here so that step.py can name it: a device block of the history's layout
+    (`d_block`), the host clock `.t` and the end times `_times` of the recorded steps.  The owner supplies
+    `_launch_record(t_in, t_out)` (its record and the tick), `record`, `snapshot`, `restore`, `graph_key`, `_check_mask`, and
+    the attributes `grid` and `material_map`."""
+
+    def set_clock(self, dt):
+        """the block's clock from the host clock: t0 = .t, this dt, n = 0 (the log slot stays)"""
+        check(lib.adi_history_set_clock(_p(self.d_block), self.t, float(dt), _stream()))
+
+    def advance_clock(self, t0, dt, nsteps):
+        """host side of `nsteps` recorded steps of dt from t0: their end times join the log's, .t = t0 + nsteps*dt"""
+        self._times.extend(t0 + (n + 1) * dt for n in range(nsteps))
+        self.t = t0 + nsteps * dt
+
+
 # ---- the freezing front: thermal gradient and cooling rate at solidification (include/adi_hip.h, DESIGN.md section 6k) --------
 class SolidificationRecord(_SeededForMask):
     """The conditions at the solidification front of a grid, on the device: per cell, taken at the moment the cell last froze

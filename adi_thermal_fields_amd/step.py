@@ -12,7 +12,7 @@ from .packs import _fc_arg, MaterialMap
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .surface_loss import LossPacks
 from .phase import PhaseField, NonlinearPacks
-from .history import ThermalHistory, SolidificationRecord
+from .history import ThermalHistory, SolidificationRecord, _StepMonitor
 
 
 def _gam(grid, mat, params):
@@ -129,7 +129,7 @@ def _ensure_general(pack):
 
 
 def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material=None, solidification=None,
-                  material_map=None):
+                  material_map=None, monitor=None):
     """TypeError / ValueError for an optional argument of the step that is of the wrong kind or was made for other packs, another
     grid or another cp: once per adi_step_hip_coeff call and once per StagedStepper, before anything is launched"""
     if material_map is not None:
@@ -191,6 +191,13 @@ def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history
         if solidification.grid is not grid:
             raise ValueError("solidification: the SolidificationRecord belongs to another grid")
         solidification._check_mask()
+    if monitor is not None:
+        if not isinstance(monitor, _StepMonitor):
+            raise TypeError("monitor must be a FieldMonitor")
+        if monitor.grid is not grid:
+            raise ValueError("monitor: the FieldMonitor belongs to another grid")
+        if monitor.material_map is not material_map:
+            raise ValueError("monitor: the FieldMonitor's material_map is not the step's")
 
 
 def _no_mark():
@@ -199,7 +206,7 @@ def _no_mark():
 
 def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, source=None, owner=None, t_set=None,
                  surface_loss=None, phase=None, history=None, captured=False, mark=_no_mark, material=None,
-                 solidification=None, material_map=None):
+                 solidification=None, material_map=None, monitor=None):
     """THE launch sequence of one step t_in -> out (fp64 tensors in the grid's layout; nothing is allocated): the surface-loss
     update from t_in, the explicit stage and sweep 0 (one launch when `fused`), the moving source's correction of sweep 0's
     output, sweeps 1 and 2, the latent-heat correction of `out`, the history record, the solidification record.  With `material` (a NonlinearPacks): its
@@ -216,7 +223,8 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
     mark: called at the stage boundaries of per-stage timing: before the explicit stage, between it and sweep 0 when they are
     two launches, after sweep 0 with the source's correction, after sweep 1 and after sweep 2.
     material_map: a MaterialMap: the explicit stage (with d_S, if any) and the three sweeps are ITS four launches
-    (adi_matmap_explicit, adi_matmap_sweep), never fused; history and solidification follow as ever."""
+    (adi_matmap_explicit, adi_matmap_sweep), never fused; history and solidification follow as ever.
+    monitor: a FieldMonitor: its record of `out` and its tick are the last launches of all, after solidification's."""
     (ta, tb), _, _ = grid.scratch(2)
     if material_map is not None:
         material_map._check_fresh()
@@ -226,7 +234,7 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
             mark()
             material_map._sweep_into(axis, a, b, params, Tinf)
         mark()
-        _record_step(t_in, out, params, history, solidification, captured)
+        _record_step(t_in, out, params, history, solidification, captured, monitor)
         return
     u = t_in                                               # what the linear step runs on
     if material is not None:
@@ -260,11 +268,12 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
         material.recover(t_in, out)
     if phase is not None:
         phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
-    _record_step(t_in, out, params, history, solidification, captured)
+    _record_step(t_in, out, params, history, solidification, captured, monitor)
 
 
-def _record_step(t_in, out, params, history, solidification, captured):
-    """the last launches of a step: the history record, then the solidification record (see _launch_step, `captured`)"""
+def _record_step(t_in, out, params, history, solidification, captured, monitor=None):
+    """the last launches of a step: the history record, then the solidification record, then the monitor's, which reads the
+    step's final field alone (see _launch_step, `captured`)"""
     if history is not None:
         if captured:
             history._launch_record(t_in, out)
@@ -275,10 +284,15 @@ def _record_step(t_in, out, params, history, solidification, captured):
             solidification._launch_record(t_in, out)
         else:
             solidification.record(t_in, out, params.dt)
+    if monitor is not None:
+        if captured:
+            monitor._launch_record(t_in, out)
+        else:
+            monitor.record(out, params.dt)
 
 
 def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None, phase=None, history=None,
-                       material=None, solidification=None, material_map=None):
+                       material=None, solidification=None, material_map=None, monitor=None):
     """adi3d_numba_coeff.py:290-302 / adi3d_gpu_coeff.py:213-230: explicit stage, then the three
     implicit sweeps in the order axis 0, 1, 2.  Returns a NEW array of the kind it was given;
     `Tn` is never modified.
@@ -311,12 +325,16 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     material id per cell.  The step is then four launches of its own kernels -- explicit stage, sweeps 0, 1, 2 -- whose couplings
     come from the map's pair table.  Combines with S= as a field and with history= and solidification=; not with a
     GoldakSource object, surface_loss=, phase= or material=.  None: the launches of before.
+    monitor: a FieldMonitor of the grid (with the step's material_map, if any): the result's value at its probes and the count,
+    extrema and sums of its regions become one row of its device log, and its clock moves on by dt (adi_monitor_record and
+    adi_history_tick on its block, the last launches of all).  Combines with every other argument.  None: no such launch.
     Every optional argument is checked before the first launch (_check_extras); the launches are _launch_step's."""
     if isinstance(S, (ScanPath, ScanPathSource)):
         raise TypeError("adi_step_hip_coeff: a scan path enters the step as its field: S=path.sample_step(grid, t, dt) from the "
                         "host, or S=path.on_device().sample_step_device(grid, t, dt) evaluated on the device")
     source = S if isinstance(S, GoldakSource) else None
-    _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification, material_map)
+    _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification, material_map,
+                  monitor)
     if history is not None:
         history._check_mask()
     t_in, kind = _as_state(Tn, grid)
@@ -328,7 +346,7 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     out = grid.layout.empty()
     _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused_supported(grid), d_S=d_S, source=source, owner=grid, t_set=t,
                  surface_loss=surface_loss, phase=phase, history=history, material=material, solidification=solidification,
-                 material_map=material_map)
+                 material_map=material_map, monitor=monitor)
     return _wrap(out, kind)
 
 
@@ -365,11 +383,13 @@ class StagedStepper:
     the last launches of every step; `run` sets the recorder's block from the recorder's own clock `history.t` (not from `t0`,
     which stays the source's time origin) and moves that clock on by nsteps*dt.  With `solidification=` (a SolidificationRecord
     of the grid) its record launch and tick come after those, the last launches of every step, on the recorder's own clock in
-    the same way."""
+    the same way.  With `monitor=` (a FieldMonitor of the grid) its record of the step's output and its tick are the last launches
+    of all, on the monitor's own clock in the same way."""
 
     def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None, surface_loss=None, phase=None,
-                 history=None, material=None, solidification=None, material_map=None):
-        _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification, material_map)
+                 history=None, material=None, solidification=None, material_map=None, monitor=None):
+        _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification, material_map,
+                      monitor)
         self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
         # temperature-dependent surface loss: the packs' Robin coefficients rewritten from the step's INPUT buffer, the first
         # launch of every step -- captured with it (X -> Y reads X, Y -> X reads Y); the law travels by value in that launch,
@@ -391,6 +411,9 @@ class StagedStepper:
         # several materials: the step's four launches are the MaterialMap's; its pair table travels by value in them (so dt and
         # theta, already in run()'s graph key, cover it) and its id field by pointer: graph_key() is part of the key
         self.material_map = material_map
+        # field monitor: the record of the step's OUTPUT buffer and the tick of its block, the last launches of all -- captured
+        # with them; probes, regions and weights travel by value and its buffers by pointer: part of run()'s graph key
+        self.monitor = monitor
         # moving source: corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step counter
         # a captured tick advances -- power, origin, velocity, eta and f_f may change between runs without a new graph
         self.source = source
@@ -420,7 +443,8 @@ class StagedStepper:
         """one step t -> out (both native-layout device tensors), no allocation: what a HIP graph captures"""
         _launch_step(t, out, self.grid, self.mat, self.params, self.packs, self.Tinf, self.fused, source=self.source, owner=self,
                      surface_loss=self.surface_loss, phase=self.phase, history=self.history, captured=captured, mark=mark,
-                     material=self.material, solidification=self.solidification, material_map=self.material_map)
+                     material=self.material, solidification=self.solidification, material_map=self.material_map,
+                     monitor=self.monitor)
 
     def run(self, T, nsteps, graph=True, t0=0.0):
         """The drivers' `nsub` loop (quick_compare_dirichlet_robin.py:169-178, waam_from_stl_v7_mm.py:525-528): `nsteps`
@@ -443,7 +467,9 @@ class StagedStepper:
                None if self.material is None else self.material.graph_key(),
                None if self.solidification is None else self.solidification.graph_key(),
                None if self.material_map is None else self.material_map.graph_key())
-        clocked = [x for x in (self.history, self.solidification) if x is not None]   # the recorders: each its own clock
+        if self.monitor is not None:                       # (without one the key is what it was)
+            key = key + (self.monitor.graph_key(),)
+        clocked = [x for x in (self.history, self.solidification, self.monitor) if x is not None]   # each its own clock
         for x in clocked:
             x._check_mask()
         st = getattr(self, '_graph', None)
@@ -458,7 +484,7 @@ class StagedStepper:
             self.source.set_block(_source_block(self), t0, prm.dt)
         if graph and nsteps >= 2 and st['g'] is None:
             g.scratch(2)                                   # every buffer exists before the capture
-            stateful = [x for x in (self.phase, self.history, self.solidification) if x is not None]
+            stateful = [x for x in (self.phase, self.history, self.solidification, self.monitor) if x is not None]
             held = [x.snapshot() for x in stateful]        # (the warm-up steps would advance f, the recorders, log and clocks)
             for x in clocked:
                 x.set_clock(prm.dt)

@@ -107,6 +107,21 @@ def solidification_result(rec):
     return dict(t_solid=np.asarray(rec.t_solid), cooling_rate=rate, G=G, R=R)
 
 
+def monitor_result(mon, mat):
+    """what the loops return of a FieldMonitor, two values: traces() and region_log(mat)"""
+    return mon.traces(), mon.region_log(mat)
+
+
+def _monitor(backend, grid, spec, rows, t=0.0):
+    """the FieldMonitor of a run from `spec`, a dict of its constructor's keyword arguments; the capacity is the run's"""
+    if spec is None:
+        return None
+    kw = dict(spec)
+    kw['capacity'] = max(1, int(rows))
+    kw.setdefault('t', t)
+    return backend.FieldMonitor(grid, **kw)
+
+
 def _is_device_backend(backend):
     return hasattr(backend, 'to_device')
 
@@ -114,15 +129,16 @@ def _is_device_backend(backend):
 def _require_device_loop(who, backend, dev_loop, **asked):
     """ValueError for an option (name = value) that is set where the loop cannot serve it"""
     for name, cls in (('surface_loss', 'LossPacks'), ('phase_change', 'PhaseField'), ('history', 'ThermalHistory'),
-                      ('material_law', 'NonlinearPacks'), ('solidification', 'SolidificationRecord')):
+                      ('material_law', 'NonlinearPacks'), ('solidification', 'SolidificationRecord'),
+                      ('monitor', 'FieldMonitor')):
         if asked.get(name) is not None and not (dev_loop and hasattr(backend, cls)):
             raise ValueError("%s: %s needs the device loop of a backend with %s" % (who, name, cls))
 
 
-def _extras_kw(lpacks, ph, hist, nm=None, sol=None):
+def _extras_kw(lpacks, ph, hist, nm=None, sol=None, mon=None):
     """the keywords of a step / a stepper for the extras that are present"""
     return {k: v for k, v in (('surface_loss', lpacks), ('phase', ph), ('history', hist), ('material', nm),
-                              ('solidification', sol)) if v is not None}
+                              ('solidification', sol), ('monitor', mon)) if v is not None}
 
 
 def _sync_extras(T, ph, hist, sol=None):
@@ -150,7 +166,7 @@ def _birth(backend, T, grid, newborn, Ts):
 
 def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, layers, times_birth, times_out,
                     on_frame=None, device_resident=True, device_loop=True, surface_loss=None, phase_change=None, history=None,
-                    solidification=None):
+                    solidification=None, monitor=None):
     """The event loop of waam_from_stl_v7_mm.py:515-550.  Returns (T_final as NumPy, number of ADI steps).
     surface_loss (a SurfaceLoss of the backend): the surface loses heat by that law, evaluated at the temperature at the start
     of every sub-step, in place of the constant `h` (which is then not used); device loop only.  None: the reference's loop.
@@ -163,7 +179,10 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     dict of history_result.  None: the loop without it, unchanged.
     solidification (T_freeze, a number): the conditions at the freezing front; one SolidificationRecord of the backend lives
     through the run on the global time like the history, and sync_mask(T) follows every birth; device loop only.  The return
-    value gains a last element (after history's), the dict of solidification_result.  None: the loop without it, unchanged."""
+    value gains a last element (after history's), the dict of solidification_result.  None: the loop without it, unchanged.
+    monitor (a dict of FieldMonitor's keyword arguments: probes, regions, extra): one FieldMonitor of the backend lives through
+    the run, sized from the schedule like the history, on the global time; stateless, so a birth needs no call; device loop
+    only.  The return value gains two last elements, its traces() and region_log(mat).  None: the loop without it, unchanged."""
     nx, ny, nz = mask_full.shape
     mask_act = np.zeros_like(mask_full, dtype=bool)
     grid = backend.Grid3D(nx, ny, nz, dx, mask_act)
@@ -186,7 +205,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         nonlocal T, nsteps
         nsub = max(1, int(math.ceil(seg / dt_cap)))
         params.dt = max(seg / nsub, 1e-15)
-        kw = _extras_kw(None if surface_loss is None else bpacks, ph, hist, sol=sol)
+        kw = _extras_kw(None if surface_loss is None else bpacks, ph, hist, sol=sol, mon=mon)
         if nsub >= GRAPH_MIN_NSUB and hasattr(backend, 'StagedStepper') and hasattr(T, 'fill_where'):
             # a long segment on the device backend: the nsub launches of this segment replayed from a HIP graph
             T = backend.StagedStepper(grid, mat, params, packs, Tinf, **kw).run(T, nsub)
@@ -205,8 +224,8 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     # output times and nothing waits for the device between births
     dev_loop = device_loop and device_resident and hasattr(backend, 'BirthPacks') and hasattr(T, 'fill_where')
     _require_device_loop('run_layer_birth', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
-                         history=history, solidification=solidification)
-    ph = hist = sol = None
+                         history=history, solidification=solidification, monitor=monitor)
+    ph = hist = sol = mon = None
     if dev_loop:
         import torch
         d_full = grid.layout.to_layout(mask_full, torch.uint8)
@@ -221,9 +240,11 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         plane_born = np.zeros(nz, dtype=bool)
         if phase_change is not None:
             ph = backend.PhaseField(grid, mat, phase_change)           # nothing is active yet: all solid
-        if history is not None:                                        # one log row per sub-step the schedule can ask for
+        if history is not None or monitor is not None:                 # one log row per sub-step the schedule can ask for
             rows = sum(max(1, int(math.ceil(a / dt_cap))) for w, a in layer_birth_schedule(times_birth, times_out)
                        if w == 'advance')
+        mon = _monitor(backend, grid, monitor, rows if monitor is not None else 1)
+        if history is not None:
             hist = backend.ThermalHistory(grid, history, capacity=max(1, rows), T=T)
         if solidification is not None:
             sol = backend.SolidificationRecord(grid, solidification, T=T)
@@ -260,7 +281,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
             if n_active > 0:                           # no ADI steps while nothing is active (:524)
                 advance(arg)
             else:
-                for x in (hist, sol):
+                for x in (hist, sol, mon):
                     if x is not None:
                         x.t = x.t + arg                # (the global time moves on all the same)
         elif what == 'birth':
@@ -269,7 +290,8 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
             on_frame(arg, np.asarray(T), d_act.cpu().contiguous().numpy().astype(bool) if dev_loop else mask_act.copy())
     res = (np.asarray(T), nsteps) + (() if ph is None else (np.asarray(ph.liquid_fraction),))
     res = res if hist is None else res + (history_result(hist),)
-    return res if sol is None else res + (solidification_result(sol),)
+    res = res if sol is None else res + (solidification_result(sol),)
+    return res if mon is None else res + monitor_result(mon, mat)
 
 
 def track_source(heat_source, track_box, dx, yi, t_step):
@@ -285,7 +307,7 @@ def track_source(heat_source, track_box, dx, yi, t_step):
 
 def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_track, theta, dt, t_step,
                      device_resident=True, heat_source=None, surface_loss=None, phase_change=None, history=None,
-                     material_law=None, solidification=None):
+                     material_law=None, solidification=None, monitor=None):
     """single_track_on_plate.py:150-177: the deposit advances one column per t_step along axis 1; packs are
     rebuilt after every column.  track_box = (x0, x1, z0, z1, n_columns).
     heat_source (a GoldakSource of the backend): the arc / laser as a moving volumetric source (track_source) during the
@@ -308,7 +330,10 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     solidification (T_freeze, a number): the conditions at the freezing front; one SolidificationRecord of the backend lives
     through the run on the global time like the history, and sync_mask(T) follows every column; device loop only; the track
     box must not overlap the plate either.  The return value gains a last element (after history's), the dict of
-    solidification_result.  None: the loop without it, unchanged."""
+    solidification_result.  None: the loop without it, unchanged.
+    monitor (a dict of FieldMonitor's keyword arguments: probes, regions, extra): one FieldMonitor of the backend lives through
+    the run, one log row per sub-step, on the global time; stateless, so a new column needs no call; device loop only.  The
+    return value gains two last elements, its traces() and region_log(mat).  None: the loop without it, unchanged."""
     x0, x1, z0, z1, ncol = track_box
     if material_law is not None and phase_change is not None:
         raise ValueError("run_single_track: phase_change cannot be combined with material_law (the MaterialLaw carries the "
@@ -329,7 +354,7 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     robin = {f: h for f in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')}
     dev_loop = device_resident and hasattr(grid, 'set_mask_device') and hasattr(T, 'fill_where')
     _require_device_loop('run_single_track', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
-                         history=history, material_law=material_law, solidification=solidification)
+                         history=history, material_law=material_law, solidification=solidification, monitor=monitor)
     if dev_loop:                                    # the mask lives in HBM: a new column is two slice assignments
         import torch
         d_mask = grid.layout.to_layout(mask, torch.uint8)
@@ -344,7 +369,8 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     if history is not None:
         hist = backend.ThermalHistory(grid, history, capacity=ncol * max(1, int(math.ceil(t_step / dt))), T=T)
     sol = backend.SolidificationRecord(grid, solidification, T=T) if solidification is not None else None
-    kw = _extras_kw(lpacks, ph, hist, nm, sol)
+    mon = _monitor(backend, grid, monitor, ncol * max(1, int(math.ceil(t_step / dt))))
+    kw = _extras_kw(lpacks, ph, hist, nm, sol, mon)
     for yi in range(ncol):
         if dev_loop:
             d_mask[x0:x1, yi:yi + 1, z0:z1] = 1
@@ -381,6 +407,8 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         res = res + (history_result(hist),)
     if sol is not None:
         res = res + (solidification_result(sol),)
+    if mon is not None:
+        res = res + monitor_result(mon, mat)
     return res if len(res) > 1 else res[0]
 
 
@@ -398,7 +426,8 @@ def path_steps(t_start, t_end, dt):
 
 
 def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, Ts, theta, dt, t_end=None, within=None,
-                        heat=False, surface_loss=None, phase_change=None, history=None, solidification=None, on_frame=None):
+                        heat=False, surface_loss=None, phase_change=None, history=None, solidification=None, on_frame=None,
+                        monitor=None):
     """Material laid along a scan path, bead by bead (README, "Deposition along a path"): from path.t_start to t_end (default
     path.t_end) in steps of dt (path_steps), every step preceded by the births of its interval -- the bead of the step [t, t + dt]
     is born at the step's start, at Ts, on top of `base_mask` (the plate; may be empty).  Device loop only: mask, field and packs
@@ -412,9 +441,10 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
     surface_loss, phase_change, history, solidification: as in run_single_track -- the newborn cells of a step are seeded at
     f_eq(Ts) / Ts / "never froze", the recorders run on the global time, from path.t_start, and the history's log holds one row
     per step.
+    monitor: as in run_single_track -- one FieldMonitor, one log row per step, its clock from path.t_start; a deposit needs no call.
     on_frame(t, T, active): called after every step with the time reached and NumPy copies (a download; None: none).
     Returns (T_final, active mask, number of ADI steps), all host side, then the final liquid fraction, history_result and
-    solidification_result for those that were asked for, in this order."""
+    solidification_result for those that were asked for, in this order, then the monitor's traces() and region_log(mat)."""
     nx, ny, nz = base_mask.shape
     grid = backend.Grid3D(nx, ny, nz, dx, np.array(base_mask, dtype=bool))
     mat = backend.Material(*mat_args)
@@ -426,7 +456,7 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
     if not dev_loop:
         raise ValueError("run_path_deposition: needs the device loop of a backend with PathDeposit")
     _require_device_loop('run_path_deposition', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
-                         history=history, solidification=solidification)
+                         history=history, solidification=solidification, monitor=monitor)
     src = path.on_device() if hasattr(path, 'on_device') else path
     dep = backend.PathDeposit(grid, src, bead, Ts, within=within)
     steps = path_steps(src.t_start, src.t_end if t_end is None else float(t_end), float(dt))
@@ -437,7 +467,8 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
     ph = backend.PhaseField(grid, mat, phase_change, T=T) if phase_change is not None else None
     hist = backend.ThermalHistory(grid, history, capacity=max(1, len(steps)), T=T, t=src.t_start) if history is not None else None
     sol = backend.SolidificationRecord(grid, solidification, T=T, t=src.t_start) if solidification is not None else None
-    kw = _extras_kw(None if surface_loss is None else bpacks, ph, hist, sol=sol)
+    mon = _monitor(backend, grid, monitor, len(steps), t=src.t_start)
+    kw = _extras_kw(None if surface_loss is None else bpacks, ph, hist, sol=sol, mon=mon)
     live = bool(np.asarray(base_mask).any())
     nsteps = 0
     for t, d in steps:
@@ -452,7 +483,7 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
             T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=S, t=t, **kw)
             nsteps += 1
         else:
-            for x in (hist, sol):
+            for x in (hist, sol, mon):
                 if x is not None:
                     x.t = x.t + d                      # (the global time moves on all the same)
         if on_frame is not None:
@@ -460,7 +491,8 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
     res = (np.asarray(T), grid.d_mask.cpu().contiguous().numpy().astype(bool), nsteps)
     res = res + (() if ph is None else (np.asarray(ph.liquid_fraction),))
     res = res if hist is None else res + (history_result(hist),)
-    return res if sol is None else res + (solidification_result(sol),)
+    res = res if sol is None else res + (solidification_result(sol),)
+    return res if mon is None else res + monitor_result(mon, mat)
 
 
 def ring_source(heat_source, R_in, wall, z_top, tau):

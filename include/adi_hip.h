@@ -964,6 +964,55 @@ int adi_solid_seed(double T_freeze, const double *d_T, double *d_t_solid, double
                    long plane_stride, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Field monitor of the Cartesian step (no counterpart in the reference, whose drivers take a probe value on the host after
+ * every step): one row of a device log per recorded step, taken from the step's final field T.  Stateless per cell: it reads
+ * T, the flags and their summary as they are, so a mask change needs no call.
+ *   probes   nprobe <= ADI_MONITOR_MAX_PROBES cells (i, j, k) of the box: T at the cell, NaN where the cell is off the mask.
+ *   regions  1 <= nreg <= ADI_MONITOR_MAX_REGIONS half-open index boxes { i0, i1, j0, j1, k0, k1 } (h_regions: 6 ints each),
+ *            non-empty, inside the box; they may overlap.  Per region, over its in-mask cells:
+ *            cells (int64), T_min, T_max (NaN when cells == 0), sum_T, sum_wT (with d_ids: w[id]*T, the product formed
+ *            first, one operation; h_weights: nmat <= ADI_MATMAP_MAX doubles by value), sum_extra (with d_extra, a second
+ *            field summed like T).  A quantity that is not asked for is logged as 0.
+ *   row      nprobe + ADI_MONITOR_REGION_WORDS * nreg 8-byte words: the probes, then per region
+ *            { cells, T_min, T_max, sum_T, sum_wT, sum_extra }.  The log is (capacity + 1) rows; a step writes row
+ *            min(slot, capacity) of the block (the thermal history's, ADI_HISTORY_BLOCK_BYTES, driven by
+ *            adi_history_set_clock / adi_history_tick; read through the pointer, so a captured graph follows it).
+ * The order of every sum is fixed by the decomposition of the box into 16 x 16 x 16 bricks and the region's box alone --
+ * not by the scheduling of workgroups, the launch box, the all-solid or the flag-reading path, or the width of the loads.
+ * An excluded cell (off the mask or outside the region) contributes +0.0.
+ *   brick (k_monitor_reduce, one workgroup of 256 threads per brick of the brick box that meets a region): thread t owns the
+ *     pairs of cells local (i, j, k) = (2 g + (t >> 7), (t >> 3) & 15, 2 (t & 7) + {0, 1}) of row groups g = 0 .. 7:
+ *     pair_g = v0 + v1;  acc = pair_0;  acc = acc + pair_g (g = 1 .. 7);  the 64 lanes of a wave by xor-butterfly
+ *     v = v + v[lane ^ o], o = 1, 2, 4, 8, 16, 32;  the four waves ((w0 + w1) + w2) + w3: one partial per (region, brick) in
+ *     d_partial, region r's bricks numbered lexicographically (bi, bj, bk) over its own brick box from offset
+ *     sum of the brick counts of the regions before it.
+ *   region (k_monitor_finish, one workgroup): thread t, acc = +0.0;  acc = acc + partial[n] for n = t, t + 256, ... in
+ *     increasing n;  then the same butterfly and the same wave order.
+ * Rounding operations from a cell to the logged sum: d = 17 + ceil(nb / 256) + 9, nb the bricks of the region's brick box
+ * (one more for sum_wT, whose product rounds first).  No floating-point atomics.  T_min / T_max are the extrema in the total
+ * order of the finite doubles in which -0.0 < +0.0: among zeros the minimum is -0.0 if one is present, the maximum +0.0 if
+ * one is present; NaN must not occur on in-mask cells.
+ * d_partial: ADI_MONITOR_PARTIAL_WORDS 8-byte words per (region, brick), partial_words of them in all (>= the need).
+ * d_probes: the device copy of h_probes (3 ints per probe) the kernel reads; a triple outside the box logs NaN.
+ * Valid: non-null block, T, flags, partial, log (d_bricks, d_extra, d_ids, h_weights may be null; d_ids needs h_weights and
+ * 1 <= nmat <= ADI_MATMAP_MAX; probes null only with nprobe == 0), 1 <= nreg <= 8, 0 <= nprobe <= 256, every region
+ * non-empty and inside the box, every probe inside the box, capacity >= 1, neither the log nor the partials aliasing T or
+ * the extra field, a brick box within 65535 bricks per axis.  Everything else is ADI_ERR_ARG, checked before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADI_MONITOR_MAX_REGIONS 8
+#define ADI_MONITOR_MAX_PROBES 256
+#define ADI_MONITOR_REGION_WORDS 6
+#define ADI_MONITOR_PARTIAL_WORDS 6
+/* k_monitor_reduce and k_monitor_finish for the field d_T into row min(slot, capacity) of d_log; the caller ticks the block */
+int adi_monitor_record(const void *d_block, const double *d_T, const double *d_extra, const uint8_t *d_ids,
+                       const uint8_t *d_flags, const uint32_t *d_bricks, int nx, int ny, int nz, long plane_stride, int nreg,
+                       const int *h_regions, int nprobe, const int *h_probes, const int *d_probes, int nmat,
+                       const double *h_weights, double *d_partial, long partial_words, double *d_log, long capacity,
+                       void *stream);
+/* every word of the capacity + 1 rows of d_log NaN; the block: slot = 0, n = 0, `capacity`; t0 and dt stay */
+int adi_monitor_reset_log(void *d_block, double *d_log, long capacity, long row_words, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Moving heat source of the cylindrical step.  For a step t_n -> t_n + dt:
  *     R0 = Tn + dt * q(x_c, t_n + dt/2) / (rho*cp)
  * and the three sweeps run unchanged.  Cell centres r_i = r_in + (i+1/2) dr, phi_j = (j+1/2) dphi, z_k = (k+1/2) dz (z from
