@@ -218,6 +218,14 @@ SIGNATURES = {
     'adi_matmap_sweep': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                  c_int, c_int, c_long, c_int, c_double_p, c_double, c_double, c_double, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),
+    'adi_matmap_phase_apply': (c_int, [c_int, c_void_p, c_int_p, c_double_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    'adi_matmap_phase_seed': (c_int, [c_int, c_void_p, c_int_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    'adi_matmap_loss_table_bytes': (c_size_t, []),
+    'adi_matmap_loss_table': (c_int, [c_int, c_void_p, c_double_p, c_double, c_void_p, c_size_t]),
+    'adi_matmap_loss_update': (c_int, [c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                       c_long, c_double, c_void_pp, c_int, c_int, c_int, c_void_p]),
     'adi_ctx_create': (c_int, [c_int, c_int, c_int, c_double, c_int, c_void_pp]),
     'adi_ctx_destroy': (c_int, [c_void_p]),
     'adi_ctx_set_mask': (c_int, [c_void_p, c_void_p]),

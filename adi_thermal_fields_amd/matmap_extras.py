@@ -1,0 +1,289 @@
+"""Latent heat and temperature-dependent surface loss on a grid of several materials: `MapPhaseField`, the
+liquid fraction of a MaterialMap's grid under one PhaseChange law per material, and `MapLossPacks`, the MaterialMap's own packs
+rewritten in place by one SurfaceLoss per material."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import lib, check, ptr_array, FACES
+from .fields import DeviceField, _SeededForMask, _device, _native_f64, _p, _stream
+from .packs import MaterialMap, _MapLoss, _MapPhase, _triples
+from .surface_loss import SurfaceLoss
+from .phase import PhaseChange
+
+
+class MapPhaseField(_SeededForMask, _MapPhase):
+    """The liquid fraction of a MaterialMap's grid, on the device: PhaseField with the law of the cell's own material.
+    laws: one entry per material of `mm`, a PhaseChange or None (the material never melts in this run: a backing bar).  It holds
+        f           fp64, the grid's layout, 0 off the mask and 0 in every cell of a law-less material
+        summary     one word per 16^3 brick, 0 exactly when every f of the brick is 0 (PhaseField's)
+        brick_ids   one word per brick: bits 0-7 the set of material ids among the brick's in-mask cells, 0 if it has none --
+                    adi_matmap_phase_apply reads it first and leaves a brick without a law at once, runs a brick of one material
+                    without reading ids, and reads the id bytes only in a brick of several
+    All buffers live as long as the object, so a StagedStepper's graph holds their pointers.  T (optional): the field f is seeded
+    from, f = f_eq(T) of the cell's own law; without it everything is solid.  dir_mask (optional): the Dirichlet cells of `apply`
+    calls that are not given any (the step passes its pack's).
+    The object remembers grid.mask_version and the MaterialMap's id field: after either changed `apply` raises ValueError until
+    sync_mask(T), which seeds the cells that joined the mask and rebuilds brick_ids.
+        apply(T, d_dir_mask=None)   the correction on a device field in the grid's layout, T and f in place: one launch
+        seed(T, sel=None)           f = f_eq(T) on the in-mask cells `sel` selects (None: all), 0 off the mask and without a law
+        sync_mask(T)                see above
+        snapshot() / restore(s)     f and the summary
+    `correct_of` / `correct` is the definition of apply, `f_eq_of` of seed, in NumPy fp64."""
+
+    def __init__(self, mm, laws, T=None, dir_mask=None):
+        if not isinstance(mm, MaterialMap):
+            raise TypeError("MapPhaseField: mm must be a MaterialMap")
+        self.laws = self._checked_laws(laws, mm.materials)
+        self.mm, self.grid = mm, mm.grid
+        L = self.grid.layout
+        self._flat = torch.zeros(L.numel_padded, dtype=torch.float64, device=_device())
+        self.f = self._flat.as_strided(L.shape, L.strides)
+        self.summary = torch.zeros(self._words(), dtype=torch.int32, device=_device())
+        self.brick_ids = torch.zeros(self._words(), dtype=torch.int32, device=_device())
+        self.d_dir_mask = None if dir_mask is None else L.to_layout(dir_mask, torch.uint8)
+        self._ids_version = None
+        if T is not None:
+            self.seed(T)
+        else:
+            self._seed_nothing()
+
+    @staticmethod
+    def _checked_laws(laws, materials):
+        """the laws as a tuple after the checks of the constructor (nothing is launched before they pass)"""
+        try:
+            laws = tuple(laws)
+        except TypeError:
+            raise TypeError("MapPhaseField: laws must be a sequence with one PhaseChange or None per material")
+        if len(laws) != len(materials):
+            raise ValueError("MapPhaseField: %d laws for %d materials" % (len(laws), len(materials)))
+        for law, (_, cp, _) in zip(laws, _triples(materials)):
+            if law is None:
+                continue
+            if not isinstance(law, PhaseChange):
+                raise TypeError("MapPhaseField: a law must be a PhaseChange or None, got %r" % type(law).__name__)
+            law.constants(cp)
+        return laws
+
+    def _words(self):
+        n = int(lib.adi_phase_summary_words(*self.grid.layout.pd[:3]))
+        if n <= 0:
+            raise ValueError("MapPhaseField: bad grid")
+        return n
+
+    def _c_laws(self):
+        n = len(self.laws)
+        none = _lib.PhaseChangeLaw(0.0, 0.0, 0.0)
+        return (n, (_lib.PhaseChangeLaw * n)(*[none if w is None else w.as_c() for w in self.laws]),
+                (ctypes.c_int * n)(*[0 if w is None else 1 for w in self.laws]))
+
+    def _remember_mask(self):
+        super()._remember_mask()
+        self._ids_version = self.mm._ids_version
+
+    def _check_fresh(self):
+        if self.grid.mask_version != self._mask_version or self.mm._ids_version != self._ids_version:
+            raise ValueError("MapPhaseField: the grid's mask or the MaterialMap's ids changed since the liquid fraction was "
+                             "seeded; call sync_mask(T)")
+
+    @property
+    def liquid_fraction(self):
+        """a copy of f as a DeviceField of the grid's shape"""
+        return DeviceField(self.f).copy()
+
+    def apply(self, T, d_dir_mask=None):
+        """adi_matmap_phase_apply on T (a DeviceField or device tensor in the grid's layout), in place; d_dir_mask: the
+        Dirichlet cells as a uint8 device tensor in the grid's layout (default: the ones given at construction)"""
+        g = self.grid
+        t = _native_f64(g, T, "MapPhaseField.apply: T must be a fp64 device field in the grid's layout (it is corrected in place)")
+        self._check_fresh()
+        assert self.summary.numel() == self._words()
+        dm = self.d_dir_mask if d_dir_mask is None else d_dir_mask
+        if dm is not None:
+            assert g.layout.is_native(dm) and dm.dtype == torch.uint8
+        n, laws, on = self._c_laws()
+        cp = (ctypes.c_double * n)(*[float(m.cp) for m in self.mm.materials])
+        check(lib.adi_matmap_phase_apply(n, laws, on, cp, _p(t), _p(self.f), _p(g.d_flags), _p(g.d_bricks), _p(self.mm._d_ids),
+                                         _p(dm), _p(self.summary), _p(self.brick_ids), *g.layout.pd, _stream()))
+        return T
+
+    def seed(self, T, sel=None):
+        """adi_matmap_phase_seed: f = f_eq(T) of the cell's own law on the in-mask cells `sel` selects (bool / uint8 array or
+        tensor of the grid's shape; None: every in-mask cell), 0 off the mask and in law-less cells; the summary and brick_ids
+        are rewritten for the grid's mask and the MaterialMap's ids as they are now"""
+        g = self.grid
+        d_sel = None if sel is None else g.layout.to_layout(sel, torch.uint8)
+        assert self.summary.numel() == self._words()
+        n, laws, on = self._c_laws()
+        check(lib.adi_matmap_phase_seed(n, laws, on, _p(_native_f64(g, T)), _p(self.f), _p(g.d_flags), _p(g.d_bricks),
+                                        _p(self.mm._d_ids), _p(d_sel), _p(self.summary), _p(self.brick_ids), *g.layout.pd,
+                                        _stream()))
+        self._remember_mask()
+
+    def _seed_nothing(self):
+        """a seed that selects no cell: every in-mask f of a material with a law is kept, the rest zeroed, and every entry of the
+        summary and of brick_ids rewritten"""
+        g = self.grid
+        self.seed(g.layout.empty(zero=True), sel=g.layout.empty(torch.uint8, zero=True))
+
+    def sync_mask(self, T):
+        """after `grid.mask` or the MaterialMap's ids changed: the cells that joined the mask since the last seed / sync are
+        seeded from T, those that left it are cleared, every other cell keeps its f (0 where its material has no law now), and
+        brick_ids is rebuilt"""
+        if self.grid.mask_version != self._mask_version:
+            super().sync_mask(T)
+        elif self.mm._ids_version != self._ids_version:
+            self._seed_nothing()
+
+    def set_liquid_fraction(self, f):
+        """load f (array / tensor / DeviceField of the grid's shape; taken as 0 off the mask and in law-less cells) and rebuild
+        the summary from it on the device"""
+        self.f.copy_(self.grid.layout.to_layout(f, torch.float64))
+        self._seed_nothing()
+
+    def snapshot(self):
+        return self._flat.clone(), self.summary.clone()
+
+    def restore(self, s):
+        self._flat.copy_(s[0])
+        self.summary.copy_(s[1])
+
+    def graph_key(self):
+        """what a captured graph holds of the field: the laws and heat capacities by value, the buffers by pointer"""
+        return (tuple(None if w is None else w.key() for w in self.laws), tuple(float(m.cp) for m in self.mm.materials),
+                self.f.data_ptr(), self.summary.data_ptr(), self.brick_ids.data_ptr(), self.mm._d_ids.data_ptr(),
+                None if self.d_dir_mask is None else self.d_dir_mask.data_ptr())
+
+    # ---- the definition in NumPy fp64 -------------------------------------------------------------------------------------
+    @staticmethod
+    def correct_of(laws, materials, T_star, f, mask, ids, dir_mask):
+        """(T, f) after the correction of the step's result T_star from the liquid fraction f it started with: THE DEFINITION.
+        For each material m that has a law it is laws[m].correct(T_star, f, mask & (ids == m), dir_mask, cp_m), one fp64
+        operation per line there; the results are composed over the disjoint cell sets.  Cells of a material without a law,
+        off-mask cells, Dirichlet cells and cells at rest keep T_star and f bit for bit."""
+        Tst = np.asarray(T_star, dtype=np.float64)
+        f = np.asarray(f, dtype=np.float64)
+        mask = np.asarray(mask, dtype=bool)
+        ids = np.asarray(ids)
+        laws = MapPhaseField._checked_laws(laws, materials)
+        T_out, f_out = Tst, f
+        for m, (law, (_, cp, _)) in enumerate(zip(laws, _triples(materials))):
+            if law is None:
+                continue
+            cells = mask & (ids == m)
+            Tm, fm = law.correct(Tst, f, cells, dir_mask, cp)
+            T_out = np.where(cells, Tm, T_out)
+            f_out = np.where(cells, fm, f_out)
+        return T_out, f_out
+
+    def correct(self, T_star, f, mask, ids, dir_mask):
+        """correct_of with this object's laws and its MaterialMap's materials"""
+        return self.correct_of(self.laws, self.mm.materials, T_star, f, mask, ids, dir_mask)
+
+    @staticmethod
+    def f_eq_of(laws, T, mask, ids):
+        """what seed(T) leaves in f: f_eq(T) of the cell's own law on the mask, 0 off it and where the material has none"""
+        T = np.asarray(T, dtype=np.float64)
+        mask = np.asarray(mask, dtype=bool)
+        ids = np.asarray(ids)
+        f = np.zeros(T.shape)
+        for m, law in enumerate(laws):
+            if law is not None:
+                f = np.where(mask & (ids == m), law.f_eq(T), f)
+        return f
+
+
+class MapLossPacks(_MapLoss):
+    """The packs of a MaterialMap whose Robin coefficient arrays are REWRITTEN IN PLACE on the device from the temperature field
+    (adi_matmap_loss_update), every exposed cell by the SurfaceLoss and the heat capacity of its own material.
+    loss: one SurfaceLoss for every material, or a sequence with one per material; they are taken as they are at construction
+    (their constants go into a small device table this object owns and uploads here, never inside a captured region).  The
+    MaterialMap must have been built with robin_h=None: its coefficient arrays are rewritten here.  `.packs is mm.packs`; pass
+    the object to the step as `surface_loss=` next to `material_map=mm`.
+        update(T, Tinf=None)                         before a step: the in-mask cells exposed along an axis only
+        rebuild(T, k_begin=0, k_end=None, Tinf=None) the planes [k_begin, k_end) of axis 2 in full: zeros where not exposed
+    A stale MapLossPacks is not an error: after `grid.mask` changed, `mm.rebuild()` (which the step demands) leaves the
+    coefficient arrays zero wherever no h was given -- everywhere -- and the next update writes every cell that is exposed now, so
+    the arrays are those of the new mask without a rebuild here.  T (optional, here): the field the arrays are evaluated from at
+    once.  `coeff_reference` is the definition in NumPy fp64."""
+
+    def __init__(self, mm, loss, Tinf, T=None):
+        if not isinstance(mm, MaterialMap):
+            raise TypeError("MapLossPacks: mm must be a MaterialMap")
+        n = len(mm.materials)
+        self.losses = self._checked_losses(loss, n)
+        for w in self.losses:
+            w.validate(Tinf)
+        if mm._bc['robin_h'] is not None:
+            raise ValueError("MapLossPacks: the MaterialMap was built with robin_h; build it with robin_h=None, its coefficient "
+                             "arrays are rewritten in place")
+        self.mm, self.grid, self.Tinf = mm, mm.grid, float(Tinf)
+        self.packs = mm.packs
+        self._coeff = ptr_array([p.d_coeff.data_ptr() for p in self.packs])
+        self._keys = tuple(w.key() for w in self.losses)
+        self._min_offset = min(float(w.T_offset) for w in self.losses)
+        nbytes = int(lib.adi_matmap_loss_table_bytes())
+        host = torch.zeros(nbytes, dtype=torch.uint8)
+        laws = (_lib.SurfaceLossLaw * n)(*[w.as_c() for w in self.losses])
+        C = (ctypes.c_double * n)(*[m.rho * m.cp for m in mm.materials])
+        check(lib.adi_matmap_loss_table(n, laws, C, self.grid.dx, ctypes.c_void_p(host.data_ptr()), nbytes))
+        self._table = host.to(_device())
+        if T is not None:
+            self.rebuild(T)
+
+    @staticmethod
+    def _checked_losses(loss, n):
+        losses = (loss,) * n if isinstance(loss, SurfaceLoss) else loss
+        try:
+            losses = tuple(losses)
+        except TypeError:
+            raise TypeError("MapLossPacks: loss must be a SurfaceLoss or a sequence with one per material")
+        if len(losses) != n:
+            raise ValueError("MapLossPacks: %d losses for %d materials" % (len(losses), n))
+        if not all(isinstance(w, SurfaceLoss) for w in losses):
+            raise TypeError("MapLossPacks: loss must be a SurfaceLoss or a sequence with one per material")
+        return losses
+
+    def _launch(self, T, Tinf, k0, k1, full):
+        g = self.grid
+        t = _native_f64(g, T)                                 # host arrays / foreign tensors: a copy (not the step's path)
+        check(lib.adi_matmap_loss_update(_p(self._table), float(self.Tinf if Tinf is None else Tinf), self._min_offset, _p(t),
+                                         _p(g.d_flags), _p(g.d_bricks), _p(self.mm._d_ids), *g.layout.pd, g.dx, self._coeff,
+                                         int(k0), int(k1), int(full), _stream()))
+
+    def update(self, T, Tinf=None):
+        """the per-step mode over the whole box, from the device field T (DeviceField or tensor in the grid's layout);
+        Tinf: the step's ambient (default: the one given at construction)"""
+        self._launch(T, Tinf, 0, self.grid.layout.pz, 0)
+        return self.packs
+
+    def rebuild(self, T, k_begin=0, k_end=None, Tinf=None):
+        """the full mode on the planes [k_begin, k_end) of axis 2 (clipped to the box), for the grid's CURRENT mask"""
+        g = self.grid
+        whole = k_end is None and int(k_begin) <= 0
+        k0 = max(0, int(k_begin))
+        k1 = g.layout.pz if whole else min(g.nz, g.nz if k_end is None else int(k_end))
+        if k1 > k0:
+            self._launch(T, Tinf, k0, k1, 1)
+        return self.packs
+
+    def graph_key(self):
+        """what a captured launch holds: the laws by value (as uploaded), the ambient given here, the table by pointer"""
+        return (self._keys, self.Tinf, self._table.data_ptr())
+
+    @staticmethod
+    def coeff_reference(T, mask, ids, materials, dx, losses, Tinf):
+        """the three coefficient arrays: THE DEFINITION -- the `coeff` arrays of MaterialMap.packs_reference(mask, ids, materials,
+        dx, robin_h={face: h_face}) with h_face = losses[ids].h_of(T, face, Tinf) chosen cell by cell"""
+        mask = np.asarray(mask, dtype=bool)
+        losses = MapLossPacks._checked_losses(losses, len(_triples(materials)))
+        idm = np.where(mask, ids, 0)
+        h = {}
+        for face in FACES:
+            hf = np.zeros(mask.shape)
+            for m, w in enumerate(losses):
+                hf = np.where(idm == m, w.h_of(T, face, Tinf), hf)
+            h[face] = hf
+        return tuple(p.coeff for p in MaterialMap.packs_reference(mask, ids, materials, dx, robin_h=h))

@@ -256,6 +256,16 @@ def _thomas_excess64(p, q, e, d):
     return x
 
 
+class _MapLoss:
+    """What step.py names of matmap_extras.MapLossPacks (that module comes after the step's in the module map, as monitor.py
+    does): the surface loss of a MaterialMap `.mm`, with `update(T, Tinf)` and `graph_key()`."""
+
+
+class _MapPhase:
+    """What step.py names of matmap_extras.MapPhaseField: the liquid fraction of a MaterialMap `.mm`, with `apply(T, d_dir_mask)`,
+    `_check_fresh()`, `snapshot()`, `restore(s)` and `graph_key()`."""
+
+
 class MaterialMap:
     """A grid of several materials: 1 to 8 (rho, cp, k) and a uint8 id per cell.  The step under it couples a cell of material
     m to an in-mask neighbour of material n with the pair-table entry G[m][n] = (kf(m, n) dt) / (C_m dx^2), kf the harmonic

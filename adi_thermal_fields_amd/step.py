@@ -8,7 +8,7 @@ from . import _lib
 from ._lib import lib, check
 from ._ledger import PromiseLedger
 from .fields import DeviceField, _as_state, _wrap, _p, _stream
-from .packs import _fc_arg, MaterialMap
+from .packs import _fc_arg, MaterialMap, _MapLoss, _MapPhase
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .surface_loss import LossPacks
 from .phase import PhaseField, NonlinearPacks
@@ -145,9 +145,16 @@ def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history
         if source is not None:
             raise ValueError("material_map: a GoldakSource object cannot be combined with it (its sweep-0 correction assumes "
                              "uniform coupling); pass the source as a field, S=path.sample_step(grid, t, dt)")
-        if surface_loss is not None or phase is not None or material is not None:
+        if ((surface_loss is not None and not isinstance(surface_loss, _MapLoss))
+                or (phase is not None and not isinstance(phase, _MapPhase)) or material is not None):
             raise ValueError("material_map: surface_loss= / phase= / material= cannot be combined with it; each assumes one cp")
+        if surface_loss is not None and surface_loss.mm is not material_map:
+            raise ValueError("surface_loss: the MapLossPacks belongs to another MaterialMap")
+        if phase is not None and phase.mm is not material_map:
+            raise ValueError("phase: the MapPhaseField belongs to another MaterialMap")
         material_map._check_fresh()
+        if phase is not None:
+            phase._check_fresh()
     if material is not None:
         if not isinstance(material, NonlinearPacks):
             raise TypeError("material must be a NonlinearPacks")
@@ -168,12 +175,12 @@ def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history
     if source is not None and not isinstance(source, GoldakSource):
         raise TypeError("source must be a GoldakSource (pass a source field, e.g. ScanPath.sample_step, to "
                         "adi_step_numba_coeff)")
-    if surface_loss is not None:
+    if surface_loss is not None and material_map is None:
         if not isinstance(surface_loss, LossPacks):
             raise TypeError("surface_loss must be a LossPacks")
         if len(packs) != 3 or any(p is not q for p, q in zip(packs, surface_loss.packs)):
             raise ValueError("surface_loss: the step must be given the LossPacks' own packs (surface_loss.packs)")
-    if phase is not None:
+    if phase is not None and material_map is None:
         if not isinstance(phase, PhaseField):
             raise TypeError("phase must be a PhaseField")
         if phase.grid is not grid:
@@ -223,17 +230,22 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, sou
     mark: called at the stage boundaries of per-stage timing: before the explicit stage, between it and sweep 0 when they are
     two launches, after sweep 0 with the source's correction, after sweep 1 and after sweep 2.
     material_map: a MaterialMap: the explicit stage (with d_S, if any) and the three sweeps are ITS four launches
-    (adi_matmap_explicit, adi_matmap_sweep), never fused; history and solidification follow as ever.
+    (adi_matmap_explicit, adi_matmap_sweep), never fused; with it `surface_loss` is a MapLossPacks, whose update from t_in comes
+    first, and `phase` a MapPhaseField, whose correction of `out` follows sweep 2; history and solidification follow as ever.
     monitor: a FieldMonitor: its record of `out` and its tick are the last launches of all, after solidification's."""
     (ta, tb), _, _ = grid.scratch(2)
     if material_map is not None:
         material_map._check_fresh()
+        if surface_loss is not None:
+            surface_loss.update(t_in, Tinf)
         mark()
         material_map._explicit_into(t_in, d_S, ta, params)
         for axis, (a, b) in enumerate(((ta, tb), (tb, ta), (ta, out))):
             mark()
             material_map._sweep_into(axis, a, b, params, Tinf)
         mark()
+        if phase is not None:
+            phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
         _record_step(t_in, out, params, history, solidification, captured, monitor)
         return
     u = t_in                                               # what the linear step runs on
@@ -323,8 +335,10 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     None: no such launch.
     material_map: a MaterialMap of the grid, with `packs` its `.packs` and `mat` its `.mat`: several materials in one grid, a
     material id per cell.  The step is then four launches of its own kernels -- explicit stage, sweeps 0, 1, 2 -- whose couplings
-    come from the map's pair table.  Combines with S= as a field and with history= and solidification=; not with a
-    GoldakSource object, surface_loss=, phase= or material=.  None: the launches of before.
+    come from the map's pair table.  Combines with S= as a field and with history= and solidification=; with
+    surface_loss= when that is a MapLossPacks of the map and with phase= when that is a MapPhaseField of the map (one law per
+    material: adi_matmap_loss_update first, adi_matmap_phase_apply after sweep 2); not with a GoldakSource object,
+    a LossPacks, a PhaseField or material=.  None: the launches of before.
     monitor: a FieldMonitor of the grid (with the step's material_map, if any): the result's value at its probes and the count,
     extrema and sums of its regions become one row of its device log, and its clock moves on by dt (adi_monitor_record and
     adi_history_tick on its block, the last launches of all).  Combines with every other argument.  None: no such launch.
@@ -409,7 +423,9 @@ class StagedStepper:
         # Kirchhoff field by pointer, so all are part of run()'s graph key.  Stateless: the warm-up steps need no snapshot
         self.material = material
         # several materials: the step's four launches are the MaterialMap's; its pair table travels by value in them (so dt and
-        # theta, already in run()'s graph key, cover it) and its id field by pointer: graph_key() is part of the key
+        # theta, already in run()'s graph key, cover it) and its id field by pointer: graph_key() is part of the key.  With it
+        # surface_loss is a MapLossPacks (the laws in a device table by pointer, the ambient by value) and phase a MapPhaseField
+        # (laws by value, f, the summary and the bricks' id sets by pointer): their graph_key() joins the key
         self.material_map = material_map
         # field monitor: the record of the step's OUTPUT buffer and the tick of its block, the last launches of all -- captured
         # with them; probes, regions and weights travel by value and its buffers by pointer: part of run()'s graph key
@@ -461,7 +477,8 @@ class StagedStepper:
                tuple(getattr(p, 'mask_version', None) for p in self.packs),
                tuple(None if p.d_coeff is None else p.d_coeff.data_ptr() for p in self.packs), self.fused,
                None if self.source is None else self.source.shape_key(),
-               None if self.surface_loss is None else self.surface_loss.loss.key(),
+               None if self.surface_loss is None else (self.surface_loss.graph_key() if self.material_map is not None
+                                                       else self.surface_loss.loss.key()),
                None if self.phase is None else self.phase.graph_key(),
                None if self.history is None else self.history.graph_key(),
                None if self.material is None else self.material.graph_key(),

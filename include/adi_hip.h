@@ -1106,6 +1106,46 @@ int adi_matmap_sweep(int axis, int variant, const double *d_in, const uint8_t *d
                      double *d_out, void *d_work, size_t work_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Several materials: latent heat and surface loss.  The two pointwise passes around the step, with
+ * the law of the cell's own material: "Latent heat" and "Temperature-dependent surface loss" above, cell by cell, with
+ * cp = cp_id and rho cp = C_id of the cell's id (d_ids as in "Several materials": an id off the mask is never used).
+ *
+ * Latent heat.  h_laws: nmat laws; h_on: nmat ints, 0 = the material never melts (its h_laws entry is not read): its cells
+ * keep T and f (= 0) bit for bit.  h_cp: nmat heat capacities; the host constants dT, Hs, Hl, cm are evaluated per material as
+ * for adi_phase_apply.  d_summary: the phase summary of "Latent heat", same rule.  d_brick_ids: one more 32-bit word per brick
+ * (same indexing, adi_phase_summary_words of them): bits 0-7 are the set of ids among the brick's in-mask cells, 0 where it has
+ * none.  adi_matmap_phase_seed rewrites it, adi_matmap_phase_apply reads it FIRST and believes it: a brick whose set holds no
+ * material with a law is left at once, nothing else read; a brick of one material runs that law without reading ids; only
+ * a brick of several materials reads the id bytes, and T only where a cell has a law.  After the mask or the ids changed the
+ * words are stale until the next adi_matmap_phase_seed.
+ * ---------------------------------------------------------------------------------------------- */
+/* The correction, d_T and d_f in place.  d_dir_mask (NULL: no Dirichlet cells): box layout, non-zero on Dirichlet cells. */
+int adi_matmap_phase_apply(int nmat, const adi_phase_change *h_laws, const int *h_on, const double *h_cp, double *d_T,
+                           double *d_f, const uint8_t *d_flags, const uint32_t *d_bricks, const uint8_t *d_ids,
+                           const uint8_t *d_dir_mask, uint32_t *d_summary, const uint32_t *d_brick_ids, int nx, int ny, int nz,
+                           long plane_stride, void *stream);
+/* f = f_eq(T) of the cell's own law on the in-mask cells d_sel selects (NULL: every in-mask cell), Dirichlet cells included;
+ * f = 0 off the mask and in every cell of a material without a law; other in-mask cells keep f.  Every entry of the summary
+ * and of d_brick_ids is rewritten. */
+int adi_matmap_phase_seed(int nmat, const adi_phase_change *h_laws, const int *h_on, const double *d_T, double *d_f,
+                          const uint8_t *d_flags, const uint32_t *d_bricks, const uint8_t *d_ids, const uint8_t *d_sel,
+                          uint32_t *d_summary, uint32_t *d_brick_ids, int nx, int ny, int nz, long plane_stride, void *stream);
+
+/* Surface loss.  The laws of up to ADI_MATMAP_MAX materials are too large to travel by value: they live in a device table of
+ * adi_matmap_loss_table_bytes() bytes that the caller owns.  adi_matmap_loss_table fills its HOST image (no HIP call) from
+ * nmat laws, h_C (C_m = rho_m cp_m) and dx: per law the products and quotients that do not depend on the cell or on Tinf, and
+ * C_m (dx dx dx); the caller copies it to the device once, outside any capture.  adi_matmap_loss_update is
+ * adi_surface_loss_update with the law and the heat capacity of the cell's id: Ta = Tinf + T_offset and Ta*Ta are evaluated
+ * from Tinf (by value) in the kernel, coeff[axis] += (h_f (dx dx)) / (C_id (dx dx dx)) on cells exposed on face f, '-' then '+':
+ * bit-identical to adi_matmap_build_coeffs with the six h_f fields.  min_T_offset: the smallest T_offset among the laws
+ * (Tinf + T_offset > 0 is checked with it).  full and the plane range as for adi_surface_loss_update. */
+size_t adi_matmap_loss_table_bytes(void);
+int adi_matmap_loss_table(int nmat, const adi_surface_loss *h_laws, const double *h_C, double dx, void *h_table, size_t bytes);
+int adi_matmap_loss_update(const void *d_table, double Tinf, double min_T_offset, const double *d_T, const uint8_t *d_flags,
+                           const uint32_t *d_bricks, const uint8_t *d_ids, int nx, int ny, int nz, long plane_stride,
+                           double dx, double *const d_coeff[3], int k_begin, int k_end, int full, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Context API: the library owns the device memory; callers hand over HOST arrays.
  * One context per GPU and thread; no hidden global state.
  * ---------------------------------------------------------------------------------------------- */

@@ -1,0 +1,128 @@
+"""Laws, fields and the branch-coverage condition of tests/test_matmap_extras_cpu.py and tests/test_matmap_extras_gpu.py: latent
+heat and surface loss with one law per material of a MaterialMap.  The grids, masks, ids and materials are those of
+tests/matmap_cases.py.
+
+Fields of the pointwise tests: T* uniform on [900, 1700]; f0 = the definition of seed (MapPhaseField.f_eq_of) of a DIFFERENT
+random field, drawn per cell about the melting range of the cell's own material -- Ts + u (Tl - Ts), u uniform on [-0.5, 1.5] -- so
+that a quarter of a material's cells start solid, half mushy and a quarter liquid whatever the width of its range; 10 % of the
+in-mask cells are Dirichlet cells.  `coverage` counts, from the definition alone, the share of a material's in-mask cells in each
+branch of the correction, and `assert_covered` holds each to at least 1 %: checked on the CPU before a device is compared."""
+import zlib
+
+import numpy as np
+
+from adi_thermal_fields_amd.matmap_extras import MapPhaseField
+from adi_thermal_fields_amd.phase import PhaseChange
+from adi_thermal_fields_amd.surface_loss import SurfaceLoss
+
+LAWS = (PhaseChange(2.7e5, 1400.0, 1450.0), PhaseChange(2.05e5, 1083.0, 1085.0), None)      # steel, copper, insulator
+TINF = 20.0
+LOSSES = (SurfaceLoss(h={'x-': 15.0, 'x+': 25.0, 'y-': 0.0, 'y+': 10.0, 'z-': 5.0, 'z+': 40.0}, emissivity=0.8,
+                      table=([300.0, 800.0, 1200.0, 1600.0], [2.0, 9.0, 30.0, 55.0])),
+          SurfaceLoss(h={'x-': 8.0, 'x+': 12.0, 'y-': 0.0, 'y+': 20.0, 'z-': 30.0, 'z+': 6.0}, emissivity=0.05),
+          SurfaceLoss(h={'x-': 3.0, 'x+': 4.0, 'y-': 0.0, 'y+': 5.0, 'z-': 6.0, 'z+': 7.0}, emissivity=0.9))
+BRANCHES = ('all_solid', 'all_liquid', 'mushy', 'rest_solid', 'rest_liquid', 'dirichlet_skipped')
+BRICK = 16
+
+
+def laws_of(materials):
+    return LAWS[:len(materials)]
+
+
+def losses_of(materials):
+    return LOSSES[:len(materials)]
+
+
+def fields(mask, ids, laws, seed=0):
+    """dict(T_star, T_seed, f0, dir_mask) for a grid under `laws`; read-only arrays, a function of the arguments alone"""
+    mask = np.asarray(mask, dtype=bool)
+    rng = np.random.default_rng((zlib.crc32(mask.tobytes()) ^ zlib.crc32(np.asarray(ids).tobytes())) + seed)
+    shape = mask.shape
+    T_star = rng.uniform(900.0, 1700.0, shape)
+    u = rng.uniform(-0.5, 1.5, shape)
+    T_seed = rng.uniform(900.0, 1700.0, shape)
+    for m, law in enumerate(laws):
+        if law is not None:
+            T_seed = np.where(ids == m, law.T_solidus + u * (law.T_liquidus - law.T_solidus), T_seed)
+    f0 = MapPhaseField.f_eq_of(laws, T_seed, mask, ids)
+    dir_mask = mask & (rng.random(shape) < 0.10)
+    out = dict(T_star=T_star, T_seed=T_seed, f0=f0, dir_mask=dir_mask)
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+def coverage(T_star, f0, mask, ids, dir_mask, materials):
+    """{material with a law: {branch: share of the material's in-mask cells}} from the definition's own quantities"""
+    out = {}
+    for m, (law, (_, cp, _)) in enumerate(zip(laws_of(materials), materials)):
+        if law is None:
+            continue
+        cells = mask & (ids == m)
+        n = int(cells.sum())
+        L, Ts, Tl = law.validate()
+        _, Hs, Hl, _ = law.constants(cp)
+        rest_s = (f0 == 0.0) & (T_star <= Ts)
+        rest_l = (f0 == 1.0) & (T_star >= Tl)
+        rest = rest_s | rest_l
+        dirc = np.zeros_like(mask) if dir_mask is None else np.asarray(dir_mask, dtype=bool)
+        act = cells & ~rest & ~dirc
+        H = cp * T_star + L * f0
+        count = dict(all_solid=act & (H <= Hs), all_liquid=act & (H >= Hl), mushy=act & (H > Hs) & (H < Hl),
+                     rest_solid=cells & rest_s, rest_liquid=cells & rest_l, dirichlet_skipped=cells & dirc & ~rest)
+        out[m] = {b: (int(count[b].sum()) / n if n else 0.0) for b in BRANCHES}
+    return out
+
+
+def assert_covered(T_star, f0, mask, ids, dir_mask, materials, what=''):
+    cov = coverage(T_star, f0, mask, ids, dir_mask, materials)
+    assert cov, what
+    for m, shares in cov.items():
+        print('%s material %d: %s' % (what, m, '  '.join('%s %.1f %%' % (b, 100 * s) for b, s in shares.items())))
+        for b, s in shares.items():
+            assert s >= 0.01, (what, m, b, s)
+
+
+def brick_words(mask, ids, pd):
+    """the NumPy statement of brick_ids for a grid held in a physical box pd = (px, py, pz): one word per 16^3 brick of the box,
+    entry ((i/16) nby + j/16) nbz + k/16, bits 0-7 the set of ids among the brick's in-mask cells"""
+    px, py, pz = pd
+    nb = [(n + BRICK - 1) // BRICK for n in (px, py, pz)]
+    words = np.zeros(nb, np.int64)
+    i, j, k = np.nonzero(mask)
+    np.bitwise_or.at(words, (i // BRICK, j // BRICK, k // BRICK), np.int64(1) << ids[i, j, k].astype(np.int64))
+    return words.ravel().astype(np.int32)
+
+
+def brick_any(a, pd):
+    """one word per brick of the physical box: 1 where any entry of `a` (the grid's shape) in the brick is non-zero"""
+    px, py, pz = pd
+    nb = [(n + BRICK - 1) // BRICK for n in (px, py, pz)]
+    words = np.zeros(nb, np.int32)
+    i, j, k = np.nonzero(a)
+    words[i // BRICK, j // BRICK, k // BRICK] = 1
+    return words.ravel()
+
+
+def h_fields(T, mask, ids, materials, Tinf, losses=None):
+    """{face: h} with h = the loss of the cell's own material at T, cell by cell (0 off the mask)"""
+    losses = losses_of(materials) if losses is None else losses
+    idm = np.where(mask, ids, 0)
+    out = {}
+    for face in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+'):
+        hf = np.zeros(mask.shape)
+        for m, w in enumerate(losses):
+            hf = np.where(mask & (idm == m), w.h_of(T, face, Tinf), hf)
+        out[face] = hf
+    return out
+
+
+def enthalpy(T, f, mask, ids, materials):
+    """sum over the mask of rho_m (cp_m T + L_m f) and of rho_m (cp_m |T| + L_m), in long double"""
+    LD = np.longdouble
+    idm = np.where(mask, ids, 0)
+    rho = np.array([m[0] for m in materials], LD)[idm]
+    cp = np.array([m[1] for m in materials], LD)[idm]
+    L = np.array([0.0 if w is None else w.latent_heat for w in laws_of(materials)], LD)[idm]
+    T, f = np.asarray(T).astype(LD), np.asarray(f).astype(LD)
+    return np.sum((rho * (cp * T + L * f))[mask]), np.sum((rho * (cp * np.abs(T) + L))[mask])
