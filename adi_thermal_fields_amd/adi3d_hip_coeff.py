@@ -33,7 +33,8 @@ GoldakSource, ScanPath, ScanPathSource and the one host definition of Goldak's d
 perimeter ratio, birth_planes, BirthPacks, BeadProfile, PathDeposit (births along a scan path); surface_loss.py -- SurfaceLoss, LossPacks; phase.py -- PhaseChange, PhaseField, MaterialLaw, NonlinearPacks;
 matmap_extras.py -- MapPhaseField, MapLossPacks (latent heat and surface loss with one law per material of a MaterialMap);
 history.py -- HistoryLevels, ThermalHistory, SolidificationRecord; monitor.py -- FieldMonitor (probes, region extrema and sums; it
-imports fields, packs and history, and step.py knows it by history._StepMonitor); step.py -- the stage entry points, the launch sequence, adi_step_hip_coeff,
+imports fields, packs and history, and step.py knows it by history._StepRecorder, the base the three recorders share); step.py --
+the stage entry points, StepExtras (the record of the step's optional parts), the launch sequence, adi_step_hip_coeff,
 StagedStepper.  Each imports only those before it in this list ("Module map"); code inside the package imports
 from them, drivers and tests from here.
 """

@@ -1,5 +1,6 @@
 """Thermal history: the levels `HistoryLevels`, the recorder of peak temperature, cooling time and melt pool, `ThermalHistory`,
-and the recorder of the conditions at the freezing front, `SolidificationRecord`."""
+and the recorder of the conditions at the freezing front, `SolidificationRecord`; `_StepRecorder`, the clock and the step's
+"record this step" call that these two and monitor.py's FieldMonitor share."""
 import ctypes
 
 import numpy as np
@@ -43,7 +44,46 @@ class HistoryLevels:
 _POOL_EMPTY_LO = np.iinfo(np.int32).max
 
 
-class ThermalHistory(_SeededForMask):
+# ---- what the step asks of a recorder: ThermalHistory, SolidificationRecord, monitor.py's FieldMonitor ---
+class _StepRecorder:
+    """The part of a recorder the step drives, written once: a device block of the history's layout (`d_block`), the host clock
+    `.t`, the end times `_times` of the recorded steps (None: the recorder keeps none) and `_keyword`, the keyword of the step
+    it is passed by, which is how step.py tells a FieldMonitor (a later module) from the other two.  The owner supplies
+    `_launch_record(t_in, t_out)` (its record and the tick), `_check_mask`, `snapshot`, `restore`, `graph_key` and `grid`."""
+    _keyword = None
+    _times = None
+
+    def set_clock(self, dt):
+        """the block's clock from the host clock: t0 = .t, this dt, n = 0 (the log slot, if there is one, stays)"""
+        check(lib.adi_history_set_clock(_p(self.d_block), self.t, float(dt), _stream()))
+
+    def advance_clock(self, t0, dt, nsteps):
+        """host side of `nsteps` recorded steps of dt from t0: their end times join the log's, .t = t0 + nsteps*dt"""
+        if self._times is not None:
+            self._times.extend(t0 + (n + 1) * dt for n in range(nsteps))
+        self.t = t0 + nsteps * dt
+
+    def record(self, T_in, T_out, dt):
+        """one step T_in (at .t) -> T_out (at .t + dt), both fp64 device fields in the grid's layout: one record launch and the
+        tick; afterwards .t = t0 + dt"""
+        strict = "%s.record: T_in and T_out must be fp64 device fields in the grid's layout" % type(self).__name__
+        t_in, t_out = _native_f64(self.grid, T_in, strict), _native_f64(self.grid, T_out, strict)
+        self._check_mask()
+        dt = float(dt)
+        self.set_clock(dt)
+        self._launch_record(t_in, t_out)
+        self.advance_clock(self.t, dt, 1)
+
+    def _record_step(self, t_in, out, dt, captured):
+        """what the step calls for "record this step" t_in -> out.  captured: a graph may replay the launches and the caller
+        keeps the clocks, so the record and the tick alone; otherwise the public `record`"""
+        if captured:
+            self._launch_record(t_in, out)
+        else:
+            self.record(t_in, out, dt)
+
+
+class ThermalHistory(_SeededForMask, _StepRecorder):
     """Thermal history of a grid under HistoryLevels, on the device: `T_peak`, `t_hi`, `t_lo` (fp64, the grid's layout, NaN off
     the mask and where "never happened"), the melt-pool log (one row of ADI_HISTORY_LOG_INTS integers per recorded step, `capacity`
     rows and a spill row), the device block (clock and log slot) and the host clock `.t`: the time at which the next recorded
@@ -59,6 +99,7 @@ class ThermalHistory(_SeededForMask):
 
     LOG_GUARD = 8        # integers either side of the log that no launch may touch (tests read them)
     GUARD_WORD = 0x5a5a5a5a
+    _keyword = 'history'
 
     def __init__(self, grid, levels, capacity=4096, T=None, t=0.0):
         if not isinstance(levels, HistoryLevels):
@@ -149,26 +190,6 @@ class ThermalHistory(_SeededForMask):
         if self.grid.mask_version != self._mask_version:
             raise ValueError("ThermalHistory: the grid's mask changed since the history was seeded; call sync_mask(T)")
 
-    def set_clock(self, dt):
-        """the block's clock from the host clock: t0 = .t, this dt, n = 0 (the log slot stays)"""
-        check(lib.adi_history_set_clock(_p(self.d_block), self.t, float(dt), _stream()))
-
-    def advance_clock(self, t0, dt, nsteps):
-        """host side of `nsteps` recorded steps of dt from t0: their end times join the log's, .t = t0 + nsteps*dt"""
-        self._times.extend(t0 + (n + 1) * dt for n in range(nsteps))
-        self.t = t0 + nsteps * dt
-
-    def record(self, T_in, T_out, dt):
-        """one step T_in (at .t) -> T_out (at .t + dt), both fp64 device fields in the grid's layout: one record launch and the
-        tick; afterwards .t = t0 + dt"""
-        strict = "ThermalHistory.record: T_in and T_out must be fp64 device fields in the grid's layout"
-        t_in, t_out = _native_f64(self.grid, T_in, strict), _native_f64(self.grid, T_out, strict)
-        self._check_mask()
-        dt = float(dt)
-        self.set_clock(dt)
-        self._launch_record(t_in, t_out)
-        self.advance_clock(self.t, dt, 1)
-
     def seed(self, T, sel=None):
         """adi_history_seed: T_peak = T, no crossing, on the in-mask cells `sel` selects (None: every in-mask cell); NaN off the
         mask"""
@@ -231,25 +252,8 @@ class ThermalHistory(_SeededForMask):
                     volume=cells * dx ** 3, dropped=max(0, slot - self.capacity))
 
 
-# ---- what the step asks of a monitor (monitor.py: FieldMonitor) ------------------------------------------
-class _StepMonitor:
-    """The part of a monitor the step drives, kept here so that step.py can name it: a device block of the history's layout
-    (`d_block`), the host clock `.t` and the end times `_times` of the recorded steps.  The owner supplies
-    `_launch_record(t_in, t_out)` (its record and the tick), `record`, `snapshot`, `restore`, `graph_key`, `_check_mask`, and
-    the attributes `grid` and `material_map`."""
-
-    def set_clock(self, dt):
-        """the block's clock from the host clock: t0 = .t, this dt, n = 0 (the log slot stays)"""
-        check(lib.adi_history_set_clock(_p(self.d_block), self.t, float(dt), _stream()))
-
-    def advance_clock(self, t0, dt, nsteps):
-        """host side of `nsteps` recorded steps of dt from t0: their end times join the log's, .t = t0 + nsteps*dt"""
-        self._times.extend(t0 + (n + 1) * dt for n in range(nsteps))
-        self.t = t0 + nsteps * dt
-
-
 # ---- the freezing front: thermal gradient and cooling rate at solidification (include/adi_hip.h, DESIGN.md section 6k) --------
-class SolidificationRecord(_SeededForMask):
+class SolidificationRecord(_SeededForMask, _StepRecorder):
     """The conditions at the solidification front of a grid, on the device: per cell, taken at the moment the cell last froze
     (dropped from above `T_freeze` to it or below within one step), the crossing time `t_solid`, the cooling rate and the
     SQUARE of the thermal gradient, `g2` (fp64, the grid's layout, NaN off the mask and where the cell never froze); the word per
@@ -267,7 +271,9 @@ class SolidificationRecord(_SeededForMask):
         R                         cooling_rate / G, the speed of the front; inf where G = 0 (a cell with no neighbour in the
                                   mask, or a flat field): such a cell cools without a front passing through it
     `record_reference` is the definition, adi_solid_record the same operations on the device.  The device stores G squared so
-    that every stored number comes from + - * / alone and is held to bit equality; the square root is taken here."""
+    that every stored number comes from + - * / alone and is held to bit equality; the square root is taken here.  It keeps no
+    list of end times (there is no log to go with them): `_times` stays None."""
+    _keyword = 'solidification'
 
     def __init__(self, grid, T_freeze, T=None, t=0.0):
         self.grid, self.T_freeze = grid, self._level(T_freeze)
@@ -366,25 +372,6 @@ class SolidificationRecord(_SeededForMask):
     def _check_mask(self):
         if self.grid.mask_version != self._mask_version:
             raise ValueError("SolidificationRecord: the grid's mask changed since the record was seeded; call sync_mask(T)")
-
-    def set_clock(self, dt):
-        """the block's clock from the host clock: t0 = .t, this dt, n = 0"""
-        check(lib.adi_history_set_clock(_p(self.d_block), self.t, float(dt), _stream()))
-
-    def advance_clock(self, t0, dt, nsteps):
-        """host side of `nsteps` recorded steps of dt from t0: .t = t0 + nsteps*dt"""
-        self.t = t0 + nsteps * dt
-
-    def record(self, T_in, T_out, dt):
-        """one step T_in (at .t) -> T_out (at .t + dt), both fp64 device fields in the grid's layout: one record launch and the
-        tick; afterwards .t = t0 + dt"""
-        strict = "SolidificationRecord.record: T_in and T_out must be fp64 device fields in the grid's layout"
-        t_in, t_out = _native_f64(self.grid, T_in, strict), _native_f64(self.grid, T_out, strict)
-        self._check_mask()
-        dt = float(dt)
-        self.set_clock(dt)
-        self._launch_record(t_in, t_out)
-        self.advance_clock(self.t, dt, 1)
 
     def seed(self, T, sel=None):
         """adi_solid_seed: "never froze" on the in-mask cells `sel` selects (None: every in-mask cell), NaN off the mask; the word

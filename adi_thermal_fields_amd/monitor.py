@@ -10,13 +10,13 @@ from . import _lib
 from ._lib import lib, check
 from .fields import DeviceField, _device, _native_f64, _p, _stream
 from .packs import MaterialMap
-from .history import _StepMonitor
+from .history import _StepRecorder
 
 _B = _lib.BRICK
 _LANES = np.arange(64)
 
 
-class FieldMonitor(_StepMonitor):
+class FieldMonitor(_StepRecorder):
     """What a run is calibrated and checked with, logged on the device after every recorded step: the step's final field at
     up to 256 `probes` (cells (i, j, k) of the logical grid; NaN while the cell is off the mask) and, over the in-mask cells of
     1 to 8 `regions` (half-open index boxes ((i0, i1), (j0, j1), (k0, k1)) inside the logical box, None: the whole grid, also
@@ -39,6 +39,7 @@ class FieldMonitor(_StepMonitor):
     GUARD_WORD = 0x5a5a5a5a5a5a5a5a
     MAX_PROBES = _lib.MONITOR_MAX_PROBES
     MAX_REGIONS = _lib.MONITOR_MAX_REGIONS
+    _keyword = 'monitor'
 
     def __init__(self, grid, probes=(), regions=(), capacity=4096, material_map=None, extra=None, t=0.0):
         shape = tuple(grid.shape)
@@ -277,6 +278,12 @@ class FieldMonitor(_StepMonitor):
             raise ValueError("FieldMonitor.record: dt must be finite and >= 0")
         self._launch_record(None, t_out)
         self.advance_clock(self.t, dt, 1)
+
+    def _record_step(self, t_in, out, dt, captured):
+        if captured:
+            self._launch_record(t_in, out)
+        else:
+            self.record(out, dt)                              # (its own signature: the non-captured half differs)
 
     def reset(self, t=0.0):
         """the log empty (slot 0), .t = t"""

@@ -1,5 +1,6 @@
-"""The Cartesian ADI step: the stage entry points, THE launch sequence (`_launch_step`), `adi_step_hip_coeff` with the
-reference's two names for it, and `StagedStepper`."""
+"""The Cartesian ADI step: the stage entry points, the record of the step's optional parts (`StepExtras`) with its checks
+(`_check_extras`), THE launch sequence (`_launch_step`), `adi_step_hip_coeff` with the reference's two names for it, and
+`StagedStepper`."""
 import ctypes
 
 import torch
@@ -12,7 +13,7 @@ from .packs import _fc_arg, MaterialMap, _MapLoss, _MapPhase
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .surface_loss import LossPacks
 from .phase import PhaseField, NonlinearPacks
-from .history import ThermalHistory, SolidificationRecord, _StepMonitor
+from .history import _StepRecorder
 
 
 def _gam(grid, mat, params):
@@ -128,44 +129,104 @@ def _ensure_general(pack):
         pack.d_qflux = L.empty(zero=True)
 
 
-def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material=None, solidification=None,
-                  material_map=None, monitor=None):
-    """TypeError / ValueError for an optional argument of the step that is of the wrong kind or was made for other packs, another
-    grid or another cp: once per adi_step_hip_coeff call and once per StagedStepper, before anything is launched"""
-    if material_map is not None:
-        if not isinstance(material_map, MaterialMap):
-            raise TypeError("material_map must be a MaterialMap")
-        if material_map.grid is not grid:
-            raise ValueError("material_map: the MaterialMap belongs to another grid")
-        if len(packs) != 3 or any(p is not q for p, q in zip(packs, material_map.packs)):
-            raise ValueError("material_map: the step must be given the MaterialMap's own packs (material_map.packs)")
-        m = material_map.mat
+class StepExtras:
+    """The eight optional parts of a step in one record: adi_step_hip_coeff and StagedStepper build it from their keywords,
+    _check_extras, _launch_step and StagedStepper.run take it.  A ninth part is a name here (and in `graph_key`), its check in
+    _check_extras, its line in _launch_step and its own module.
+        recorders   history, solidification, monitor: those present, in the order they launch; each keeps a clock of its own
+        stateful    phase, then the recorders: what a step changes besides the field (run() holds a snapshot of each over its
+                    warm-up steps; `material` is stateless and `surface_loss` is rewritten from the field at every step)"""
+    __slots__ = ('source', 'surface_loss', 'phase', 'history', 'material', 'solidification', 'material_map', 'monitor',
+                 'recorders')
+
+    def __init__(self, source=None, surface_loss=None, phase=None, history=None, material=None, solidification=None,
+                 material_map=None, monitor=None):
+        self.source, self.surface_loss, self.phase, self.history = source, surface_loss, phase, history
+        self.material, self.solidification, self.material_map, self.monitor = material, solidification, material_map, monitor
+        self.recorders = [x for x in (history, solidification, monitor) if x is not None]
+
+    @property
+    def stateful(self):
+        return self.recorders if self.phase is None else [self.phase] + self.recorders
+
+    def graph_key(self):
+        """What a graph captured by StagedStepper.run holds of the optional parts: one entry each, None for an absent one, in
+        the order below (the monitor's only when there is one: without it the key is what it was before there were monitors).
+        Every launch named here is captured with the step (X -> Y reads X, Y -> X reads Y).
+          source: the moving source, corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step
+            counter a captured tick advances -- power, origin, velocity, eta and f_f may change between runs without a new graph;
+            the extent of its support (shape_key) is what the key holds.
+          surface_loss: temperature-dependent surface loss, the packs' Robin coefficients rewritten from the step's INPUT buffer,
+            the first launch of every step; the law travels by value in that launch, so its parameters are the entry.
+          phase: latent heat, the correction of the step's OUTPUT buffer, the last launch before the recorders'; the law travels by
+            value and f and the summary by pointer, so all three are in the entry.
+          history: the record of the step input -> output and the tick of its block; the levels travel by value and the five
+            buffers by pointer.
+          material: k(T), cp(T) -- the Kirchhoff transform of the step's INPUT buffer (with the loss update, the first launches)
+            and the recovery of its OUTPUT buffer after sweep 2; the laws and the ambient travel by value, the Kirchhoff field by
+            pointer.  Stateless: the warm-up steps need no snapshot.
+          solidification: the record of the step input -> output and the tick of its block, after the history's; T_freeze and dx
+            travel by value and the five buffers by pointer.
+          material_map: several materials, the step's four launches are the MaterialMap's; its pair table travels by value in them
+            (so dt and theta, in run()'s key already, cover it) and its id field by pointer.  With it surface_loss is a
+            MapLossPacks (the laws in a device table by pointer, the ambient by value) and phase a MapPhaseField (laws by value,
+            f, the summary and the bricks' id sets by pointer): each answers graph_key() for itself.
+          monitor: the record of the step's OUTPUT buffer and the tick of its block, the last launches of all; probes, regions
+            and weights travel by value and its buffers by pointer."""
+        key = (None if self.source is None else self.source.shape_key(),) + tuple(
+            None if x is None else x.graph_key()
+            for x in (self.surface_loss, self.phase, self.history, self.material, self.solidification, self.material_map))
+        return key if self.monitor is None else key + (self.monitor.graph_key(),)
+
+
+def _check_extras(grid, mat, params, packs, extras):
+    """TypeError / ValueError for an optional part of the step that is of the wrong kind or was made for other packs, another
+    grid or another cp, and the rules about which parts combine: once per adi_step_hip_coeff call and once per StagedStepper,
+    before anything is launched.
+    One asymmetry, kept because code that builds a StagedStepper before `sync_mask` works and must go on working: the mask of
+    the solidification record is checked here, the history's is not -- adi_step_hip_coeff checks it itself before it launches,
+    StagedStepper.__init__ does not, and StagedStepper.run checks every recorder."""
+    x = extras
+    source, surface_loss, phase, material, mm = x.source, x.surface_loss, x.phase, x.material, x.material_map
+
+    def same_grid(kw, part, cls):
+        if part.grid is not grid:
+            raise ValueError("%s: the %s belongs to another grid" % (kw, cls))
+
+    def own_packs(kw, part, owner):
+        if len(packs) != 3 or any(p is not q for p, q in zip(packs, part.packs)):
+            raise ValueError("%s: the step must be given the %s own packs (%s.packs)" % (kw, owner, kw))
+
+    def own_material(kw, part, owner, why=""):
+        m = part.mat
         if (float(mat.rho), float(mat.cp), float(mat.k)) != (m.rho, m.cp, m.k):
-            raise ValueError("material_map: the step must be given the MaterialMap's own material (material_map.mat)")
+            raise ValueError("%s: the step must be given the %s own material (%s.mat)%s" % (kw, owner, kw, why))
+
+    if mm is not None:
+        if not isinstance(mm, MaterialMap):
+            raise TypeError("material_map must be a MaterialMap")
+        same_grid('material_map', mm, 'MaterialMap')
+        own_packs('material_map', mm, "MaterialMap's")
+        own_material('material_map', mm, "MaterialMap's")
         if source is not None:
             raise ValueError("material_map: a GoldakSource object cannot be combined with it (its sweep-0 correction assumes "
                              "uniform coupling); pass the source as a field, S=path.sample_step(grid, t, dt)")
         if ((surface_loss is not None and not isinstance(surface_loss, _MapLoss))
                 or (phase is not None and not isinstance(phase, _MapPhase)) or material is not None):
             raise ValueError("material_map: surface_loss= / phase= / material= cannot be combined with it; each assumes one cp")
-        if surface_loss is not None and surface_loss.mm is not material_map:
+        if surface_loss is not None and surface_loss.mm is not mm:
             raise ValueError("surface_loss: the MapLossPacks belongs to another MaterialMap")
-        if phase is not None and phase.mm is not material_map:
+        if phase is not None and phase.mm is not mm:
             raise ValueError("phase: the MapPhaseField belongs to another MaterialMap")
-        material_map._check_fresh()
+        mm._check_fresh()
         if phase is not None:
             phase._check_fresh()
     if material is not None:
         if not isinstance(material, NonlinearPacks):
             raise TypeError("material must be a NonlinearPacks")
-        if material.grid is not grid:
-            raise ValueError("material: the NonlinearPacks belongs to another grid")
-        if len(packs) != 3 or any(p is not q for p, q in zip(packs, material.packs)):
-            raise ValueError("material: the step must be given the NonlinearPacks' own packs (material.packs)")
-        m = material.mat
-        if (float(mat.rho), float(mat.cp), float(mat.k)) != (m.rho, m.cp, m.k):
-            raise ValueError("material: the step must be given the NonlinearPacks' own material (material.mat): the linear step "
-                             "runs with (rho, cp_ref, k_ref)")
+        same_grid('material', material, 'NonlinearPacks')
+        own_packs('material', material, "NonlinearPacks'")
+        own_material('material', material, "NonlinearPacks'", ": the linear step runs with (rho, cp_ref, k_ref)")
         if phase is not None or surface_loss is not None:
             raise ValueError("material: phase= / surface_loss= cannot be combined with it; the MaterialLaw carries the latent "
                              "heat and the NonlinearPacks the surface loss")
@@ -175,132 +236,106 @@ def _check_extras(grid, mat, params, packs, source, surface_loss, phase, history
     if source is not None and not isinstance(source, GoldakSource):
         raise TypeError("source must be a GoldakSource (pass a source field, e.g. ScanPath.sample_step, to "
                         "adi_step_numba_coeff)")
-    if surface_loss is not None and material_map is None:
+    if surface_loss is not None and mm is None:
         if not isinstance(surface_loss, LossPacks):
             raise TypeError("surface_loss must be a LossPacks")
-        if len(packs) != 3 or any(p is not q for p, q in zip(packs, surface_loss.packs)):
-            raise ValueError("surface_loss: the step must be given the LossPacks' own packs (surface_loss.packs)")
-    if phase is not None and material_map is None:
+        own_packs('surface_loss', surface_loss, "LossPacks'")
+    if phase is not None and mm is None:
         if not isinstance(phase, PhaseField):
             raise TypeError("phase must be a PhaseField")
-        if phase.grid is not grid:
-            raise ValueError("phase: the PhaseField belongs to another grid")
+        same_grid('phase', phase, 'PhaseField')
         if float(phase.mat.cp) != float(mat.cp):
             raise ValueError("phase: the PhaseField was made for cp = %r, the step runs with %r" % (phase.mat.cp, mat.cp))
-    if history is not None:
-        if not isinstance(history, ThermalHistory):
-            raise TypeError("history must be a ThermalHistory")
-        if history.grid is not grid:
-            raise ValueError("history: the ThermalHistory belongs to another grid")
-    if solidification is not None:
-        if not isinstance(solidification, SolidificationRecord):
-            raise TypeError("solidification must be a SolidificationRecord")
-        if solidification.grid is not grid:
-            raise ValueError("solidification: the SolidificationRecord belongs to another grid")
-        solidification._check_mask()
-    if monitor is not None:
-        if not isinstance(monitor, _StepMonitor):
-            raise TypeError("monitor must be a FieldMonitor")
-        if monitor.grid is not grid:
-            raise ValueError("monitor: the FieldMonitor belongs to another grid")
-        if monitor.material_map is not material_map:
-            raise ValueError("monitor: the FieldMonitor's material_map is not the step's")
+    for kw, cls in (('history', 'ThermalHistory'), ('solidification', 'SolidificationRecord'), ('monitor', 'FieldMonitor')):
+        rec = getattr(x, kw)
+        if rec is None:
+            continue
+        if not isinstance(rec, _StepRecorder) or rec._keyword != kw:
+            raise TypeError("%s must be a %s" % (kw, cls))
+        same_grid(kw, rec, cls)
+        if kw == 'solidification':
+            rec._check_mask()                              # (and not the history's: the asymmetry above)
+    if x.monitor is not None and x.monitor.material_map is not mm:
+        raise ValueError("monitor: the FieldMonitor's material_map is not the step's")
 
 
 def _no_mark():
     pass
 
 
-def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, d_S=None, source=None, owner=None, t_set=None,
-                 surface_loss=None, phase=None, history=None, captured=False, mark=_no_mark, material=None,
-                 solidification=None, material_map=None, monitor=None):
+def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, extras, d_S=None, owner=None, t_set=None, captured=False,
+                 mark=_no_mark):
     """THE launch sequence of one step t_in -> out (fp64 tensors in the grid's layout; nothing is allocated): the surface-loss
     update from t_in, the explicit stage and sweep 0 (one launch when `fused`), the moving source's correction of sweep 0's
-    output, sweeps 1 and 2, the latent-heat correction of `out`, the history record, the solidification record.  With `material` (a NonlinearPacks): its
-    `begin(t_in)` first, the launches above on its Kirchhoff field with Theta(Tinf) as the ambient, its `recover(t_in, out)`
-    after sweep 2, and the history and the solidification record on (t_in, out) as ever.  Every form of the step calls it --
-    adi_step_hip_coeff with or without a source field, StagedStepper.step, and what StagedStepper.run captures -- with
-    arguments that _check_extras has passed.
+    output, sweeps 1 and 2, the latent-heat correction of `out`, then the recorders in their order: the history record, the
+    solidification record, the monitor's.  With `extras.material` (a NonlinearPacks): its `begin(t_in)` first, the launches above
+    on its Kirchhoff field with Theta(Tinf) as the ambient, its `recover(t_in, out)` after sweep 2, and the recorders on (t_in,
+    out) as ever.  Every form of the step calls it -- adi_step_hip_coeff with or without a source field, StagedStepper.step, and
+    what StagedStepper.run captures -- with a StepExtras that _check_extras has passed.
     d_S: a source FIELD in the grid's layout; the explicit stage takes it (adi_explicit_rhs_src), never fused.
-    source, owner: a GoldakSource and the object that holds its device block and workspace; t_set: the step's start time if the
-    block is to be set here, just ahead of the correction (None: the caller has set it).
+    extras.source, owner: a GoldakSource and the object that holds its device block and workspace; t_set: the step's start time
+    if the block is to be set here, just ahead of the correction (None: the caller has set it).
     captured: a graph may replay these launches and the caller keeps the clocks: the source's block is ticked after the
-    correction, and the history and the solidification record launch their records without moving their host clocks.  Otherwise
-    no tick, and history.record / solidification.record.
+    correction, and the recorders launch their records without moving their host clocks.  Otherwise no tick, and each recorder's
+    public `record`.
     mark: called at the stage boundaries of per-stage timing: before the explicit stage, between it and sweep 0 when they are
     two launches, after sweep 0 with the source's correction, after sweep 1 and after sweep 2.
-    material_map: a MaterialMap: the explicit stage (with d_S, if any) and the three sweeps are ITS four launches
+    extras.material_map: a MaterialMap: the explicit stage (with d_S, if any) and the three sweeps are ITS four launches
     (adi_matmap_explicit, adi_matmap_sweep), never fused; with it `surface_loss` is a MapLossPacks, whose update from t_in comes
-    first, and `phase` a MapPhaseField, whose correction of `out` follows sweep 2; history and solidification follow as ever.
-    monitor: a FieldMonitor: its record of `out` and its tick are the last launches of all, after solidification's."""
+    first, and `phase` a MapPhaseField, whose correction of `out` follows sweep 2; the recorders follow as ever.
+    extras.monitor: a FieldMonitor: its record of `out` and its tick are the last launches of all, after solidification's."""
+    x, mm = extras, extras.material_map
     (ta, tb), _, _ = grid.scratch(2)
-    if material_map is not None:
-        material_map._check_fresh()
-        if surface_loss is not None:
-            surface_loss.update(t_in, Tinf)
-        mark()
-        material_map._explicit_into(t_in, d_S, ta, params)
-        for axis, (a, b) in enumerate(((ta, tb), (tb, ta), (ta, out))):
-            mark()
-            material_map._sweep_into(axis, a, b, params, Tinf)
-        mark()
-        if phase is not None:
-            phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
-        _record_step(t_in, out, params, history, solidification, captured, monitor)
-        return
     u = t_in                                               # what the linear step runs on
-    if material is not None:
-        u, Tinf = material.begin(t_in), material.theta_inf
-    if surface_loss is not None:
-        surface_loss.update(t_in, Tinf)
+    if mm is not None:
+        mm._check_fresh()
+        fused = False
+
+        def explicit(dst):
+            mm._explicit_into(u, d_S, dst, params)
+
+        def sweep(axis, a, b):
+            mm._sweep_into(axis, a, b, params, Tinf)
+    else:
+        if x.material is not None:
+            u, Tinf = x.material.begin(t_in), x.material.theta_inf
+
+        def explicit(dst):
+            if d_S is None:
+                kappa, _ = _gam(grid, mat, params)
+                check(lib.adi_explicit_rhs(_p(u), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt,
+                                           kappa, params.theta, _p(dst), _stream()))
+            else:
+                _explicit_src_into(u, d_S, dst, grid, mat, params)
+
+        def sweep(axis, a, b):
+            _sweep_into(axis, a, b, grid, mat, params, packs[axis], Tinf)
+    if x.surface_loss is not None:
+        x.surface_loss.update(t_in, Tinf)
     mark()
     if fused and d_S is None:
         _explicit_sweep0_into(u, tb, grid, mat, params, packs[0], Tinf)
     else:
-        if d_S is None:
-            kappa, _ = _gam(grid, mat, params)
-            check(lib.adi_explicit_rhs(_p(u), _p(grid.d_flags), *grid.layout.pd, grid.dx, params.dt,
-                                       kappa, params.theta, _p(ta), _stream()))
-        else:
-            _explicit_src_into(u, d_S, ta, grid, mat, params)
+        explicit(ta)
         mark()
-        _sweep_into(0, ta, tb, grid, mat, params, packs[0], Tinf)
-    if source is not None:
+        sweep(0, ta, tb)
+    if x.source is not None:
         if t_set is not None:
-            source.set_block(_source_block(owner), t_set, params.dt)
-        _source_lines0_into(tb, grid, mat, params, packs[0], source, owner)
+            x.source.set_block(_source_block(owner), t_set, params.dt)
+        _source_lines0_into(tb, grid, mat, params, packs[0], x.source, owner)
         if captured:
             check(lib.adi_source_tick(_p(_source_block(owner)), _stream()))
     mark()
-    _sweep_into(1, tb, ta, grid, mat, params, packs[1], Tinf)
+    sweep(1, tb, ta)
     mark()
-    _sweep_into(2, ta, out, grid, mat, params, packs[2], Tinf)
+    sweep(2, ta, out)
     mark()
-    if material is not None:
-        material.recover(t_in, out)
-    if phase is not None:
-        phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
-    _record_step(t_in, out, params, history, solidification, captured, monitor)
-
-
-def _record_step(t_in, out, params, history, solidification, captured, monitor=None):
-    """the last launches of a step: the history record, then the solidification record, then the monitor's, which reads the
-    step's final field alone (see _launch_step, `captured`)"""
-    if history is not None:
-        if captured:
-            history._launch_record(t_in, out)
-        else:
-            history.record(t_in, out, params.dt)
-    if solidification is not None:
-        if captured:
-            solidification._launch_record(t_in, out)
-        else:
-            solidification.record(t_in, out, params.dt)
-    if monitor is not None:
-        if captured:
-            monitor._launch_record(t_in, out)
-        else:
-            monitor.record(out, params.dt)
+    if x.material is not None:
+        x.material.recover(t_in, out)
+    if x.phase is not None:
+        x.phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
+    for rec in x.recorders:
+        rec._record_step(t_in, out, params.dt, captured)
 
 
 def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None, phase=None, history=None,
@@ -347,10 +382,10 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
         raise TypeError("adi_step_hip_coeff: a scan path enters the step as its field: S=path.sample_step(grid, t, dt) from the "
                         "host, or S=path.on_device().sample_step_device(grid, t, dt) evaluated on the device")
     source = S if isinstance(S, GoldakSource) else None
-    _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification, material_map,
-                  monitor)
+    extras = StepExtras(source, surface_loss, phase, history, material, solidification, material_map, monitor)
+    _check_extras(grid, mat, params, packs, extras)
     if history is not None:
-        history._check_mask()
+        history._check_mask()                              # (here and not in _check_extras: see there)
     t_in, kind = _as_state(Tn, grid)
     d_S = None
     if S is not None and source is None:
@@ -358,9 +393,7 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
             raise ValueError("S has shape %s, the grid %s" % (tuple(S.shape), grid.shape))
         d_S = grid.layout.to_layout(S, torch.float64)
     out = grid.layout.empty()
-    _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused_supported(grid), d_S=d_S, source=source, owner=grid, t_set=t,
-                 surface_loss=surface_loss, phase=phase, history=history, material=material, solidification=solidification,
-                 material_map=material_map, monitor=monitor)
+    _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused_supported(grid), extras, d_S=d_S, owner=grid, t_set=t)
     return _wrap(out, kind)
 
 
@@ -402,37 +435,10 @@ class StagedStepper:
 
     def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None, surface_loss=None, phase=None,
                  history=None, material=None, solidification=None, material_map=None, monitor=None):
-        _check_extras(grid, mat, params, packs, source, surface_loss, phase, history, material, solidification, material_map,
-                      monitor)
+        # the optional parts: what each does in a step and what a captured graph holds of it is written at StepExtras.graph_key
+        self.extras = StepExtras(source, surface_loss, phase, history, material, solidification, material_map, monitor)
+        _check_extras(grid, mat, params, packs, self.extras)
         self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
-        # temperature-dependent surface loss: the packs' Robin coefficients rewritten from the step's INPUT buffer, the first
-        # launch of every step -- captured with it (X -> Y reads X, Y -> X reads Y); the law travels by value in that launch,
-        # so its parameters are part of run()'s graph key
-        self.surface_loss = surface_loss
-        # latent heat: the correction of the step's OUTPUT buffer, the last launch of every step -- captured with it; the law
-        # travels by value and f and the summary by pointer, so all three are part of run()'s graph key
-        self.phase = phase
-        # thermal history: the record of the step input -> output and the tick of its block, the last launches of every step
-        # -- captured with it; the levels travel by value and the five buffers by pointer, so all are part of run()'s graph key
-        self.history = history
-        # solidification record: the record of the step input -> output and the tick of its block, after the history's --
-        # captured with them; T_freeze and dx travel by value and the five buffers by pointer: part of run()'s graph key
-        self.solidification = solidification
-        # k(T), cp(T): the Kirchhoff transform of the step's INPUT buffer (with the loss update, the first launches) and the
-        # recovery of its OUTPUT buffer after sweep 2 -- captured with it; the laws and the ambient travel by value, the
-        # Kirchhoff field by pointer, so all are part of run()'s graph key.  Stateless: the warm-up steps need no snapshot
-        self.material = material
-        # several materials: the step's four launches are the MaterialMap's; its pair table travels by value in them (so dt and
-        # theta, already in run()'s graph key, cover it) and its id field by pointer: graph_key() is part of the key.  With it
-        # surface_loss is a MapLossPacks (the laws in a device table by pointer, the ambient by value) and phase a MapPhaseField
-        # (laws by value, f, the summary and the bricks' id sets by pointer): their graph_key() joins the key
-        self.material_map = material_map
-        # field monitor: the record of the step's OUTPUT buffer and the tick of its block, the last launches of all -- captured
-        # with them; probes, regions and weights travel by value and its buffers by pointer: part of run()'s graph key
-        self.monitor = monitor
-        # moving source: corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step counter
-        # a captured tick advances -- power, origin, velocity, eta and f_f may change between runs without a new graph
-        self.source = source
         self.captures = 0              # HIP graphs captured by run() so far
         self.fused = fused_supported(grid) if fused is None else (bool(fused) and fused_supported(grid))
         if material_map is not None:
@@ -457,10 +463,8 @@ class StagedStepper:
 
     def _step_into(self, t, out, captured=True, mark=_no_mark):
         """one step t -> out (both native-layout device tensors), no allocation: what a HIP graph captures"""
-        _launch_step(t, out, self.grid, self.mat, self.params, self.packs, self.Tinf, self.fused, source=self.source, owner=self,
-                     surface_loss=self.surface_loss, phase=self.phase, history=self.history, captured=captured, mark=mark,
-                     material=self.material, solidification=self.solidification, material_map=self.material_map,
-                     monitor=self.monitor)
+        _launch_step(t, out, self.grid, self.mat, self.params, self.packs, self.Tinf, self.fused, self.extras, owner=self,
+                     captured=captured, mark=mark)
 
     def run(self, T, nsteps, graph=True, t0=0.0):
         """The drivers' `nsub` loop (quick_compare_dirichlet_robin.py:169-178, waam_from_stl_v7_mm.py:525-528): `nsteps`
@@ -473,22 +477,12 @@ class StagedStepper:
         extent recaptures."""
         g, prm = self.grid, self.params
         nsteps = int(nsteps)
+        x = self.extras
         key = (float(prm.dt), float(prm.theta), self.Tinf, g.mask_version, tuple(id(p) for p in self.packs),
                tuple(getattr(p, 'mask_version', None) for p in self.packs),
-               tuple(None if p.d_coeff is None else p.d_coeff.data_ptr() for p in self.packs), self.fused,
-               None if self.source is None else self.source.shape_key(),
-               None if self.surface_loss is None else (self.surface_loss.graph_key() if self.material_map is not None
-                                                       else self.surface_loss.loss.key()),
-               None if self.phase is None else self.phase.graph_key(),
-               None if self.history is None else self.history.graph_key(),
-               None if self.material is None else self.material.graph_key(),
-               None if self.solidification is None else self.solidification.graph_key(),
-               None if self.material_map is None else self.material_map.graph_key())
-        if self.monitor is not None:                       # (without one the key is what it was)
-            key = key + (self.monitor.graph_key(),)
-        clocked = [x for x in (self.history, self.solidification, self.monitor) if x is not None]   # each its own clock
-        for x in clocked:
-            x._check_mask()
+               tuple(None if p.d_coeff is None else p.d_coeff.data_ptr() for p in self.packs), self.fused) + x.graph_key()
+        for rec in x.recorders:
+            rec._check_mask()
         st = getattr(self, '_graph', None)
         if st is None or st['key'] != key:
             # (zeroed where the box is padded, as Layout.to_layout does: the cells outside the logical grid are identity rows of
@@ -497,19 +491,18 @@ class StagedStepper:
             st = self._graph = dict(key=key, X=X, Y=Y, g=None)
         X, Y = st['X'], st['Y']
         X.copy_(g.layout.to_layout(T, torch.float64))
-        if self.source is not None:
-            self.source.set_block(_source_block(self), t0, prm.dt)
+        if x.source is not None:
+            x.source.set_block(_source_block(self), t0, prm.dt)
         if graph and nsteps >= 2 and st['g'] is None:
             g.scratch(2)                                   # every buffer exists before the capture
-            stateful = [x for x in (self.phase, self.history, self.solidification, self.monitor) if x is not None]
-            held = [x.snapshot() for x in stateful]        # (the warm-up steps would advance f, the recorders, log and clocks)
-            for x in clocked:
-                x.set_clock(prm.dt)
+            held = [s.snapshot() for s in x.stateful]      # (the warm-up steps would advance f, the recorders, log and clocks)
+            for rec in x.recorders:
+                rec.set_clock(prm.dt)
             self._step_into(X, Y); self._step_into(Y, X)   # warm-up outside the capture (lazy module loads, and the
             self._step_into(X, Y); self._step_into(Y, X)   # no-fallback promise is learnt on the third step); harmless:
             X.copy_(g.layout.to_layout(T, torch.float64))  # X is restored
-            for x, snap in zip(stateful, held):
-                x.restore(snap)                            # ... and so is what the extras hold
+            for s, snap in zip(x.stateful, held):
+                s.restore(snap)                            # ... and so is what the extras hold
             torch.cuda.synchronize()
             cg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(cg):
@@ -517,10 +510,10 @@ class StagedStepper:
                 self._step_into(Y, X)
             st['g'] = cg
             self.captures += 1
-        if self.source is not None:
-            self.source.set_block(_source_block(self), t0, prm.dt)   # (after the warm-up: the counter starts at 0)
-        for x in clocked:
-            x.set_clock(prm.dt)                            # (likewise; the recorder's own clock, not t0)
+        if x.source is not None:
+            x.source.set_block(_source_block(self), t0, prm.dt)   # (after the warm-up: the counter starts at 0)
+        for rec in x.recorders:
+            rec.set_clock(prm.dt)                          # (likewise; each recorder's own clock, not t0)
         done = 0
         if graph and st['g'] is not None:
             for _ in range(nsteps // 2):
@@ -530,8 +523,8 @@ class StagedStepper:
         for _ in range(nsteps - done):
             self._step_into(cur, oth)
             cur, oth = oth, cur
-        for x in clocked:
-            x.advance_clock(x.t, float(prm.dt), nsteps)
+        for rec in x.recorders:
+            rec.advance_clock(rec.t, float(prm.dt), nsteps)
         out = g.layout.empty()
         out.copy_(cur)
         return DeviceField(out)
@@ -539,8 +532,8 @@ class StagedStepper:
     def step(self, T, events=None, t=0.0):
         """one step from time t (the source, if any, at t + dt/2)"""
         g, prm = self.grid, self.params
-        if self.source is not None:
-            self.source.set_block(_source_block(self), t, prm.dt)
+        if self.extras.source is not None:
+            self.extras.source.set_block(_source_block(self), t, prm.dt)
         t_in = g.layout.to_layout(T, torch.float64)
         out = g.layout.empty()
         ev = iter(events or ())

@@ -164,6 +164,10 @@ class LossPacks:
         self._launch(T, Tinf, 0, self.grid.layout.pz, 0)
         return self.packs
 
+    def graph_key(self):
+        """what a captured launch holds of the loss: the law, by value"""
+        return self.loss.key()
+
     def rebuild(self, T, k_begin=0, k_end=None, Tinf=None):
         """the full mode on the planes [k_begin, k_end) of axis 2 (clipped to the box), for the grid's CURRENT mask"""
         g, m = self.grid, self.mat

@@ -112,16 +112,6 @@ def monitor_result(mon, mat):
     return mon.traces(), mon.region_log(mat)
 
 
-def _monitor(backend, grid, spec, rows, t=0.0):
-    """the FieldMonitor of a run from `spec`, a dict of its constructor's keyword arguments; the capacity is the run's"""
-    if spec is None:
-        return None
-    kw = dict(spec)
-    kw['capacity'] = max(1, int(rows))
-    kw.setdefault('t', t)
-    return backend.FieldMonitor(grid, **kw)
-
-
 def _is_device_backend(backend):
     return hasattr(backend, 'to_device')
 
@@ -135,18 +125,50 @@ def _require_device_loop(who, backend, dev_loop, **asked):
             raise ValueError("%s: %s needs the device loop of a backend with %s" % (who, name, cls))
 
 
-def _extras_kw(lpacks, ph, hist, nm=None, sol=None, mon=None):
-    """the keywords of a step / a stepper for the extras that are present"""
-    return {k: v for k, v in (('surface_loss', lpacks), ('phase', ph), ('history', hist), ('material', nm),
-                              ('solidification', sol), ('monitor', mon)) if v is not None}
+class _LoopExtras:
+    """The bookkeeping of the optional parts that live through a device loop, once for the three run_* loops: the PhaseField
+    (`ph`), the ThermalHistory (`hist`), the SolidificationRecord (`sol`) and the FieldMonitor (`mon`) of the backend, each None
+    when its option is.  T: the field they are seeded from (phase_T: the PhaseField's; None seeds nothing, all solid); rows: the
+    capacity of the history's log and the monitor's; t: where their clocks start."""
 
+    def __init__(self, backend, grid, mat, T, rows=1, t=0.0, phase_T=None, phase_change=None, history=None, solidification=None,
+                 monitor=None):
+        self.mat = mat
+        self.ph = self.hist = self.sol = self.mon = None
+        if phase_change is not None:
+            self.ph = backend.PhaseField(grid, mat, phase_change, T=phase_T)
+        if history is not None:
+            self.hist = backend.ThermalHistory(grid, history, capacity=rows, T=T, t=t)
+        if solidification is not None:
+            self.sol = backend.SolidificationRecord(grid, solidification, T=T, t=t)
+        if monitor is not None:                        # (a dict of FieldMonitor's keywords; the capacity is the run's)
+            self.mon = backend.FieldMonitor(grid, **dict(dict({'t': t}, **monitor), capacity=max(1, int(rows))))
 
-def _sync_extras(T, ph, hist, sol=None):
-    """after a birth / a new column: the newborn cells at f_eq(T), at T_peak = T and "never froze" (cells born above T_freeze
-    set their brick's word)"""
-    for x in (ph, hist, sol):
-        if x is not None:
-            x.sync_mask(T)
+    def step_kw(self, surface_loss=None, material=None):
+        """the keywords of a step / a stepper for the parts that are present, with the loop's LossPacks or NonlinearPacks"""
+        return {k: v for k, v in (('surface_loss', surface_loss), ('phase', self.ph), ('history', self.hist),
+                                  ('material', material), ('solidification', self.sol), ('monitor', self.mon)) if v is not None}
+
+    def sync(self, T):
+        """after a birth / a new column / a deposit: the newborn cells at f_eq(T), at T_peak = T and "never froze" (cells born
+        above T_freeze set their brick's word); the monitor is stateless"""
+        for x in (self.ph, self.hist, self.sol):
+            if x is not None:
+                x.sync_mask(T)
+
+    def idle(self, seconds):
+        """an interval without a step: the global time moves on all the same"""
+        for x in (self.hist, self.sol, self.mon):
+            if x is not None:
+                x.t = x.t + seconds
+
+    def results(self):
+        """what a loop's return value ends with, for the parts that are present: the liquid fraction, history_result,
+        solidification_result, the two of monitor_result"""
+        res = () if self.ph is None else (np.asarray(self.ph.liquid_fraction),)
+        res = res if self.hist is None else res + (history_result(self.hist),)
+        res = res if self.sol is None else res + (solidification_result(self.sol),)
+        return res if self.mon is None else res + monitor_result(self.mon, self.mat)
 
 
 def _step(backend, T, grid, mat, params, packs, Tinf):
@@ -205,7 +227,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         nonlocal T, nsteps
         nsub = max(1, int(math.ceil(seg / dt_cap)))
         params.dt = max(seg / nsub, 1e-15)
-        kw = _extras_kw(None if surface_loss is None else bpacks, ph, hist, sol=sol, mon=mon)
+        kw = ex.step_kw(surface_loss=None if surface_loss is None else bpacks)
         if nsub >= GRAPH_MIN_NSUB and hasattr(backend, 'StagedStepper') and hasattr(T, 'fill_where'):
             # a long segment on the device backend: the nsub launches of this segment replayed from a HIP graph
             T = backend.StagedStepper(grid, mat, params, packs, Tinf, **kw).run(T, nsub)
@@ -225,7 +247,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     dev_loop = device_loop and device_resident and hasattr(backend, 'BirthPacks') and hasattr(T, 'fill_where')
     _require_device_loop('run_layer_birth', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
                          history=history, solidification=solidification, monitor=monitor)
-    ph = hist = sol = mon = None
+    ex = _LoopExtras(backend, grid, mat, T)                            # (nothing was asked for where there is no device loop)
     if dev_loop:
         import torch
         d_full = grid.layout.to_layout(mask_full, torch.uint8)
@@ -238,16 +260,13 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         packs = bpacks.packs
         plane_cells = np.asarray(mask_full).sum(axis=(0, 1)).astype(np.int64)      # newborn cells per plane, host-known
         plane_born = np.zeros(nz, dtype=bool)
-        if phase_change is not None:
-            ph = backend.PhaseField(grid, mat, phase_change)           # nothing is active yet: all solid
+        rows = 1
         if history is not None or monitor is not None:                 # one log row per sub-step the schedule can ask for
-            rows = sum(max(1, int(math.ceil(a / dt_cap))) for w, a in layer_birth_schedule(times_birth, times_out)
-                       if w == 'advance')
-        mon = _monitor(backend, grid, monitor, rows if monitor is not None else 1)
-        if history is not None:
-            hist = backend.ThermalHistory(grid, history, capacity=max(1, rows), T=T)
-        if solidification is not None:
-            sol = backend.SolidificationRecord(grid, solidification, T=T)
+            rows = max(1, sum(max(1, int(math.ceil(a / dt_cap))) for w, a in layer_birth_schedule(times_birth, times_out)
+                              if w == 'advance'))
+        # (the PhaseField unseeded: nothing is active yet, all solid)
+        ex = _LoopExtras(backend, grid, mat, T, rows, phase_change=phase_change, history=history, solidification=solidification,
+                         monitor=monitor)
     else:
         packs = build_packs()
     n_active = 0
@@ -264,7 +283,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
                 packs = bpacks.update(ks - 1, ke + 2)                             # :534, the planes that changed
             else:
                 packs = bpacks.rebuild(T, ks - 1, ke + 2)
-            _sync_extras(T, ph, hist, sol)
+            ex.sync(T)
             return
         born = np.zeros_like(mask_full, dtype=bool)
         born[:, :, ks:ke + 1] = mask_full[:, :, ks:ke + 1]
@@ -281,17 +300,12 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
             if n_active > 0:                           # no ADI steps while nothing is active (:524)
                 advance(arg)
             else:
-                for x in (hist, sol, mon):
-                    if x is not None:
-                        x.t = x.t + arg                # (the global time moves on all the same)
+                ex.idle(arg)
         elif what == 'birth':
             birth(*layers[arg])
         elif on_frame is not None:
             on_frame(arg, np.asarray(T), d_act.cpu().contiguous().numpy().astype(bool) if dev_loop else mask_act.copy())
-    res = (np.asarray(T), nsteps) + (() if ph is None else (np.asarray(ph.liquid_fraction),))
-    res = res if hist is None else res + (history_result(hist),)
-    res = res if sol is None else res + (solidification_result(sol),)
-    return res if mon is None else res + monitor_result(mon, mat)
+    return (np.asarray(T), nsteps) + ex.results()
 
 
 def track_source(heat_source, track_box, dx, yi, t_step):
@@ -364,13 +378,9 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
                                     loss=surface_loss if surface_loss is not None else backend.SurfaceLoss(h=h))
         mat = nm.mat
     lpacks = backend.LossPacks(grid, mat, surface_loss, Tinf) if surface_loss is not None and nm is None else None
-    ph = backend.PhaseField(grid, mat, phase_change, T=T) if phase_change is not None else None
-    hist = None
-    if history is not None:
-        hist = backend.ThermalHistory(grid, history, capacity=ncol * max(1, int(math.ceil(t_step / dt))), T=T)
-    sol = backend.SolidificationRecord(grid, solidification, T=T) if solidification is not None else None
-    mon = _monitor(backend, grid, monitor, ncol * max(1, int(math.ceil(t_step / dt))))
-    kw = _extras_kw(lpacks, ph, hist, nm, sol, mon)
+    ex = _LoopExtras(backend, grid, mat, T, ncol * max(1, int(math.ceil(t_step / dt))), phase_T=T, phase_change=phase_change,
+                     history=history, solidification=solidification, monitor=monitor)
+    kw = ex.step_kw(surface_loss=lpacks, material=nm)
     for yi in range(ncol):
         if dev_loop:
             d_mask[x0:x1, yi:yi + 1, z0:z1] = 1
@@ -383,7 +393,7 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         T[x0:x1, yi:yi + 1, z0:z1] = T_track
         if lpacks is not None or nm is not None:
             packs = (nm or lpacks).rebuild(T)        # the column changed the exposure: every cell, stale ones zeroed
-        _sync_extras(T, ph, hist, sol)
+        ex.sync(T)
         n_sub = max(1, int(math.ceil(t_step / dt)))
         dt_orig = params.dt
         params.dt = t_step / n_sub
@@ -402,13 +412,7 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
             for i in range(n_sub):
                 T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=src, t=i * params.dt)
         params.dt = dt_orig
-    res = (np.asarray(T),) + (() if ph is None else (np.asarray(ph.liquid_fraction),))
-    if hist is not None:
-        res = res + (history_result(hist),)
-    if sol is not None:
-        res = res + (solidification_result(sol),)
-    if mon is not None:
-        res = res + monitor_result(mon, mat)
+    res = (np.asarray(T),) + ex.results()
     return res if len(res) > 1 else res[0]
 
 
@@ -464,18 +468,16 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
     bpacks = backend.BirthPacks(grid, mat, robin_h=robin) if surface_loss is None else \
         backend.LossPacks(grid, mat, surface_loss, Tinf)
     packs = bpacks.packs
-    ph = backend.PhaseField(grid, mat, phase_change, T=T) if phase_change is not None else None
-    hist = backend.ThermalHistory(grid, history, capacity=max(1, len(steps)), T=T, t=src.t_start) if history is not None else None
-    sol = backend.SolidificationRecord(grid, solidification, T=T, t=src.t_start) if solidification is not None else None
-    mon = _monitor(backend, grid, monitor, len(steps), t=src.t_start)
-    kw = _extras_kw(None if surface_loss is None else bpacks, ph, hist, sol=sol, mon=mon)
+    ex = _LoopExtras(backend, grid, mat, T, max(1, len(steps)), t=src.t_start, phase_T=T, phase_change=phase_change,
+                     history=history, solidification=solidification, monitor=monitor)
+    kw = ex.step_kw(surface_loss=None if surface_loss is None else bpacks)
     live = bool(np.asarray(base_mask).any())
     nsteps = 0
     for t, d in steps:
         rng = dep.deposit(T, t, d)
         if rng is not None:                            # something could have been born: the planes that changed
             packs = bpacks.update(*rng) if surface_loss is None else bpacks.rebuild(T, *rng)
-            _sync_extras(T, ph, hist, sol)
+            ex.sync(T)
             live = True
         if live:
             params.dt = d
@@ -483,16 +485,10 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
             T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=S, t=t, **kw)
             nsteps += 1
         else:
-            for x in (hist, sol, mon):
-                if x is not None:
-                    x.t = x.t + d                      # (the global time moves on all the same)
+            ex.idle(d)
         if on_frame is not None:
             on_frame(t + d, np.asarray(T), grid.d_mask.cpu().contiguous().numpy().astype(bool))
-    res = (np.asarray(T), grid.d_mask.cpu().contiguous().numpy().astype(bool), nsteps)
-    res = res + (() if ph is None else (np.asarray(ph.liquid_fraction),))
-    res = res if hist is None else res + (history_result(hist),)
-    res = res if sol is None else res + (solidification_result(sol),)
-    return res if mon is None else res + monitor_result(mon, mat)
+    return (np.asarray(T), grid.d_mask.cpu().contiguous().numpy().astype(bool), nsteps) + ex.results()
 
 
 def ring_source(heat_source, R_in, wall, z_top, tau):

@@ -138,7 +138,7 @@ def test_check_extras_refuses_before_any_launch(mods, steel):
     prm = hip.Params(0.01, 0.5)
 
     def check(grid=grid, mat=nm.mat, prm=prm, packs=packs, surface_loss=None, phase=None, material=nm):
-        step._check_extras(grid, mat, prm, packs, None, surface_loss, phase, None, material)
+        step._check_extras(grid, mat, prm, packs, step.StepExtras(surface_loss=surface_loss, phase=phase, material=material))
     check()
     with pytest.raises(TypeError, match='NonlinearPacks'):
         check(material=steel)

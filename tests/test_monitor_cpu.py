@@ -290,15 +290,15 @@ def test_check_extras_refuses_a_foreign_monitor(FM):
     mon = FM.__new__(FM)
     mon.grid, mon.material_map = g1, None
     prm = types.SimpleNamespace(dt=0.1, theta=0.5)
-    args = (None, prm, (), None, None, None, None)
-    step._check_extras(g1, *args, monitor=mon)
+    args = (None, prm, ())
+    step._check_extras(g1, *args, step.StepExtras(monitor=mon))
     with pytest.raises(ValueError, match='belongs to another grid'):
-        step._check_extras(g2, *args, monitor=mon)
+        step._check_extras(g2, *args, step.StepExtras(monitor=mon))
     with pytest.raises(TypeError, match='must be a FieldMonitor'):
-        step._check_extras(g1, *args, monitor=object())
+        step._check_extras(g1, *args, step.StepExtras(monitor=object()))
     mon.material_map = object()
     with pytest.raises(ValueError, match="material_map is not the step's"):
-        step._check_extras(g1, *args, monitor=mon)
+        step._check_extras(g1, *args, step.StepExtras(monitor=mon))
 
 
 def test_the_waam_loops_refuse_a_monitor_on_other_backends():
