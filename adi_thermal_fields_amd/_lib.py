@@ -177,6 +177,9 @@ SIGNATURES = {
     'adi_bead_deposit': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                  c_int, c_int, c_int, c_int, c_long, c_double, c_double, c_double, c_double, c_void_p,
                                  c_void_p]),
+    'adi_bead_deposit_ids': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_double, c_double, c_double,
+                                     c_double, c_void_p, c_void_p]),
     'adi_surface_loss_update': (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double,
                                         c_double, c_double, c_void_pp, c_int, c_int, c_int, c_void_p]),
     'adi_phase_summary_words': (ctypes.c_long, [c_int, c_int, c_int]),
@@ -212,6 +215,11 @@ SIGNATURES = {
     'adi_matmap_build_coeffs': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_int, c_double_p,
                                         c_int_p, c_double_p, c_void_pp, c_int_p, c_double_p, c_void_pp, c_void_pp, c_void_pp,
                                         c_void_p]),
+    'adi_matmap_build_coeffs_planes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_int, c_double_p,
+                                               c_int_p, c_double_p, c_void_pp, c_int_p, c_double_p, c_void_pp, c_void_pp,
+                                               c_void_pp, c_int, c_int, c_void_p]),
+    'adi_matmap_source_add_r0': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double,
+                                         c_double, c_int, c_double_p, c_void_p]),
     'adi_matmap_explicit': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_double_p,
                                     c_double_p, c_double, c_double, c_void_p, c_void_p]),
     'adi_matmap_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, c_long, ctypes.POINTER(c_size_t)]),

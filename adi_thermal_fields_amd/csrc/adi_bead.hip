@@ -1,7 +1,8 @@
 // adi_bead.hip -- the bead a scan path lays during a step (include/adi_hip.h, "Bead deposition along a scan path"):
 //   adi_bead_index_box     the index box that holds every cell a step can bear, on the host: no HIP call
 //   adi_bead_deposit_host  the evaluator (adi_bead_eval.hpp) on the CPU over host arrays: no HIP call
-//   k_bead_deposit         the births of a step on the device: T = Ts and active = 1 on the newborn cells of the launch box
+//   k_bead_deposit         the births of a step on the device: T = Ts and active = 1 on the newborn cells of the launch box,
+//                          and their material id where the grid has an id field (adi_bead_deposit_ids)
 // The launch box comes from the HOST table inside the entry point and is clipped to the logical box, which lies inside the
 // physical one: no argument of the caller is an address range.  K travels by value and bounds every loop over segments.
 #include "adi_bead_eval.hpp"
@@ -18,11 +19,12 @@ struct BeadPathArg {
 };
 
 // One thread per cell of the launch box B (consecutive threads along axis 2), 64-bit cell indices.  A cell that is active
-// already, or outside `within`, is decided before any arithmetic; T and active are written on newborn cells only.
+// already, or outside `within`, is decided before any arithmetic; T and active are written on newborn cells only, and so is
+// ids (optional: the id field of a grid of several materials), which gets `id` there.
 __global__ __launch_bounds__(256) void k_bead_deposit(BeadPathArg P, ScanBox B, Lay L, double dx, double t, double t1, double Ts,
                                                       double *__restrict__ T, uint8_t *__restrict__ active,
-                                                      const uint8_t *__restrict__ within,
-                                                      unsigned long long *__restrict__ n_new)
+                                                      const uint8_t *__restrict__ within, uint8_t *__restrict__ ids,
+                                                      unsigned id, unsigned long long *__restrict__ n_new)
 {
 #pragma clang fp contract(off)
     const long bj = B.hi[1] - B.lo[1], bk = B.hi[2] - B.lo[2];
@@ -38,6 +40,7 @@ __global__ __launch_bounds__(256) void k_bead_deposit(BeadPathArg P, ScanBox B, 
         if (active[p] == 0 && (within == nullptr || within[p] != 0) &&
             bead_inside_step(P.b, P.tab, P.K, P.t_end, P.k0, P.k1, t, t1, (i + 0.5) * dx, (j + 0.5) * dx, (k + 0.5) * dx)) {
             T[p] = Ts; active[p] = 1; born = 1;
+            if (ids != nullptr) ids[p] = (uint8_t)id;
         }
     }
     const unsigned long long b = __ballot(born);
@@ -77,6 +80,34 @@ static bool step_box(const adi_bead_shape &b, const double *tab, int K, double t
     return bead_window_box(b, tab, K, t_end, k0, k1, t, t1, n, dx, B);
 }
 
+// adi_bead_deposit (d_ids null) and adi_bead_deposit_ids; fn names the entry in the error text
+static int bead_deposit(const char *fn, const adi_bead_shape *shape, const double *h_table, const double *d_table, int K,
+                        double t_end, double *d_T, uint8_t *d_active, const uint8_t *d_within, uint8_t *d_ids, int id, int lx,
+                        int ly, int lz, int nx, int ny, int nz, long plane_stride, double dx, double t, double dt, double Ts,
+                        unsigned long long *d_newborn, void *stream)
+{
+    if (int rc = check_step(shape, h_table, K, t_end, lx, ly, lz, dx, t, dt, fn)) return rc;
+    ADI_REQUIRE(std::isfinite(Ts), "%s: non-finite Ts", fn);
+    ADI_REQUIRE(d_table && d_T && d_active && d_newborn, "%s: null argument", fn);
+    ADI_REQUIRE(d_active != d_within, "%s: the active mask aliases `within`", fn);
+    ADI_REQUIRE(lx <= nx && ly <= ny && lz <= nz, "%s: the logical box %d x %d x %d exceeds the physical %d x %d x %d", fn,
+                lx, ly, lz, nx, ny, nz);
+    Lay L;
+    if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
+    ScanBox B;
+    int k0, k1;
+    step_box(*shape, h_table, K, t_end, lx, ly, lz, dx, t, dt, B, k0, k1);
+    hipStream_t st = as_stream(stream);
+    ADI_HIP_TRY(hipMemsetAsync(d_newborn, 0, sizeof(unsigned long long), st));
+    if (scan_box_empty(B)) return ADI_OK;
+    const long total = (long)(B.hi[0] - B.lo[0]) * (B.hi[1] - B.lo[1]) * (B.hi[2] - B.lo[2]);   // < 2^32: inside the box of L
+    const BeadPathArg P{*shape, d_table, K, k0, k1, t_end};
+    hipLaunchKernelGGL(k_bead_deposit, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, L, dx, t, t + dt, Ts, d_T,
+                       d_active, d_within, d_ids, (unsigned)id, d_newborn);
+    ADI_CHECK_LAUNCH();
+    return ADI_OK;
+}
+
 }  // namespace adi
 
 using namespace adi;
@@ -109,26 +140,20 @@ int adi_bead_deposit(const adi_bead_shape *shape, const double *h_table, const d
                      uint8_t *d_active, const uint8_t *d_within, int lx, int ly, int lz, int nx, int ny, int nz,
                      long plane_stride, double dx, double t, double dt, double Ts, unsigned long long *d_newborn, void *stream)
 {
-    if (int rc = check_step(shape, h_table, K, t_end, lx, ly, lz, dx, t, dt, "adi_bead_deposit")) return rc;
-    ADI_REQUIRE(std::isfinite(Ts), "adi_bead_deposit: non-finite Ts");
-    ADI_REQUIRE(d_table && d_T && d_active && d_newborn, "adi_bead_deposit: null argument");
-    ADI_REQUIRE(d_active != d_within, "adi_bead_deposit: the active mask aliases `within`");
-    ADI_REQUIRE(lx <= nx && ly <= ny && lz <= nz, "adi_bead_deposit: the logical box %d x %d x %d exceeds the physical %d x %d x %d",
-                lx, ly, lz, nx, ny, nz);
-    Lay L;
-    if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
-    ScanBox B;
-    int k0, k1;
-    step_box(*shape, h_table, K, t_end, lx, ly, lz, dx, t, dt, B, k0, k1);
-    hipStream_t st = as_stream(stream);
-    ADI_HIP_TRY(hipMemsetAsync(d_newborn, 0, sizeof(unsigned long long), st));
-    if (scan_box_empty(B)) return ADI_OK;
-    const long total = (long)(B.hi[0] - B.lo[0]) * (B.hi[1] - B.lo[1]) * (B.hi[2] - B.lo[2]);   // < 2^32: inside the box of L
-    const BeadPathArg P{*shape, d_table, K, k0, k1, t_end};
-    hipLaunchKernelGGL(k_bead_deposit, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, B, L, dx, t, t + dt, Ts, d_T,
-                       d_active, d_within, d_newborn);
-    ADI_CHECK_LAUNCH();
-    return ADI_OK;
+    return bead_deposit("adi_bead_deposit", shape, h_table, d_table, K, t_end, d_T, d_active, d_within, nullptr, 0, lx, ly, lz, nx,
+                        ny, nz, plane_stride, dx, t, dt, Ts, d_newborn, stream);
+}
+
+int adi_bead_deposit_ids(const adi_bead_shape *shape, const double *h_table, const double *d_table, int K, double t_end,
+                         double *d_T, uint8_t *d_active, const uint8_t *d_within, uint8_t *d_ids, int id, int lx, int ly, int lz,
+                         int nx, int ny, int nz, long plane_stride, double dx, double t, double dt, double Ts,
+                         unsigned long long *d_newborn, void *stream)
+{
+    ADI_REQUIRE(d_ids != nullptr, "adi_bead_deposit_ids: null id field");
+    ADI_REQUIRE(id >= 0 && id < ADI_MATMAP_MAX, "adi_bead_deposit_ids: material id %d (0 to %d)", id, ADI_MATMAP_MAX - 1);
+    ADI_REQUIRE(d_ids != d_active && d_ids != d_within, "adi_bead_deposit_ids: the id field aliases a mask");
+    return bead_deposit("adi_bead_deposit_ids", shape, h_table, d_table, K, t_end, d_T, d_active, d_within, d_ids, id, lx, ly, lz,
+                        nx, ny, nz, plane_stride, dx, t, dt, Ts, d_newborn, stream);
 }
 
 }  // extern "C"

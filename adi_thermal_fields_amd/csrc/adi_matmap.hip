@@ -1,7 +1,8 @@
 // adi_matmap.hip -- the Cartesian step on a grid of several materials (include/adi_hip.h, "Several materials"; DESIGN.md
 // section 6l): every cell carries a material id, the coupling of a cell to a neighbour is the pair-table entry
 // G[own id][neighbour's id], and each row is divided by its own C = rho cp.  Hand-written HIP for gfx950:
-//   k_matmap_build_coeffs   Robin coefficient + Neumann flux fields of the three axes, (h A) / (C_id V) per exposed face
+//   k_matmap_build_coeffs   Robin coefficient + Neumann flux fields of the three axes, (h A) / (C_id V) per exposed face;
+//                           k_mapcoeffs_planes: the same cells' values on a range of axis-2 planes only
 //   k_matmap_explicit       R0 = T + (1 - theta) sum G[id][id_n] (T_n - T)  [+ dt S / C_id]
 //   k_matmap_sweep_contig   sweep along memory axis 2: a line's segments in the lanes of one wave (condense / pcr_solve /
 //                           back_solve of adi_core.hpp with per-row off-diagonals), lines of at most kMaxFastLine rows
@@ -21,19 +22,15 @@ struct MapFaceSpec {
 };
 
 // k_build_coeffs (adi_fields.hip) with the cell's own heat capacity: '-' face then '+' face per axis, (h * A) / (C_id * V) with
-// IEEE division, contraction off -> bit-identical to MaterialMap.packs_reference.  s.c = C_m * V.  An id off the mask is not read.
-__global__ __launch_bounds__(256) void k_matmap_build_coeffs(const uint8_t *__restrict__ mask, const uint8_t *__restrict__ ids,
-                                                             Lay L, double A, MapScal s, MapFaceSpec h, MapFaceSpec q,
-                                                             double *__restrict__ c0, double *__restrict__ c1,
-                                                             double *__restrict__ c2, double *__restrict__ q0,
-                                                             double *__restrict__ q1, double *__restrict__ q2)
+// IEEE division, contraction off -> bit-identical to MaterialMap.packs_reference.  sC: C_m * V in LDS.  An id off the mask is not
+// read.  The six values of the cell (i, j, k) at offset p, zeros where it is not exposed: what both kernels below store.
+__device__ __forceinline__ void map_coeffs_cell(const uint8_t *__restrict__ mask, const uint8_t *__restrict__ ids, const Lay &L,
+                                                double A, const double *sC, const MapFaceSpec &h, const MapFaceSpec &q, int i, int j,
+                                                int k, long p, double *__restrict__ c0, double *__restrict__ c1,
+                                                double *__restrict__ c2, double *__restrict__ q0, double *__restrict__ q1,
+                                                double *__restrict__ q2)
 {
 #pragma clang fp contract(off)
-    __shared__ double sG[kMapMaxMat * kMapMaxMat], sC[kMapMaxMat];
-    map_tables_to_lds(s, sG, sC);
-    int i, j, k;
-    long p;
-    if (!cell_of((long)blockIdx.x * blockDim.x + threadIdx.x, L, i, j, k, p)) return;
     const long st[3] = {L.sx, (long)L.nz, 1};
     const int pos[3] = {i, j, k}, nn[3] = {L.nx, L.ny, L.nz};
     const bool m = mask[p] != 0;
@@ -58,6 +55,41 @@ __global__ __launch_bounds__(256) void k_matmap_build_coeffs(const uint8_t *__re
     }
     c0[p] = co[0]; c1[p] = co[1]; c2[p] = co[2];
     q0[p] = qq[0]; q1[p] = qq[1]; q2[p] = qq[2];
+}
+
+__global__ __launch_bounds__(256) void k_matmap_build_coeffs(const uint8_t *__restrict__ mask, const uint8_t *__restrict__ ids,
+                                                             Lay L, double A, MapScal s, MapFaceSpec h, MapFaceSpec q,
+                                                             double *__restrict__ c0, double *__restrict__ c1,
+                                                             double *__restrict__ c2, double *__restrict__ q0,
+                                                             double *__restrict__ q1, double *__restrict__ q2)
+{
+    __shared__ double sG[kMapMaxMat * kMapMaxMat], sC[kMapMaxMat];
+    map_tables_to_lds(s, sG, sC);
+    int i, j, k;
+    long p;
+    if (!cell_of((long)blockIdx.x * blockDim.x + threadIdx.x, L, i, j, k, p)) return;
+    map_coeffs_cell(mask, ids, L, A, sC, h, q, i, j, k, p, c0, c1, c2, q0, q1, q2);
+}
+
+// The same cells' values on the planes [k0, k1) of axis 2 only (the planes a birth or a deposit touches): one thread per cell of
+// the range, nothing outside it is written.  Only the C table goes to LDS.
+__global__ __launch_bounds__(256) void k_mapcoeffs_planes(const uint8_t *__restrict__ mask,
+                                                                    const uint8_t *__restrict__ ids, Lay L, int k0, int k1,
+                                                                    double A, MapScal s, MapFaceSpec h, MapFaceSpec q,
+                                                                    double *__restrict__ c0, double *__restrict__ c1,
+                                                                    double *__restrict__ c2, double *__restrict__ q0,
+                                                                    double *__restrict__ q1, double *__restrict__ q2)
+{
+    __shared__ double sC[kMapMaxMat];
+    {
+        const double *kc = s.c;
+        if (threadIdx.x < kMapMaxMat) sC[threadIdx.x] = kc[threadIdx.x];
+        __syncthreads();
+    }
+    int i, j, k;
+    long p;
+    if (!cell_of_k((long)blockIdx.x * blockDim.x + threadIdx.x, L, k0, k1, i, j, k, p)) return;
+    map_coeffs_cell(mask, ids, L, A, sC, h, q, i, j, k, p, c0, c1, c2, q0, q1, q2);
 }
 
 // Explicit stage: kExplicitCells cells per thread, a block's threads on consecutive cells (the table's way into LDS is paid once
@@ -290,17 +322,43 @@ __global__ __launch_bounds__(256) void k_matmap_sweep_lines(
     }
 }
 
-// nmat and the first nmat x nmat entries of a pair table / nmat entries of a C table
-static int check_tables(const char *who, int nmat, const double *h_G, const double *h_C)
+// adi_matmap_build_coeffs (planes = false: the whole box) and adi_matmap_build_coeffs_planes (the planes [k_begin, k_end) of
+// axis 2, not empty and inside the box); `who` names the entry in the error text
+static int map_build_coeffs(const char *who, const uint8_t *d_mask, const uint8_t *d_ids, int nx, int ny, int nz,
+                            long plane_stride, double dx, int nmat, const double *h_C, const int *h_mode, const double *h_scalar,
+                            const double *const *d_h_field, const int *q_mode, const double *q_scalar,
+                            const double *const *d_q_field, double *const *d_coeff, double *const *d_qflux, bool planes,
+                            int k_begin, int k_end, void *stream)
 {
-    ADI_REQUIRE(nmat >= 1 && nmat <= kMapMaxMat, "%s: %d materials (1 to %d)", who, nmat, kMapMaxMat);
-    for (int m = 0; m < nmat; ++m) {
-        if (h_C != nullptr) ADI_REQUIRE(isfinite(h_C[m]) && h_C[m] > 0.0, "%s: C of material %d must be finite and > 0", who, m);
-        if (h_G != nullptr)
-            for (int k = 0; k < nmat; ++k)
-                ADI_REQUIRE(isfinite(h_G[m * kMapMaxMat + k]) && h_G[m * kMapMaxMat + k] > 0.0,
-                            "%s: pair table entry [%d][%d] must be finite and > 0", who, m, k);
+#pragma clang fp contract(off)
+    ADI_REQUIRE(d_mask && d_ids && h_C && h_mode && h_scalar && q_mode && q_scalar && d_coeff && d_qflux, "%s: null argument", who);
+    ADI_REQUIRE(isfinite(dx) && dx > 0.0, "%s: dx must be finite and > 0", who);
+    if (int rc = check_tables(who, nmat, nullptr, h_C)) return rc;
+    Lay L;
+    if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
+    if (planes) ADI_REQUIRE(k_begin >= 0 && k_end <= nz && k_begin < k_end, "%s: bad plane range [%d, %d)", who, k_begin, k_end);
+    MapFaceSpec h, q;
+    for (int f = 0; f < 6; ++f) {
+        h.mode[f] = h_mode[f]; h.scalar[f] = h_scalar[f]; h.field[f] = d_h_field ? d_h_field[f] : nullptr;
+        q.mode[f] = q_mode[f]; q.scalar[f] = q_scalar[f]; q.field[f] = d_q_field ? d_q_field[f] : nullptr;
+        ADI_REQUIRE(h.mode[f] >= 0 && h.mode[f] <= 2 && q.mode[f] >= 0 && q.mode[f] <= 2, "%s: bad face mode", who);
+        ADI_REQUIRE(h.mode[f] != ADI_FACE_FIELD || h.field[f], "%s: missing h field for face %d", who, f);
+        ADI_REQUIRE(q.mode[f] != ADI_FACE_FIELD || q.field[f], "%s: missing q field for face %d", who, f);
     }
+    for (int a = 0; a < 3; ++a) ADI_REQUIRE(d_coeff[a] && d_qflux[a], "%s: null output", who);
+    MapScal s = {};
+    const double A = dx * dx;
+    const double V = dx * dx * dx;
+    for (int m = 0; m < kMapMaxMat; ++m) s.c[m] = m < nmat ? h_C[m] * V : 1.0;
+    if (planes) {
+        const unsigned blocks = (unsigned)(((long)L.nx * L.ny * (k_end - k_begin) + 255) / 256);
+        hipLaunchKernelGGL(k_mapcoeffs_planes, dim3(blocks), dim3(256), 0, as_stream(stream), d_mask, d_ids, L, k_begin,
+                           k_end, A, s, h, q, d_coeff[0], d_coeff[1], d_coeff[2], d_qflux[0], d_qflux[1], d_qflux[2]);
+    } else {
+        hipLaunchKernelGGL(k_matmap_build_coeffs, dim3(cell_blocks(L)), dim3(256), 0, as_stream(stream), d_mask, d_ids, L, A, s, h,
+                           q, d_coeff[0], d_coeff[1], d_coeff[2], d_qflux[0], d_qflux[1], d_qflux[2]);
+    }
+    ADI_CHECK_LAUNCH();
     return ADI_OK;
 }
 
@@ -315,30 +373,18 @@ int adi_matmap_build_coeffs(const uint8_t *d_mask, const uint8_t *d_ids, int nx,
                             const double *const *d_h_field, const int *q_mode, const double *q_scalar,
                             const double *const *d_q_field, double *const *d_coeff, double *const *d_qflux, void *stream)
 {
-#pragma clang fp contract(off)
-    ADI_REQUIRE(d_mask && d_ids && h_C && h_mode && h_scalar && q_mode && q_scalar && d_coeff && d_qflux,
-                "adi_matmap_build_coeffs: null argument");
-    ADI_REQUIRE(isfinite(dx) && dx > 0.0, "adi_matmap_build_coeffs: dx must be finite and > 0");
-    if (int rc = check_tables("adi_matmap_build_coeffs", nmat, nullptr, h_C)) return rc;
-    Lay L;
-    if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
-    MapFaceSpec h, q;
-    for (int f = 0; f < 6; ++f) {
-        h.mode[f] = h_mode[f]; h.scalar[f] = h_scalar[f]; h.field[f] = d_h_field ? d_h_field[f] : nullptr;
-        q.mode[f] = q_mode[f]; q.scalar[f] = q_scalar[f]; q.field[f] = d_q_field ? d_q_field[f] : nullptr;
-        ADI_REQUIRE(h.mode[f] >= 0 && h.mode[f] <= 2 && q.mode[f] >= 0 && q.mode[f] <= 2, "adi_matmap_build_coeffs: bad face mode");
-        ADI_REQUIRE(h.mode[f] != ADI_FACE_FIELD || h.field[f], "adi_matmap_build_coeffs: missing h field for face %d", f);
-        ADI_REQUIRE(q.mode[f] != ADI_FACE_FIELD || q.field[f], "adi_matmap_build_coeffs: missing q field for face %d", f);
-    }
-    for (int a = 0; a < 3; ++a) ADI_REQUIRE(d_coeff[a] && d_qflux[a], "adi_matmap_build_coeffs: null output");
-    MapScal s = {};
-    const double A = dx * dx;
-    const double V = dx * dx * dx;
-    for (int m = 0; m < kMapMaxMat; ++m) s.c[m] = m < nmat ? h_C[m] * V : 1.0;
-    hipLaunchKernelGGL(k_matmap_build_coeffs, dim3(cell_blocks(L)), dim3(256), 0, as_stream(stream), d_mask, d_ids, L, A, s, h, q,
-                       d_coeff[0], d_coeff[1], d_coeff[2], d_qflux[0], d_qflux[1], d_qflux[2]);
-    ADI_CHECK_LAUNCH();
-    return ADI_OK;
+    return map_build_coeffs("adi_matmap_build_coeffs", d_mask, d_ids, nx, ny, nz, plane_stride, dx, nmat, h_C, h_mode, h_scalar,
+                            d_h_field, q_mode, q_scalar, d_q_field, d_coeff, d_qflux, false, 0, nz, stream);
+}
+
+int adi_matmap_build_coeffs_planes(const uint8_t *d_mask, const uint8_t *d_ids, int nx, int ny, int nz, long plane_stride,
+                                   double dx, int nmat, const double *h_C, const int *h_mode, const double *h_scalar,
+                                   const double *const *d_h_field, const int *q_mode, const double *q_scalar,
+                                   const double *const *d_q_field, double *const *d_coeff, double *const *d_qflux, int k_begin,
+                                   int k_end, void *stream)
+{
+    return map_build_coeffs("adi_matmap_build_coeffs_planes", d_mask, d_ids, nx, ny, nz, plane_stride, dx, nmat, h_C, h_mode,
+                            h_scalar, d_h_field, q_mode, q_scalar, d_q_field, d_coeff, d_qflux, true, k_begin, k_end, stream);
 }
 
 int adi_matmap_explicit(const double *d_T, const double *d_S, const uint8_t *d_flags, const uint8_t *d_ids, int nx, int ny,

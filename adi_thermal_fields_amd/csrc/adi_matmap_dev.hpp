@@ -1,5 +1,5 @@
 // adi_matmap_dev.hpp -- device-side pieces of the several-materials step (adi_matmap.hip): the scalars a
-// launch carries by value and the row of a sweep whose couplings differ from face to face.
+// launch carries by value, the row of a sweep whose couplings differ from face to face, and the host's check of the tables.
 #pragma once
 #include "adi_cart_host.hpp"
 #include "adi_cell_dev.hpp"
@@ -71,6 +71,20 @@ __device__ __forceinline__ void map_row(bool m, bool lo, bool hi, bool dir, doub
     if (HAS_Q) rhs = rhs + dt * qv;
     rhs = rhs + dc * Tinf;
     d = fr ? rhs : ((HAS_DIR && m) ? dv : in);
+}
+
+// nmat and the first nmat x nmat entries of a pair table / nmat entries of a C table
+inline int check_tables(const char *who, int nmat, const double *h_G, const double *h_C)
+{
+    ADI_REQUIRE(nmat >= 1 && nmat <= kMapMaxMat, "%s: %d materials (1 to %d)", who, nmat, kMapMaxMat);
+    for (int m = 0; m < nmat; ++m) {
+        if (h_C != nullptr) ADI_REQUIRE(isfinite(h_C[m]) && h_C[m] > 0.0, "%s: C of material %d must be finite and > 0", who, m);
+        if (h_G != nullptr)
+            for (int k = 0; k < nmat; ++k)
+                ADI_REQUIRE(isfinite(h_G[m * kMapMaxMat + k]) && h_G[m * kMapMaxMat + k] > 0.0,
+                            "%s: pair table entry [%d][%d] must be finite and > 0", who, m, k);
+    }
+    return ADI_OK;
 }
 
 }  // namespace adi

@@ -9,6 +9,9 @@
 //   k_source_add_r0     the source added to R0 on the planes of a slab the support can meet (the slab forms whose axis-0 lines
 //                       cross ranks without a zero-boundary local solve: dist_slab's 'exact', 'slab', 'window')
 //   k_source_lines0_slab, k_source_lines0_long_slab   the lines kernels for one slab of a grid cut along axis 0
+//   k_mapsource_add_r0   the source added to R0 on a grid of several materials, each cell divided by the C of its own id
+//                       (the step of a MaterialMap takes the source there: its couplings differ from cell to cell, so the
+//                       sweep-0 correction of the lines kernels does not apply)
 // No existing kernel changes: the correction runs after whichever sweep-0 form (fused or not) the step used.  The slab
 // kernels take a plane origin i_org: local plane i of a slab that starts at global plane i_org has its centre at
 // (i_org + i + 1/2) dx; the single-domain kernels are the same bodies without it (their arguments and arithmetic as before).
@@ -17,6 +20,7 @@
 #include "adi_cart_host.hpp"
 #include "adi_cell_dev.hpp"
 #include "adi_goldak_dev.hpp"
+#include "adi_matmap_dev.hpp"
 
 namespace adi {
 
@@ -362,10 +366,27 @@ struct AddArgs {
     int n0, nj, nk;             // planes of the launch box along axis 0 (at most i_end - i_begin), lines along axes 1 / 2
 };
 
+// The column (j, k) of the launch box that thread kb of line jb owns, and the first local plane i_lo of its walk along axis 0.
+// The box is placed from the block's mid-step centre c as lines0_line places it; along axis 0 it starts at the later of its
+// first plane and i_begin.  false: a column outside the box or off the grid.
+__device__ inline bool add_r0_column(const SrcBlock &B, const Lay &L, const AddArgs &A, int jb, int kb, double (&c)[3], int &j,
+                                     int &k, int &i_lo)
+{
+#pragma clang fp contract(off)
+    const adi_heat_source &s = B.s;
+    if (kb >= A.nk || jb >= A.nj) return false;
+    src_centre(s, src_tmid(B), c);
+    j = src_box_first(s, c, 1, A.dx) + jb;
+    k = src_box_first(s, c, 2, A.dx) + kb;
+    if (!(j >= 0 && j < L.ny && k >= 0 && k < L.nz)) return false;
+    const int g0 = src_box_first(s, c, 0, A.dx) - A.i_org;
+    i_lo = g0 > A.i_begin ? g0 : A.i_begin;
+    return true;
+}
+
 // R0 += dt*q(t_n + dt/2)/(rho cp) on the in-mask, non-Dirichlet cells of local planes [i_begin, i_end) inside the launch box,
-// one thread per cell of the box (lanes adjacent along k).  The box is placed from the block's mid-step centre as
-// lines0_line places it; along axis 0 it starts at the later of its first plane and i_begin.  Cells of the box outside the
-// support get q = 0 (goldak_q's cut) and are not written.
+// one thread per cell of the box (lanes adjacent along k).  Cells of the box outside the support get q = 0 (goldak_q's cut)
+// and are not written.
 __global__ __launch_bounds__(64) void k_source_add_r0(const SrcBlock *__restrict__ blk, double *__restrict__ R0,
                                                       const uint8_t *__restrict__ flags, const uint8_t *__restrict__ dirm,
                                                       Lay L, AddArgs A)
@@ -373,14 +394,9 @@ __global__ __launch_bounds__(64) void k_source_add_r0(const SrcBlock *__restrict
 #pragma clang fp contract(off)
     const SrcBlock &B = *blk;            // (read in place, as k_source_lines0 does)
     const adi_heat_source &s = B.s;
-    const int kb = (int)(blockIdx.x * blockDim.x + threadIdx.x), jb = (int)blockIdx.y;
-    if (kb >= A.nk || jb >= A.nj) return;
     double c[3];
-    src_centre(s, src_tmid(B), c);
-    const int j = src_box_first(s, c, 1, A.dx) + jb, k = src_box_first(s, c, 2, A.dx) + kb;
-    if (!(j >= 0 && j < L.ny && k >= 0 && k < L.nz)) return;
-    const int g0 = src_box_first(s, c, 0, A.dx) - A.i_org;
-    const int i_lo = g0 > A.i_begin ? g0 : A.i_begin;
+    int j, k, i_lo;
+    if (!add_r0_column(B, L, A, (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x), c, j, k, i_lo)) return;
     const double yj = (j + 0.5) * A.dx, zk = (k + 0.5) * A.dx;
     const long base = (long)j * L.nz + k;
     for (int ib = (int)blockIdx.z; ib < A.n0; ib += (int)gridDim.z) {
@@ -390,6 +406,41 @@ __global__ __launch_bounds__(64) void k_source_add_r0(const SrcBlock *__restrict
         if (!(flags[p] & 1u) || (dirm != nullptr && dirm[p])) continue;
         const double q = goldak_q(s, c, ((A.i_org + i) + 0.5) * A.dx, yj, zk);
         if (q != 0.0) R0[p] = R0[p] + A.scale * q;
+    }
+}
+
+// The same walk on a grid of several materials (include/adi_hip.h, "Several materials"): R0 = R0 + (dt * q) / C[id] on every
+// in-mask cell of the box the support reaches -- the operations of k_matmap_explicit's source-field branch, in its order, with
+// q evaluated here instead of read from a field.  A.scale = dt; C travels by value and goes through LDS (a lane picks the
+// entry of its cell's id).  17 bytes per in-mask cell of the support: flags, id, R0 read and written.
+struct MapCTab {
+    double c[kMapMaxMat];
+};
+__global__ __launch_bounds__(64) void k_mapsource_add_r0(const SrcBlock *__restrict__ blk, double *__restrict__ R0,
+                                                             const uint8_t *__restrict__ flags, const uint8_t *__restrict__ ids,
+                                                             Lay L, AddArgs A, MapCTab C)
+{
+#pragma clang fp contract(off)
+    __shared__ double sC[kMapMaxMat];
+    {
+        const double *kc = C.c;
+        if (threadIdx.x < kMapMaxMat) sC[threadIdx.x] = kc[threadIdx.x];
+        __syncthreads();
+    }
+    const SrcBlock &B = *blk;            // (read in place, as k_source_lines0 does)
+    const adi_heat_source &s = B.s;
+    double c[3];
+    int j, k, i_lo;
+    if (!add_r0_column(B, L, A, (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x), c, j, k, i_lo)) return;
+    const double yj = (j + 0.5) * A.dx, zk = (k + 0.5) * A.dx;
+    const long base = (long)j * L.nz + k;
+    for (int ib = (int)blockIdx.z; ib < A.n0; ib += (int)gridDim.z) {
+        const int i = i_lo + ib;
+        if (i >= A.i_end) return;
+        const long p = (long)i * L.sx + base;
+        if (!(flags[p] & 1u)) continue;
+        const double q = goldak_q(s, c, (i + 0.5) * A.dx, yj, zk);
+        if (q != 0.0) R0[p] = R0[p] + (A.scale * q) / sC[ids[p] & (kMapMaxMat - 1)];
     }
 }
 
@@ -419,6 +470,22 @@ static void lines0_box(const adi_heat_source &s, int ny, int nz, double dx, int 
     nk = src_box_lines(s, 2, dx);
     if (nj > ny + 4) nj = ny + 4;
     if (nk > nz + 4) nk = nz + 4;
+}
+
+// the arguments and the launch grid of the add-R0 kernels for the local planes [i_begin, i_end): the box of the support, at most
+// the planes given along axis 0 and lines0_box along axes 1 / 2
+static dim3 add_r0_box(const adi_heat_source &s, int ny, int nz, double dx, double scale, int i_org, int i_begin, int i_end,
+                       AddArgs &A)
+{
+    A.dx = dx; A.scale = scale;
+    A.i_org = i_org; A.i_begin = i_begin; A.i_end = i_end;
+    double lo, hi;
+    src_extent(s, 0, lo, hi);
+    const double n0 = floor((lo + hi) / dx) + 4.0;          // src_box_lines along axis 0, in double: no int overflow
+    A.n0 = n0 < (double)(i_end - i_begin) ? (int)n0 : i_end - i_begin;
+    lines0_box(s, ny, nz, dx, A.nj, A.nk);
+    const unsigned gz = (unsigned)(A.n0 < 65535 ? A.n0 : 65535);
+    return dim3((unsigned)((A.nk + 63) / 64), (unsigned)A.nj, gz);
 }
 
 template <int M, int SEG>
@@ -588,16 +655,29 @@ int adi_source_add_r0(const void *d_block, const adi_heat_source *h_src, double 
                 i_begin, i_end, nx);
     if (i_begin == i_end) return ADI_OK;
     AddArgs A;
-    A.dx = dx; A.scale = dt / (rho * cp);
-    A.i_org = i_org; A.i_begin = i_begin; A.i_end = i_end;
-    double lo, hi;
-    src_extent(*h_src, 0, lo, hi);
-    const double n0 = floor((lo + hi) / dx) + 4.0;          // src_box_lines along axis 0, in double: no int overflow
-    A.n0 = n0 < (double)(i_end - i_begin) ? (int)n0 : i_end - i_begin;
-    lines0_box(*h_src, ny, nz, dx, A.nj, A.nk);
-    const unsigned gz = (unsigned)(A.n0 < 65535 ? A.n0 : 65535);
-    hipLaunchKernelGGL(k_source_add_r0, dim3((unsigned)((A.nk + 63) / 64), (unsigned)A.nj, gz), dim3(64), 0,
-                       as_stream(stream), (const SrcBlock *)d_block, d_R0, d_flags, d_dir_mask, L, A);
+    const dim3 grid = add_r0_box(*h_src, ny, nz, dx, dt / (rho * cp), i_org, i_begin, i_end, A);
+    hipLaunchKernelGGL(k_source_add_r0, grid, dim3(64), 0, as_stream(stream), (const SrcBlock *)d_block, d_R0, d_flags,
+                       d_dir_mask, L, A);
+    ADI_CHECK_LAUNCH();
+    return ADI_OK;
+}
+
+int adi_matmap_source_add_r0(const void *d_block, const adi_heat_source *h_src, double *d_R0, const uint8_t *d_flags,
+                             const uint8_t *d_ids, int nx, int ny, int nz, long plane_stride, double dx, double dt, int nmat,
+                             const double *h_C, void *stream)
+{
+    if (int rc = check_source(h_src, "adi_matmap_source_add_r0")) return rc;
+    ADI_REQUIRE(d_block && d_R0 && d_flags && d_ids && h_C, "adi_matmap_source_add_r0: null argument");
+    ADI_REQUIRE(std::isfinite(dx) && std::isfinite(dt) && dx > 0.0 && dt > 0.0, "adi_matmap_source_add_r0: bad dx / dt");
+    if (int rc = check_tables("adi_matmap_source_add_r0", nmat, nullptr, h_C)) return rc;
+    Lay L;
+    if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
+    AddArgs A;
+    const dim3 grid = add_r0_box(*h_src, ny, nz, dx, dt, 0, 0, nx, A);
+    MapCTab C;
+    for (int m = 0; m < kMapMaxMat; ++m) C.c[m] = m < nmat ? h_C[m] : 1.0;
+    hipLaunchKernelGGL(k_mapsource_add_r0, grid, dim3(64), 0, as_stream(stream), (const SrcBlock *)d_block, d_R0, d_flags,
+                       d_ids, L, A, C);
     ADI_CHECK_LAUNCH();
     return ADI_OK;
 }

@@ -9,7 +9,7 @@ from . import _lib
 from ._lib import lib, check, ptr_array, FACES
 from .fields import DeviceField, Grid3D, _device, _native_f64, _p, _stream
 from .heat_source import ScanPath, ScanPathSource
-from .packs import AxisCoeffPack, _face_constants
+from .packs import AxisCoeffPack, MaterialMap, _face_constants
 
 
 def apply_surface_impulse_Q(T, grid, mat, Q, face='z-'):
@@ -169,9 +169,13 @@ class PathDeposit:
     planes whose exposure can have changed; the packs are the caller's (BirthPacks.update / LossPacks.rebuild on the range it
     returns).  Nothing is read back and nothing is synchronised.
     `grid` may also be any object with nx, ny, nz, dx and mask (no device): then `born_host` and `index_box` work, which need
-    no GPU, and `deposit` does not."""
+    no GPU, and `deposit` does not.
+    material_map, material_id (both or neither): the grid carries several materials (a MaterialMap of this grid) and what this
+    path lays is material `material_id` of it: `deposit` also writes that id into the map's device id field on exactly the
+    newborn cells (adi_bead_deposit_ids; ids_after = where(reference(...), material_id, ids_before)).  The caller then calls
+    `material_map.update(*rng)` on the range `deposit` returns.  One PathDeposit lays one material; use two for two wires."""
 
-    def __init__(self, grid, path, bead, Ts, within=None):
+    def __init__(self, grid, path, bead, Ts, within=None, material_map=None, material_id=None):
         if isinstance(path, ScanPath):
             path = path.on_device()
         if not isinstance(path, ScanPathSource):
@@ -184,6 +188,20 @@ class PathDeposit:
             raise ValueError("PathDeposit: Ts must be a real number")
         if not np.isfinite(self.Ts):
             raise ValueError("PathDeposit: non-finite Ts")
+        if (material_map is None) != (material_id is None):
+            raise ValueError("PathDeposit: material_map and material_id go together (the map whose id field is stamped, and the "
+                             "id of what this path lays)")
+        if material_map is not None:
+            if not isinstance(material_map, MaterialMap):
+                raise TypeError("PathDeposit: material_map must be a MaterialMap, got %s" % type(material_map).__name__)
+            if material_map.grid is not grid:
+                raise ValueError("PathDeposit: the MaterialMap belongs to another grid")
+            if isinstance(material_id, bool) or not isinstance(material_id, (int, np.integer)) \
+                    or not 0 <= material_id < len(material_map.materials):
+                raise ValueError("PathDeposit: material_id must be an integer from 0 to %d (the MaterialMap has %d materials), "
+                                 "got %r" % (len(material_map.materials) - 1, len(material_map.materials), material_id))
+            material_id = int(material_id)
+        self.material_map, self.material_id = material_map, material_id
         self.grid, self.path, self.bead = grid, path, bead
         self._c_shape = bead.as_c(path.depth_axis)
         self._n = (int(grid.nx), int(grid.ny), int(grid.nz))
@@ -289,7 +307,7 @@ class PathDeposit:
         the newborn cells, the grid's device mask 1, in place; then grid.set_mask_device rebuilds flags and bricks on the planes
         [k_lo, k_hi) of axis 2 whose exposure can have changed -- the index box's planes and one either side when the path's
         depth axis is 2, every plane otherwise.  -> (k_lo, k_hi) for the caller's packs; None, and nothing launched, when the step
-        bears nothing.  `count`: optional int64 device tensor (1 element) that receives the number of newborn cells (0 when the
+        bears nothing.  With `material_map=` the newborn cells also get `material_id` in the map's device id field.  `count`: optional int64 device tensor (1 element) that receives the number of newborn cells (0 when the
         step bears nothing)."""
         if not self._on_device:
             raise TypeError("PathDeposit.deposit: the grid is not a Grid3D on the device")
@@ -299,9 +317,15 @@ class PathDeposit:
         if box is None and count is None:
             return None
         d_active = g.d_mask
-        check(lib.adi_bead_deposit(*self._path_args()[:2], _p(self.path.d_table), self.path.K, self.path.t_end, _p(t_),
-                                   _p(d_active), _p(self.d_within), *self._n, *g.layout.pd, g.dx, float(t), float(dt), self.Ts,
-                                   _p(self._count if count is None else count), _stream()))
+        tail = (*self._n, *g.layout.pd, g.dx, float(t), float(dt), self.Ts, _p(self._count if count is None else count), _stream())
+        head = (*self._path_args()[:2], _p(self.path.d_table), self.path.K, self.path.t_end, _p(t_), _p(d_active),
+                _p(self.d_within))
+        mm = self.material_map
+        if mm is None:
+            check(lib.adi_bead_deposit(*head, *tail))
+        else:
+            check(lib.adi_bead_deposit_ids(*head, _p(mm._d_ids), self.material_id, *tail))
+            mm._ids_stamped = True                         # the map's host copy of the ids is stale: mm.ids downloads
         if box is None:
             return None
         k_lo, k_hi = (max(0, box[2][0] - 1), min(g.nz, box[2][1] + 1)) if self.path.depth_axis == 2 else (0, g.nz)

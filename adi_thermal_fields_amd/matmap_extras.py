@@ -1,6 +1,7 @@
 """Latent heat and temperature-dependent surface loss on a grid of several materials: `MapPhaseField`, the
 liquid fraction of a MaterialMap's grid under one PhaseChange law per material, and `MapLossPacks`, the MaterialMap's own packs
-rewritten in place by one SurfaceLoss per material."""
+rewritten in place by one SurfaceLoss per material; and `MapSource`, a moving GoldakSource inside the step of a MaterialMap
+(DESIGN.md section 6l3)."""
 import ctypes
 
 import numpy as np
@@ -8,8 +9,9 @@ import torch
 
 from . import _lib
 from ._lib import lib, check, ptr_array, FACES
-from .fields import DeviceField, _SeededForMask, _device, _native_f64, _p, _stream
-from .packs import MaterialMap, _MapLoss, _MapPhase, _triples
+from .fields import DeviceField, _SeededForMask, _as_state, _device, _native_f64, _p, _stream, _wrap
+from .packs import MaterialMap, _MapLoss, _MapPhase, _MapSource, _triples
+from .heat_source import GoldakSource, _source_block
 from .surface_loss import SurfaceLoss
 from .phase import PhaseChange
 
@@ -287,3 +289,50 @@ class MapLossPacks(_MapLoss):
                 hf = np.where(idm == m, w.h_of(T, face, Tinf), hf)
             h[face] = hf
         return tuple(p.coeff for p in MaterialMap.packs_reference(mask, ids, materials, dx, robin_h=h))
+
+
+class MapSource(_MapSource):
+    """A moving GoldakSource for the step of one MaterialMap: pass it as `S=` of adi_step_numba_coeff or `source=` of
+    StagedStepper next to `material_map=mm`.  The one-material step corrects the output of sweep 0 by superposition, which
+    assumes one coupling along a line; here the source is added to the explicit stage's output instead, one thread per cell of the
+    support (adi_matmap_source_add_r0):
+        R0 = R0 + (dt * q(t_n + dt/2)) / C[id]     on the in-mask cells the support reaches,
+    the operations of the field form S=src.sample_device(grid, t + dt/2), in its order, without the field.  The time comes from
+    the device block of adi_source_set / adi_source_tick, so a captured step replays it; power, origin, velocity, eta and f_f of
+    `src` may change between the runs of a StagedStepper without a new graph, the extent of its support recaptures.
+    It is not a GoldakSource: the bare object next to material_map= is still refused."""
+
+    def __init__(self, mm, src):
+        if not isinstance(mm, MaterialMap):
+            raise TypeError("MapSource: mm must be a MaterialMap")
+        if not isinstance(src, GoldakSource):
+            raise TypeError("MapSource: src must be a GoldakSource, got %s" % type(src).__name__)
+        src.validate()
+        self.mm, self.grid, self.src = mm, mm.grid, src
+
+    def shape_key(self):
+        """what the launch box depends on (a change recaptures a stepper's graph): the wrapped source's, marked as a map's"""
+        return ('map',) + self.src.shape_key()
+
+    def set_block(self, blk, t0, dt, n=0):
+        self.src.set_block(blk, t0, dt, n)
+
+    def add_r0(self, R0, params, blk):
+        """R0 (a device tensor in the grid's layout, the explicit stage's output) gains the source of the block `blk` at its
+        mid-step time, in place: one launch"""
+        mm, g = self.mm, self.grid
+        _, C = mm._tables(params.dt)
+        check(lib.adi_matmap_source_add_r0(_p(blk), ctypes.byref(self.src.as_c()), _p(R0), _p(g.d_flags), _p(mm._d_ids),
+                                           *g.layout.pd, g.dx, params.dt, len(mm.materials), C, _stream()))
+
+    def explicit_rhs(self, T, params, t=0.0):
+        """R0 of the step that starts at time t (stage entry point): mm.explicit_rhs(T, params) plus this source at t + dt/2"""
+        mm, g = self.mm, self.grid
+        mm._check_fresh()
+        x, kind = _as_state(T, g)
+        out = g.layout.empty()
+        mm._explicit_into(x, None, out, params)
+        blk = _source_block(self)
+        self.set_block(blk, t, params.dt)
+        self.add_r0(out, params, blk)
+        return _wrap(out, kind)

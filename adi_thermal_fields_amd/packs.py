@@ -266,6 +266,11 @@ class _MapPhase:
     `_check_fresh()`, `snapshot()`, `restore(s)` and `graph_key()`."""
 
 
+class _MapSource:
+    """What step.py names of matmap_extras.MapSource: a moving GoldakSource `.src` for the step of a MaterialMap `.mm`, with
+    `set_block(blk, t0, dt)`, `shape_key()` and `add_r0(R0, params, blk)`."""
+
+
 class MaterialMap:
     """A grid of several materials: 1 to 8 (rho, cp, k) and a uint8 id per cell.  The step under it couples a cell of material
     m to an in-mask neighbour of material n with the pair-table entry G[m][n] = (kf(m, n) dt) / (C_m dx^2), kf the harmonic
@@ -275,7 +280,10 @@ class MaterialMap:
     `.mat` (= materials[0]) and `.packs` are what the step's `mat` and `packs` arguments must be.  The packs are built on the
     device from the id field (adi_matmap_build_coeffs) and read sparsely, at exposed cells; `face_consts` stays None.  An id
     off the mask is never read: it has to be valid when `rebuild()` finds the cell in the mask, so one id field serves a whole
-    deposition run.  After `grid.mask` changed call `rebuild()`: the pack objects stay, their arrays are rewritten.
+    deposition run.  After `grid.mask` changed call `rebuild()`: the pack objects stay, their arrays are rewritten.  After a
+    birth or a deposit `update(k_begin, k_end)` rewrites the planes it touched only and reads nothing back; it needs every id of
+    the field, in or off the mask, to name a material (`ids_all_valid`).  A PathDeposit made with `material_map=` writes the id of
+    its newborn cells into the device field; `ids` then downloads it.
     Lines of any length are served: up to 1024 rows in registers (segment kernels on all three axes), longer ones by one
     thread per line.  `packs_reference` and `step_reference` are the definition in NumPy fp64."""
     MAX_MATERIALS = _lib.MATMAP_MAX
@@ -296,6 +304,8 @@ class MaterialMap:
         self._tables_for = None
         self.packs = None
         self._d_ids = grid.layout.to_layout(torch.from_numpy(self._ids), torch.uint8)
+        self._ids_stamped = False       # a PathDeposit wrote ids on the device since the host copy was made
+        self._specs = None              # the face specs with their device copies of per-voxel fields, made by the first build
         self._work = None
         self.rebuild()
 
@@ -310,6 +320,7 @@ class MaterialMap:
             raise ValueError("MaterialMap: ids have shape %s, the grid %s" % (tuple(ids.shape), g.shape))
         ids = np.array(ids, dtype=np.uint8, order='C')
         self._check_in_mask(ids)
+        self.ids_all_valid = bool(ids.size == 0 or int(ids.max()) < len(self.materials))   # off the mask too: update() needs it
         return ids
 
     def _check_in_mask(self, ids):
@@ -318,22 +329,67 @@ class MaterialMap:
             raise ValueError("MaterialMap: an in-mask cell has id %d, there are %d materials"
                              % (int(ids[mask].max()), len(self.materials)))
 
-    ids = property(lambda self: self._ids.copy())
+    def _host_ids(self):
+        """the host copy of the id field, downloaded first when a PathDeposit has stamped the device field since"""
+        if self._ids_stamped:
+            self._ids = np.array(self.grid.layout.to_host(self._d_ids), dtype=np.uint8, order='C')
+            self._ids_stamped = False
+        return self._ids
+
+    ids = property(lambda self: self._host_ids().copy())
 
     def set_ids(self, ids):
-        """replace the id field, then rebuild the packs"""
+        """replace the id field, on the host and on the device, then rebuild the packs"""
         self._ids = self._checked_ids(ids)
+        self._ids_stamped = False
         self._d_ids = self.grid.layout.to_layout(torch.from_numpy(self._ids), torch.uint8)
         self._ids_version += 1
         self.rebuild()
 
+    def _face_args(self):
+        """the face specs of the constructor as the coefficient builds take them; the device copies of per-voxel robin_h / neumann
+        fields are made once, by the first build, and live as long as the map (update() uploads nothing)"""
+        if self._specs is None:
+            keep = []
+            h_specs, q_specs = _face_specs(self.grid.layout, self._bc['robin_h'], self._bc['neumann'], keep)
+            self._specs = (h_specs, q_specs, keep)
+        return self._specs[0], self._specs[1]
+
+    def _mark_fresh(self):
+        g = self.grid
+        for a, p in enumerate(self.packs):
+            p.mask_version = g.mask_version
+            p.sparse_ok = True
+            p.face_consts = None                          # C differs from cell to cell: no per-face constants
+            p._fractions = (g, a, g.mask_version)
+
+    def update(self, k_begin, k_end):
+        """rebuild the planes [k_begin, k_end) of axis 2 (clipped to the box) from the grid's device mask and the device id
+        field as they are now (adi_matmap_build_coeffs_planes) and mark the packs fresh for grid.mask_version -> packs.  One
+        launch; nothing is uploaded, downloaded or synchronised -- so no id can be checked against the mask here, and every id
+        of the field must name a material (ValueError otherwise: use rebuild())."""
+        if not self.ids_all_valid:
+            raise ValueError("MaterialMap.update: the id field holds an id that names no material (off the mask, where rebuild() "
+                             "never reads it); update() reads no mask back, so every id must be below %d -- use rebuild(), or "
+                             "set_ids() with a field whose ids are all valid" % len(self.materials))
+        g, L = self.grid, self.grid.layout
+        k0, k1 = max(0, int(k_begin)), min(L.pz, int(k_end))
+        if k1 > k0:
+            h_specs, q_specs = self._face_args()
+            C = (ctypes.c_double * len(self.materials))(*[m.rho * m.cp for m in self.materials])
+            check(lib.adi_matmap_build_coeffs_planes(_p(g.d_mask), _p(self._d_ids), *L.pd, g.dx, len(self.materials), C,
+                                                     *_face_spec_args(h_specs), *_face_spec_args(q_specs),
+                                                     ptr_array([p.d_coeff.data_ptr() for p in self.packs]),
+                                                     ptr_array([p.d_qflux.data_ptr() for p in self.packs]), k0, k1, _stream()))
+        self._mark_fresh()
+        return self.packs
+
     def rebuild(self):
         """(re)build the packs for grid.mask as it is now, with the boundary specs of the constructor"""
         g, L, bc = self.grid, self.grid.layout, self._bc
-        self._check_in_mask(self._ids)
+        self._check_in_mask(self._host_ids())
         d_mask = g.sync_mask()
-        keep = []
-        h_specs, q_specs = _face_specs(L, bc['robin_h'], bc['neumann'], keep)
+        h_specs, q_specs = self._face_args()
         first = self.packs is None
         coeff = [L.empty() for _ in range(3)] if first else [p.d_coeff for p in self.packs]
         qflux = [L.empty() for _ in range(3)] if first else [p.d_qflux for p in self.packs]
@@ -353,12 +409,8 @@ class MaterialMap:
                 check(lib.adi_matmap_workspace_bytes(ax, *L.pd, ctypes.byref(b)))
                 wb = max(wb, b.value)
             self._work = torch.empty(wb, dtype=torch.uint8, device=coeff[0].device) if wb else None
-        for a, p in enumerate(self.packs):
-            p.mask_version = g.mask_version
-            p.sparse_ok = True
-            p.face_consts = None                          # C differs from cell to cell: no per-face constants
-            p._fractions = (g, a, g.mask_version)
-        torch.cuda.current_stream().synchronize()          # the per-voxel spec copies in `keep` may go now
+        self._mark_fresh()
+        torch.cuda.current_stream().synchronize()          # (as ever: the build is done when rebuild returns)
 
     def graph_key(self):
         """what a captured launch holds of this map besides dt and theta: the id field by pointer, the table by value"""

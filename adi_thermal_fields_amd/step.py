@@ -9,7 +9,7 @@ from . import _lib
 from ._lib import lib, check
 from ._ledger import PromiseLedger
 from .fields import DeviceField, _as_state, _wrap, _p, _stream
-from .packs import _fc_arg, MaterialMap, _MapLoss, _MapPhase
+from .packs import _fc_arg, MaterialMap, _MapLoss, _MapPhase, _MapSource
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .surface_loss import LossPacks
 from .phase import PhaseField, NonlinearPacks
@@ -170,7 +170,10 @@ class StepExtras:
           material_map: several materials, the step's four launches are the MaterialMap's; its pair table travels by value in them
             (so dt and theta, in run()'s key already, cover it) and its id field by pointer.  With it surface_loss is a
             MapLossPacks (the laws in a device table by pointer, the ambient by value) and phase a MapPhaseField (laws by value,
-            f, the summary and the bricks' id sets by pointer): each answers graph_key() for itself.
+            f, the summary and the bricks' id sets by pointer): each answers graph_key() for itself.  With it `source` is a
+            MapSource: the source added to the explicit stage's output (adi_matmap_source_add_r0), its time read from the same
+            device block by pointer and ticked in the capture; the extent of its support travels by value (shape_key) and the
+            C table by value in the launch, everything else of the source through the block, as for a GoldakSource.
           monitor: the record of the step's OUTPUT buffer and the tick of its block, the last launches of all; probes, regions
             and weights travel by value and its buffers by pointer."""
         key = (None if self.source is None else self.source.shape_key(),) + tuple(
@@ -208,9 +211,11 @@ def _check_extras(grid, mat, params, packs, extras):
         same_grid('material_map', mm, 'MaterialMap')
         own_packs('material_map', mm, "MaterialMap's")
         own_material('material_map', mm, "MaterialMap's")
-        if source is not None:
+        if source is not None and not isinstance(source, _MapSource):
             raise ValueError("material_map: a GoldakSource object cannot be combined with it (its sweep-0 correction assumes "
                              "uniform coupling); pass the source as a field, S=path.sample_step(grid, t, dt)")
+        if source is not None and source.mm is not mm:
+            raise ValueError("source: the MapSource belongs to another MaterialMap")
         if ((surface_loss is not None and not isinstance(surface_loss, _MapLoss))
                 or (phase is not None and not isinstance(phase, _MapPhase)) or material is not None):
             raise ValueError("material_map: surface_loss= / phase= / material= cannot be combined with it; each assumes one cp")
@@ -233,7 +238,10 @@ def _check_extras(grid, mat, params, packs, extras):
         if params.theta < material.law.min_theta():
             raise ValueError("material: theta = %r is below the law's stability limit cp_ref / (2 min c_eff) = %r"
                              % (params.theta, material.law.min_theta()))
-    if source is not None and not isinstance(source, GoldakSource):
+    if isinstance(source, _MapSource) and mm is None:
+        raise ValueError("source: a MapSource needs material_map= (its MaterialMap's step); without one pass the GoldakSource "
+                         "itself")
+    if source is not None and not isinstance(source, (GoldakSource, _MapSource)):
         raise TypeError("source must be a GoldakSource (pass a source field, e.g. ScanPath.sample_step, to "
                         "adi_step_numba_coeff)")
     if surface_loss is not None and mm is None:
@@ -282,7 +290,10 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, extras, d_S=N
     two launches, after sweep 0 with the source's correction, after sweep 1 and after sweep 2.
     extras.material_map: a MaterialMap: the explicit stage (with d_S, if any) and the three sweeps are ITS four launches
     (adi_matmap_explicit, adi_matmap_sweep), never fused; with it `surface_loss` is a MapLossPacks, whose update from t_in comes
-    first, and `phase` a MapPhaseField, whose correction of `out` follows sweep 2; the recorders follow as ever.
+    first, and `phase` a MapPhaseField, whose correction of `out` follows sweep 2; the recorders follow as ever.  With it
+    `extras.source` is a MapSource and the order is: the map's explicit stage, the source added to its output
+    (adi_matmap_source_add_r0, the block set just ahead of it when t_set is given), adi_source_tick when captured, sweep 0 -- no
+    correction after sweep 0.
     extras.monitor: a FieldMonitor: its record of `out` and its tick are the last launches of all, after solidification's."""
     x, mm = extras, extras.material_map
     (ta, tb), _, _ = grid.scratch(2)
@@ -317,9 +328,15 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, extras, d_S=N
         _explicit_sweep0_into(u, tb, grid, mat, params, packs[0], Tinf)
     else:
         explicit(ta)
+        if mm is not None and x.source is not None:
+            if t_set is not None:
+                x.source.set_block(_source_block(owner), t_set, params.dt)
+            x.source.add_r0(ta, params, _source_block(owner))
+            if captured:
+                check(lib.adi_source_tick(_p(_source_block(owner)), _stream()))
         mark()
         sweep(0, ta, tb)
-    if x.source is not None:
+    if x.source is not None and mm is None:
         if t_set is not None:
             x.source.set_block(_source_block(owner), t_set, params.dt)
         _source_lines0_into(tb, grid, mat, params, packs[0], x.source, owner)
@@ -373,7 +390,8 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     come from the map's pair table.  Combines with S= as a field and with history= and solidification=; with
     surface_loss= when that is a MapLossPacks of the map and with phase= when that is a MapPhaseField of the map (one law per
     material: adi_matmap_loss_update first, adi_matmap_phase_apply after sweep 2); not with a GoldakSource object,
-    a LossPacks, a PhaseField or material=.  None: the launches of before.
+    a LossPacks, a PhaseField or material=.  A moving Goldak source goes in wrapped, S=MapSource(mm, src): it is added to the
+    explicit stage's output with each cell's own C (adi_matmap_source_add_r0).  None: the launches of before.
     monitor: a FieldMonitor of the grid (with the step's material_map, if any): the result's value at its probes and the count,
     extrema and sums of its regions become one row of its device log, and its clock moves on by dt (adi_monitor_record and
     adi_history_tick on its block, the last launches of all).  Combines with every other argument.  None: no such launch.
@@ -381,7 +399,7 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     if isinstance(S, (ScanPath, ScanPathSource)):
         raise TypeError("adi_step_hip_coeff: a scan path enters the step as its field: S=path.sample_step(grid, t, dt) from the "
                         "host, or S=path.on_device().sample_step_device(grid, t, dt) evaluated on the device")
-    source = S if isinstance(S, GoldakSource) else None
+    source = S if isinstance(S, (GoldakSource, _MapSource)) else None
     extras = StepExtras(source, surface_loss, phase, history, material, solidification, material_map, monitor)
     _check_extras(grid, mat, params, packs, extras)
     if history is not None:

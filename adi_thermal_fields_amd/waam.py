@@ -120,7 +120,7 @@ def _require_device_loop(who, backend, dev_loop, **asked):
     """ValueError for an option (name = value) that is set where the loop cannot serve it"""
     for name, cls in (('surface_loss', 'LossPacks'), ('phase_change', 'PhaseField'), ('history', 'ThermalHistory'),
                       ('material_law', 'NonlinearPacks'), ('solidification', 'SolidificationRecord'),
-                      ('monitor', 'FieldMonitor')):
+                      ('monitor', 'FieldMonitor'), ('material_map', 'MaterialMap')):
         if asked.get(name) is not None and not (dev_loop and hasattr(backend, cls)):
             raise ValueError("%s: %s needs the device loop of a backend with %s" % (who, name, cls))
 
@@ -129,25 +129,32 @@ class _LoopExtras:
     """The bookkeeping of the optional parts that live through a device loop, once for the three run_* loops: the PhaseField
     (`ph`), the ThermalHistory (`hist`), the SolidificationRecord (`sol`) and the FieldMonitor (`mon`) of the backend, each None
     when its option is.  T: the field they are seeded from (phase_T: the PhaseField's; None seeds nothing, all solid); rows: the
-    capacity of the history's log and the monitor's; t: where their clocks start."""
+    capacity of the history's log and the monitor's; t: where their clocks start.
+    mm: the loop's MaterialMap (None: one material).  With it `phase_change` is a sequence of PhaseChange / None per material and
+    `ph` a MapPhaseField, the monitor is built with material_map=mm (its region_log reports sum_wT), and step_kw carries
+    material_map=mm."""
 
     def __init__(self, backend, grid, mat, T, rows=1, t=0.0, phase_T=None, phase_change=None, history=None, solidification=None,
-                 monitor=None):
-        self.mat = mat
+                 monitor=None, mm=None):
+        self.mat, self.mm = mat, mm
         self.ph = self.hist = self.sol = self.mon = None
-        if phase_change is not None:
+        if phase_change is not None and mm is not None:
+            self.ph = backend.MapPhaseField(mm, phase_change, T=phase_T)
+        elif phase_change is not None:
             self.ph = backend.PhaseField(grid, mat, phase_change, T=phase_T)
         if history is not None:
             self.hist = backend.ThermalHistory(grid, history, capacity=rows, T=T, t=t)
         if solidification is not None:
             self.sol = backend.SolidificationRecord(grid, solidification, T=T, t=t)
         if monitor is not None:                        # (a dict of FieldMonitor's keywords; the capacity is the run's)
-            self.mon = backend.FieldMonitor(grid, **dict(dict({'t': t}, **monitor), capacity=max(1, int(rows))))
+            more = {} if mm is None else {'material_map': mm}
+            self.mon = backend.FieldMonitor(grid, **dict(dict({'t': t}, **monitor), capacity=max(1, int(rows)), **more))
 
     def step_kw(self, surface_loss=None, material=None):
         """the keywords of a step / a stepper for the parts that are present, with the loop's LossPacks or NonlinearPacks"""
         return {k: v for k, v in (('surface_loss', surface_loss), ('phase', self.ph), ('history', self.hist),
-                                  ('material', material), ('solidification', self.sol), ('monitor', self.mon)) if v is not None}
+                                  ('material', material), ('solidification', self.sol), ('monitor', self.mon),
+                                  ('material_map', self.mm)) if v is not None}
 
     def sync(self, T):
         """after a birth / a new column / a deposit: the newborn cells at f_eq(T), at T_peak = T and "never froze" (cells born
@@ -171,6 +178,26 @@ class _LoopExtras:
         return res if self.mon is None else res + monitor_result(self.mon, self.mat)
 
 
+MAP_DOC = """material_map (a dict; device loop only): several materials in one grid -- materials=[(rho, cp, k), ...] and ids= (uint8,
+    the full shape, the id of every cell the run can activate; EVERY id must name a material, off the final shape too).  The loop
+    builds one MaterialMap, with robin_h from the scalar `h` unless surface_loss is given, and passes material_map= to every step and
+    stepper; the step's material is materials[0] (mat_args is not used).  surface_loss may then be one SurfaceLoss or a sequence
+    per material (a MapLossPacks), phase_change is a sequence of PhaseChange / None per material (a MapPhaseField, newborn cells
+    seeded by sync_mask); history, solidification and monitor run as without it, the monitor's region_log reports sum_wT.  Not
+    together with material_law (ValueError).  None: the loop without it, unchanged."""
+
+
+def _loop_map(who, backend, grid, material_map, h, Tinf, surface_loss, material_law=None, keys=('materials', 'ids')):
+    """the MaterialMap of a device loop and its MapLossPacks (None without surface_loss) from the `material_map` dict"""
+    if material_law is not None:
+        raise ValueError("%s: material_map cannot be combined with material_law (k(T) and cp(T) per material are not served)" % who)
+    if not isinstance(material_map, dict) or set(material_map) != set(keys):
+        raise ValueError("%s: material_map must be a dict with the keys %s" % (who, ', '.join(keys)))
+    robin = None if surface_loss is not None else {f: h for f in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')}
+    mm = backend.MaterialMap(grid, material_map['materials'], np.asarray(material_map['ids']), robin_h=robin)
+    return mm, (None if surface_loss is None else backend.MapLossPacks(mm, surface_loss, Tinf))
+
+
 def _step(backend, T, grid, mat, params, packs, Tinf):
     fn = getattr(backend, 'adi_step_hip_coeff', None) or backend.adi_step_numba_coeff
     return fn(T, grid, mat, params, packs, Tinf=Tinf)
@@ -188,8 +215,11 @@ def _birth(backend, T, grid, newborn, Ts):
 
 def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, layers, times_birth, times_out,
                     on_frame=None, device_resident=True, device_loop=True, surface_loss=None, phase_change=None, history=None,
-                    solidification=None, monitor=None):
+                    solidification=None, monitor=None, material_map=None):
     """The event loop of waam_from_stl_v7_mm.py:515-550.  Returns (T_final as NumPy, number of ADI steps).
+    material_map: see waam.MAP_DOC -- mask_full may then hold several materials (a plate and a part): after a birth the map's
+    packs are rewritten on the planes that changed (MaterialMap.update), nothing is read back; the time-step cap is taken with the
+    largest diffusivity among the materials.
     surface_loss (a SurfaceLoss of the backend): the surface loses heat by that law, evaluated at the temperature at the start
     of every sub-step, in place of the constant `h` (which is then not used); device loop only.  None: the reference's loop.
     phase_change (a PhaseChange of the backend): latent heat of melting and freezing; one PhaseField lives through the run, every
@@ -211,11 +241,14 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     mat = backend.Material(*mat_args)
     params = backend.Params(dt=1e-3, theta=theta)
     alpha = mat_args[2] / (mat_args[0] * mat_args[1])
+    if isinstance(material_map, dict) and 'materials' in material_map:
+        alpha = max(float(k) / (float(rho) * float(cp)) for rho, cp, k in material_map['materials'])
     dt_cap = cfl * dx * dx / alpha
     T = np.full((nx, ny, nz), float(Tinf), dtype=np.float64)
     if device_resident and _is_device_backend(backend):
         T = backend.to_device(T)
     robin = {f: h for f in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')}
+    mm = None
 
     def build_packs():
         return backend.precompute_coeff_packs_unified(grid, mat, dir_mask=None, dir_value=None, neumann=None,
@@ -246,7 +279,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
     # output times and nothing waits for the device between births
     dev_loop = device_loop and device_resident and hasattr(backend, 'BirthPacks') and hasattr(T, 'fill_where')
     _require_device_loop('run_layer_birth', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
-                         history=history, solidification=solidification, monitor=monitor)
+                         history=history, solidification=solidification, monitor=monitor, material_map=material_map)
     ex = _LoopExtras(backend, grid, mat, T)                            # (nothing was asked for where there is no device loop)
     if dev_loop:
         import torch
@@ -255,9 +288,15 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
         grid.set_mask_device(d_act, all_solid=False)
         # (with a surface loss: LossPacks, whose coefficients follow the field -- `update` ahead of every sub-step, inside the
         # step; `rebuild` on the planes a birth changed)
-        bpacks = backend.BirthPacks(grid, mat, robin_h=robin) if surface_loss is None else \
-            backend.LossPacks(grid, mat, surface_loss, Tinf)
-        packs = bpacks.packs
+        if material_map is not None:
+            # several materials: the map's own packs, rewritten on the planes a birth changed (MaterialMap.update); its
+            # MapLossPacks needs no call of its own there -- update leaves zeros and the step's loss update writes the exposed cells
+            mm, bpacks = _loop_map('run_layer_birth', backend, grid, material_map, h, Tinf, surface_loss)
+            mat, packs = mm.mat, mm.packs
+        else:
+            bpacks = backend.BirthPacks(grid, mat, robin_h=robin) if surface_loss is None else \
+                backend.LossPacks(grid, mat, surface_loss, Tinf)
+            packs = bpacks.packs
         plane_cells = np.asarray(mask_full).sum(axis=(0, 1)).astype(np.int64)      # newborn cells per plane, host-known
         plane_born = np.zeros(nz, dtype=bool)
         rows = 1
@@ -266,7 +305,7 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
                               if w == 'advance'))
         # (the PhaseField unseeded: nothing is active yet, all solid)
         ex = _LoopExtras(backend, grid, mat, T, rows, phase_change=phase_change, history=history, solidification=solidification,
-                         monitor=monitor)
+                         monitor=monitor, mm=mm)
     else:
         packs = build_packs()
     n_active = 0
@@ -279,7 +318,9 @@ def run_layer_birth(backend, mask_full, dx, mat_args, h, Tinf, Ts, theta, cfl, l
             n_active += int(plane_cells[ks:ke + 1][fresh].sum())
             plane_born[ks:ke + 1] = True
             grid.set_mask_device(d_act, ks - 1 if ks > 0 else 0, min(nz, ke + 2), all_solid=False)   # :494-495
-            if surface_loss is None:
+            if mm is not None:
+                packs = mm.update(ks - 1, ke + 2)
+            elif surface_loss is None:
                 packs = bpacks.update(ks - 1, ke + 2)                             # :534, the planes that changed
             else:
                 packs = bpacks.rebuild(T, ks - 1, ke + 2)
@@ -321,9 +362,12 @@ def track_source(heat_source, track_box, dx, yi, t_step):
 
 def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_track, theta, dt, t_step,
                      device_resident=True, heat_source=None, surface_loss=None, phase_change=None, history=None,
-                     material_law=None, solidification=None, monitor=None):
+                     material_law=None, solidification=None, monitor=None, material_map=None):
     """single_track_on_plate.py:150-177: the deposit advances one column per t_step along axis 1; packs are
     rebuilt after every column.  track_box = (x0, x1, z0, z1, n_columns).
+    material_map: see waam.MAP_DOC -- e.g. a track of one alloy on a plate of another: the map's packs are rebuilt in full after
+    every column (MaterialMap.rebuild, the shape of this loop), `heat_source` becomes a MapSource of the map, and columns of at
+    least GRAPH_MIN_NSUB sub-steps are replayed from a HIP graph.
     heat_source (a GoldakSource of the backend): the arc / laser as a moving volumetric source (track_source) during the
     sub-steps of every column, on top of the newborn cells set to T_track.  None: the reference's driver, unchanged.
     surface_loss (a SurfaceLoss of the backend): the surface loses heat by that law, evaluated at the temperature at the start
@@ -368,19 +412,23 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
     robin = {f: h for f in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')}
     dev_loop = device_resident and hasattr(grid, 'set_mask_device') and hasattr(T, 'fill_where')
     _require_device_loop('run_single_track', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
-                         history=history, material_law=material_law, solidification=solidification, monitor=monitor)
+                         history=history, material_law=material_law, solidification=solidification, monitor=monitor,
+                         material_map=material_map)
     if dev_loop:                                    # the mask lives in HBM: a new column is two slice assignments
         import torch
         d_mask = grid.layout.to_layout(mask, torch.uint8)
-    nm = None
+    nm = mm = None
+    if material_map is not None:
+        mm, maploss = _loop_map('run_single_track', backend, grid, material_map, h, Tinf, surface_loss, material_law)
+        mat = mm.mat
     if material_law is not None:
         nm = backend.NonlinearPacks(grid, mat.rho, material_law, Tinf,
                                     loss=surface_loss if surface_loss is not None else backend.SurfaceLoss(h=h))
         mat = nm.mat
-    lpacks = backend.LossPacks(grid, mat, surface_loss, Tinf) if surface_loss is not None and nm is None else None
+    lpacks = backend.LossPacks(grid, mat, surface_loss, Tinf) if surface_loss is not None and nm is None and mm is None else None
     ex = _LoopExtras(backend, grid, mat, T, ncol * max(1, int(math.ceil(t_step / dt))), phase_T=T, phase_change=phase_change,
-                     history=history, solidification=solidification, monitor=monitor)
-    kw = ex.step_kw(surface_loss=lpacks, material=nm)
+                     history=history, solidification=solidification, monitor=monitor, mm=mm)
+    kw = ex.step_kw(surface_loss=lpacks if mm is None else maploss, material=nm)
     for yi in range(ncol):
         if dev_loop:
             d_mask[x0:x1, yi:yi + 1, z0:z1] = 1
@@ -388,7 +436,10 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         else:
             mask[x0:x1, yi:yi + 1, z0:z1] = True
             grid.mask = mask
-        if lpacks is None and nm is None:
+        if mm is not None:
+            mm.rebuild()                            # (its MapLossPacks needs no call: rebuild left zeros, the step writes the rest)
+            packs = mm.packs
+        elif lpacks is None and nm is None:
             packs = backend.precompute_coeff_packs_unified(grid, mat, robin_h=robin, robin_Tinf=Tinf)
         T[x0:x1, yi:yi + 1, z0:z1] = T_track
         if lpacks is not None or nm is not None:
@@ -399,6 +450,8 @@ def run_single_track(backend, plate_mask, track_box, dx, mat_args, h, Tinf, T_tr
         params.dt = t_step / n_sub
         if kw:
             src = None if heat_source is None else track_source(heat_source, track_box, dx, yi, t_step)
+            if src is not None and mm is not None:
+                src = backend.MapSource(mm, src)
             if n_sub >= GRAPH_MIN_NSUB:
                 T = backend.StagedStepper(grid, mat, params, packs, Tinf, source=src, **kw).run(T, n_sub, t0=0.0)
             else:
@@ -431,7 +484,7 @@ def path_steps(t_start, t_end, dt):
 
 def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, Ts, theta, dt, t_end=None, within=None,
                         heat=False, surface_loss=None, phase_change=None, history=None, solidification=None, on_frame=None,
-                        monitor=None):
+                        monitor=None, material_map=None):
     """Material laid along a scan path, bead by bead (README, "Deposition along a path"): from path.t_start to t_end (default
     path.t_end) in steps of dt (path_steps), every step preceded by the births of its interval -- the bead of the step [t, t + dt]
     is born at the step's start, at Ts, on top of `base_mask` (the plate; may be empty).  Device loop only: mask, field and packs
@@ -446,6 +499,10 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
     f_eq(Ts) / Ts / "never froze", the recorders run on the global time, from path.t_start, and the history's log holds one row
     per step.
     monitor: as in run_single_track -- one FieldMonitor, one log row per step, its clock from path.t_start; a deposit needs no call.
+    material_map: see waam.MAP_DOC, with one more key, wire=m: the id of what the path lays -- a wire of one alloy on a base plate
+    of another.  Every deposit writes m into the map's device id field on its newborn cells (PathDeposit(material_map=,
+    material_id=)) and the map's packs are rewritten on the planes it changed (MaterialMap.update); nothing is read back.
+    heat=True stays the field form.
     on_frame(t, T, active): called after every step with the time reached and NumPy copies (a download; None: none).
     Returns (T_final, active mask, number of ADI steps), all host side, then the final liquid fraction, history_result and
     solidification_result for those that were asked for, in this order, then the monitor's traces() and region_log(mat)."""
@@ -460,23 +517,33 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
     if not dev_loop:
         raise ValueError("run_path_deposition: needs the device loop of a backend with PathDeposit")
     _require_device_loop('run_path_deposition', backend, dev_loop, surface_loss=surface_loss, phase_change=phase_change,
-                         history=history, solidification=solidification, monitor=monitor)
+                         history=history, solidification=solidification, monitor=monitor, material_map=material_map)
     src = path.on_device() if hasattr(path, 'on_device') else path
-    dep = backend.PathDeposit(grid, src, bead, Ts, within=within)
     steps = path_steps(src.t_start, src.t_end if t_end is None else float(t_end), float(dt))
     robin = {f: h for f in ('x-', 'x+', 'y-', 'y+', 'z-', 'z+')}
-    bpacks = backend.BirthPacks(grid, mat, robin_h=robin) if surface_loss is None else \
-        backend.LossPacks(grid, mat, surface_loss, Tinf)
-    packs = bpacks.packs
+    mm = None
+    if material_map is not None:
+        mm, bpacks = _loop_map('run_path_deposition', backend, grid, material_map, h, Tinf, surface_loss,
+                               keys=('materials', 'ids', 'wire'))
+        dep = backend.PathDeposit(grid, src, bead, Ts, within=within, material_map=mm, material_id=material_map['wire'])
+        mat, packs = mm.mat, mm.packs
+    else:
+        dep = backend.PathDeposit(grid, src, bead, Ts, within=within)
+        bpacks = backend.BirthPacks(grid, mat, robin_h=robin) if surface_loss is None else \
+            backend.LossPacks(grid, mat, surface_loss, Tinf)
+        packs = bpacks.packs
     ex = _LoopExtras(backend, grid, mat, T, max(1, len(steps)), t=src.t_start, phase_T=T, phase_change=phase_change,
-                     history=history, solidification=solidification, monitor=monitor)
+                     history=history, solidification=solidification, monitor=monitor, mm=mm)
     kw = ex.step_kw(surface_loss=None if surface_loss is None else bpacks)
     live = bool(np.asarray(base_mask).any())
     nsteps = 0
     for t, d in steps:
         rng = dep.deposit(T, t, d)
         if rng is not None:                            # something could have been born: the planes that changed
-            packs = bpacks.update(*rng) if surface_loss is None else bpacks.rebuild(T, *rng)
+            if mm is not None:
+                packs = mm.update(*rng)
+            else:
+                packs = bpacks.update(*rng) if surface_loss is None else bpacks.rebuild(T, *rng)
             ex.sync(T)
             live = True
         if live:

@@ -744,6 +744,13 @@ int adi_bead_deposit_host(const adi_bead_shape *shape, const double *h_table, in
 int adi_bead_deposit(const adi_bead_shape *shape, const double *h_table, const double *d_table, int K, double t_end, double *d_T,
                      uint8_t *d_active, const uint8_t *d_within, int lx, int ly, int lz, int nx, int ny, int nz,
                      long plane_stride, double dx, double t, double dt, double Ts, unsigned long long *d_newborn, void *stream);
+/* adi_bead_deposit on a grid of several materials ("Several materials" below): on exactly the newborn cells it also writes
+ * d_ids[p] = id (0 <= id < ADI_MATMAP_MAX; d_ids in the box layout, not NULL, no alias of a mask); every other id keeps its
+ * bits, and d_T, d_active and *d_newborn are what adi_bead_deposit gives (one kernel serves both). */
+int adi_bead_deposit_ids(const adi_bead_shape *shape, const double *h_table, const double *d_table, int K, double t_end,
+                         double *d_T, uint8_t *d_active, const uint8_t *d_within, uint8_t *d_ids, int id, int lx, int ly, int lz,
+                         int nx, int ny, int nz, long plane_stride, double dx, double t, double dt, double Ts,
+                         unsigned long long *d_newborn, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Temperature-dependent surface loss of the Cartesian step (no counterpart in the reference, which freezes robin_h when the
@@ -1089,6 +1096,24 @@ int adi_matmap_build_coeffs(const uint8_t *d_mask, const uint8_t *d_ids, int nx,
                             int nmat, const double *h_C, const int *h_mode, const double *h_scalar,
                             const double *const *d_h_field, const int *q_mode, const double *q_scalar,
                             const double *const *d_q_field, double *const *d_coeff, double *const *d_qflux, void *stream);
+/* The same on the planes [k_begin, k_end) of axis 2 only (0 <= k_begin < k_end <= nz, else ADI_ERR_ARG "bad plane range"): inside
+ * the range every cell of the six arrays gets exactly what adi_matmap_build_coeffs writes, zeros where it is not exposed;
+ * outside it not one byte is written.  After a birth or a deposit only the planes it touched and one either side change
+ * exposure.  Nothing but d_mask, d_ids and the per-voxel fields is read. */
+int adi_matmap_build_coeffs_planes(const uint8_t *d_mask, const uint8_t *d_ids, int nx, int ny, int nz, long plane_stride,
+                                   double dx, int nmat, const double *h_C, const int *h_mode, const double *h_scalar,
+                                   const double *const *d_h_field, const int *q_mode, const double *q_scalar,
+                                   const double *const *d_q_field, double *const *d_coeff, double *const *d_qflux, int k_begin,
+                                   int k_end, void *stream);
+/* A moving Goldak source on such a grid, added to the explicit stage's output: R0_i = R0_i + (dt q_i(t_n + dt/2)) / C_{id_i} on
+ * the in-mask cells the support reaches, q from the parameter block d_block of adi_source_set / adi_source_tick and the cell
+ * centres ((i + 1/2) dx, ...) -- the operations of adi_matmap_explicit's d_S term, in its order, with q evaluated in the
+ * kernel.  One thread per cell of the support's launch box, placed on the device from the block and clipped to the grid as
+ * adi_source_add_r0 places it (h_src: the same source on the host, for the box's extent); off-mask cells and cells the support
+ * misses are not written.  Reads flags, id and R0 and writes R0: 17 bytes per in-mask cell of the support. */
+int adi_matmap_source_add_r0(const void *d_block, const adi_heat_source *h_src, double *d_R0, const uint8_t *d_flags,
+                             const uint8_t *d_ids, int nx, int ny, int nz, long plane_stride, double dx, double dt, int nmat,
+                             const double *h_C, void *stream);
 /* R0 into d_out (must not alias d_T); d_S (optional): source field in W/m^3 */
 int adi_matmap_explicit(const double *d_T, const double *d_S, const uint8_t *d_flags, const uint8_t *d_ids, int nx, int ny,
                         int nz, long plane_stride, int nmat, const double *h_G, const double *h_C, double dt, double theta,

@@ -44,6 +44,8 @@ FOOT = [
     ('adi::k_matmap_sweep_contig<16, true, true>', 'the same, 16 rows per lane (513 - 1024 rows): one wave per SIMD'),
     ('adi::k_matmap_sweep_lines<true, true>', 'several materials: lines beyond 1024 rows, one thread per line, 50 B/cell'),
     ('adi::k_matmap_build_coeffs', 'several materials: the coefficient build'),
+    ('adi::k_mapcoeffs_planes', 'several materials (section 6l3): the coefficient build on a range of axis-2 planes'),
+    ('adi::k_mapsource_add_r0', 'several materials (section 6l3): a moving Goldak source added to R0, 17 B per in-mask cell of the support'),
 ]
 
 
