@@ -21,16 +21,31 @@ LOSSES = (SurfaceLoss(h={'x-': 15.0, 'x+': 25.0, 'y-': 0.0, 'y+': 10.0, 'z-': 5.
                       table=([300.0, 800.0, 1200.0, 1600.0], [2.0, 9.0, 30.0, 55.0])),
           SurfaceLoss(h={'x-': 8.0, 'x+': 12.0, 'y-': 0.0, 'y+': 20.0, 'z-': 30.0, 'z+': 6.0}, emissivity=0.05),
           SurfaceLoss(h={'x-': 3.0, 'x+': 4.0, 'y-': 0.0, 'y+': 5.0, 'z-': 6.0, 'z+': 7.0}, emissivity=0.9))
+# Eight materials (tests/matmap_eight_cases.py, MATERIALS8): the three above, then five more.  The melting ranges lie inside the
+# range of the test fields, [900, 1700], where every branch of the correction is reached (they are not the metals' own), and two
+# materials -- ids 2 and 4 -- have no law: the set of materials with one is 0b11101011.  The losses: a table with and without
+# radiation, radiation alone, a plain h, faces where nothing is lost at all.
+LAWS8 = LAWS + (PhaseChange(1.3e5, 1480.0, 1540.0), None, PhaseChange(2.0e4, 1100.0, 1130.0),
+                PhaseChange(2.1e5, 1260.0, 1336.0), PhaseChange(3.7e5, 1150.0, 1300.0))
+LOSSES8 = LOSSES + (
+    SurfaceLoss(emissivity=0.6),                                                                   # radiation alone
+    SurfaceLoss(h={'x-': 11.0, 'x+': 0.0, 'y-': 13.0, 'y+': 17.0, 'z-': 0.0, 'z+': 19.0}),         # h alone; nothing on x+ and z-
+    SurfaceLoss(h={'x-': 2.0, 'x+': 3.0, 'y-': 5.0, 'y+': 7.0, 'z-': 11.0, 'z+': 13.0},
+                table=([250.0, 1000.0, 1750.0], [1.0, 20.0, 80.0])),                               # a table without radiation
+    SurfaceLoss(h={'x-': 0.0, 'x+': 9.0, 'y-': 0.0, 'y+': 0.0, 'z-': 21.0, 'z+': 0.0},
+                emissivity={'x-': 0.0, 'x+': 0.3, 'y-': 0.7, 'y+': 0.0, 'z-': 0.2, 'z+': 0.0},
+                table=([100.0, 600.0, 900.0, 1300.0, 1900.0], [4.0, 6.0, 15.0, 22.0, 90.0])),      # x-, y+ and z+ lose nothing
+    SurfaceLoss(h=27.0, emissivity=0.45, T_offset=0.0))                                            # temperatures in kelvin
 BRANCHES = ('all_solid', 'all_liquid', 'mushy', 'rest_solid', 'rest_liquid', 'dirichlet_skipped')
 BRICK = 16
 
 
 def laws_of(materials):
-    return LAWS[:len(materials)]
+    return LAWS8[:len(materials)]
 
 
 def losses_of(materials):
-    return LOSSES[:len(materials)]
+    return LOSSES8[:len(materials)]
 
 
 def fields(mask, ids, laws, seed=0):
