@@ -234,6 +234,11 @@ SIGNATURES = {
     'adi_matmap_loss_table': (c_int, [c_int, c_void_p, c_double_p, c_double, c_void_p, c_size_t]),
     'adi_matmap_loss_update': (c_int, [c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                        c_long, c_double, c_void_pp, c_int, c_int, c_int, c_void_p]),
+    'adi_matmap_transition': (c_int, [c_int, c_int_p, c_double_p, c_void_p, c_int_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long,
+                                      c_double, c_double_p, c_int_p, c_double_p, c_void_pp, c_int_p, c_double_p, c_void_pp,
+                                      c_void_pp, c_void_pp, c_void_p]),
+    'adi_matmap_brick_sets': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
     'adi_ctx_create': (c_int, [c_int, c_int, c_int, c_double, c_int, c_void_pp]),
     'adi_ctx_destroy': (c_int, [c_void_p]),
     'adi_ctx_set_mask': (c_int, [c_void_p, c_void_p]),

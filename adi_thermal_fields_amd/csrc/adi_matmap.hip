@@ -1,8 +1,9 @@
 // adi_matmap.hip -- the Cartesian step on a grid of several materials (include/adi_hip.h, "Several materials"; DESIGN.md
 // section 6l): every cell carries a material id, the coupling of a cell to a neighbour is the pair-table entry
 // G[own id][neighbour's id], and each row is divided by its own C = rho cp.  Hand-written HIP for gfx950:
-//   k_matmap_build_coeffs   Robin coefficient + Neumann flux fields of the three axes, (h A) / (C_id V) per exposed face;
-//                           k_mapcoeffs_planes: the same cells' values on a range of axis-2 planes only
+//   k_matmap_build_coeffs   Robin coefficient + Neumann flux fields of the three axes, (h A) / (C_id V) per exposed face
+//                           (map_coeffs_cell of adi_matmap_dev.hpp); k_mapcoeffs_planes: the same cells' values on a range of
+//                           axis-2 planes only
 //   k_matmap_explicit       R0 = T + (1 - theta) sum G[id][id_n] (T_n - T)  [+ dt S / C_id]
 //   k_matmap_sweep_contig   sweep along memory axis 2: a line's segments in the lanes of one wave (condense / pcr_solve /
 //                           back_solve of adi_core.hpp with per-row off-diagonals), lines of at most kMaxFastLine rows
@@ -14,48 +15,6 @@
 #include "adi_matmap_dev.hpp"
 
 namespace adi {
-
-struct MapFaceSpec {
-    int mode[6];
-    double scalar[6];
-    const double *field[6];
-};
-
-// k_build_coeffs (adi_fields.hip) with the cell's own heat capacity: '-' face then '+' face per axis, (h * A) / (C_id * V) with
-// IEEE division, contraction off -> bit-identical to MaterialMap.packs_reference.  sC: C_m * V in LDS.  An id off the mask is not
-// read.  The six values of the cell (i, j, k) at offset p, zeros where it is not exposed: what both kernels below store.
-__device__ __forceinline__ void map_coeffs_cell(const uint8_t *__restrict__ mask, const uint8_t *__restrict__ ids, const Lay &L,
-                                                double A, const double *sC, const MapFaceSpec &h, const MapFaceSpec &q, int i, int j,
-                                                int k, long p, double *__restrict__ c0, double *__restrict__ c1,
-                                                double *__restrict__ c2, double *__restrict__ q0, double *__restrict__ q1,
-                                                double *__restrict__ q2)
-{
-#pragma clang fp contract(off)
-    const long st[3] = {L.sx, (long)L.nz, 1};
-    const int pos[3] = {i, j, k}, nn[3] = {L.nx, L.ny, L.nz};
-    const bool m = mask[p] != 0;
-    const double Ccell = m ? sC[ids[p] & (kMapMaxMat - 1)] : 1.0;
-    double co[3] = {0.0, 0.0, 0.0}, qq[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int f = 0; f < 6; ++f) {
-        const int ax = f >> 1;
-        const int nbp = pos[ax] + ((f & 1) ? 1 : -1);
-        bool exposed = m;
-        if (m && nbp >= 0 && nbp < nn[ax]) exposed = mask[p + ((f & 1) ? st[ax] : -st[ax])] == 0;
-        if (exposed) {
-            if (h.mode[f] != ADI_FACE_NONE) {
-                const double hv = (h.mode[f] == ADI_FACE_SCALAR) ? h.scalar[f] : h.field[f][p];
-                co[ax] += (hv * A / Ccell);
-            }
-            if (q.mode[f] != ADI_FACE_NONE) {
-                const double qv = (q.mode[f] == ADI_FACE_SCALAR) ? q.scalar[f] : q.field[f][p];
-                qq[ax] += (qv * A / Ccell);
-            }
-        }
-    }
-    c0[p] = co[0]; c1[p] = co[1]; c2[p] = co[2];
-    q0[p] = qq[0]; q1[p] = qq[1]; q2[p] = qq[2];
-}
 
 __global__ __launch_bounds__(256) void k_matmap_build_coeffs(const uint8_t *__restrict__ mask, const uint8_t *__restrict__ ids,
                                                              Lay L, double A, MapScal s, MapFaceSpec h, MapFaceSpec q,
@@ -338,13 +297,7 @@ static int map_build_coeffs(const char *who, const uint8_t *d_mask, const uint8_
     if (int rc = make_lay(nx, ny, nz, plane_stride, &L)) return rc;
     if (planes) ADI_REQUIRE(k_begin >= 0 && k_end <= nz && k_begin < k_end, "%s: bad plane range [%d, %d)", who, k_begin, k_end);
     MapFaceSpec h, q;
-    for (int f = 0; f < 6; ++f) {
-        h.mode[f] = h_mode[f]; h.scalar[f] = h_scalar[f]; h.field[f] = d_h_field ? d_h_field[f] : nullptr;
-        q.mode[f] = q_mode[f]; q.scalar[f] = q_scalar[f]; q.field[f] = d_q_field ? d_q_field[f] : nullptr;
-        ADI_REQUIRE(h.mode[f] >= 0 && h.mode[f] <= 2 && q.mode[f] >= 0 && q.mode[f] <= 2, "%s: bad face mode", who);
-        ADI_REQUIRE(h.mode[f] != ADI_FACE_FIELD || h.field[f], "%s: missing h field for face %d", who, f);
-        ADI_REQUIRE(q.mode[f] != ADI_FACE_FIELD || q.field[f], "%s: missing q field for face %d", who, f);
-    }
+    if (int rc = make_face_specs(who, h_mode, h_scalar, d_h_field, q_mode, q_scalar, d_q_field, &h, &q)) return rc;
     for (int a = 0; a < 3; ++a) ADI_REQUIRE(d_coeff[a] && d_qflux[a], "%s: null output", who);
     MapScal s = {};
     const double A = dx * dx;

@@ -57,18 +57,6 @@ struct LdsLaws {
     __device__ __forceinline__ double get(int field, unsigned id) const { return t[field * kMapMaxMat + id]; }
 };
 
-// the id bytes of a pair: cell 0 in bits 0-7, cell 1 in bits 8-15 (VEC: one 2-byte load, the id field 2-byte aligned)
-template <bool VEC>
-__device__ __forceinline__ unsigned load_id_pair(const uint8_t *__restrict__ ids, const PhaseCell &c)
-{
-    if (VEC) return *reinterpret_cast<const unsigned short *>(ids + c.p);
-    unsigned v = ids[c.p];
-    if (c.in & 2u) v |= (unsigned)ids[c.p + 1] << 8;
-    return v;
-}
-
-__device__ __forceinline__ unsigned id_of(unsigned pair, int s) { return (pair >> (8 * s)) & (unsigned)(kMapMaxMat - 1); }
-
 // the body of k_phase_apply (adi_phase.hip) with the law taken from LAWS: uniform (OneLaw) or per cell (LdsLaws)
 template <bool VEC, class LAWS>
 __device__ __forceinline__ void phase_brick(const LAWS &laws, double *__restrict__ T, double *__restrict__ F,
@@ -255,11 +243,6 @@ static int make_phase_table(const char *who, int nmat, const adi_phase_change *h
         t->on |= 1u << m;
     }
     return ADI_OK;
-}
-
-static bool map_pair_vec(const Lay &L, const void *flags, const void *ids, const void *a, const void *b)
-{
-    return pair_vec(L, flags, a, b) && ((uintptr_t)ids & 1) == 0;
 }
 
 }  // namespace adi

@@ -1,7 +1,8 @@
 """Latent heat and temperature-dependent surface loss on a grid of several materials: `MapPhaseField`, the
 liquid fraction of a MaterialMap's grid under one PhaseChange law per material, and `MapLossPacks`, the MaterialMap's own packs
-rewritten in place by one SurfaceLoss per material; and `MapSource`, a moving GoldakSource inside the step of a MaterialMap
-(DESIGN.md section 6l3)."""
+rewritten in place by one SurfaceLoss per material; `MapSource`, a moving GoldakSource inside the step of a MaterialMap
+(DESIGN.md section 6l3); and `MaterialTransitions`, cells that change their material when they get hot enough (DESIGN.md section
+6l4)."""
 import ctypes
 
 import numpy as np
@@ -10,7 +11,7 @@ import torch
 from . import _lib
 from ._lib import lib, check, ptr_array, FACES
 from .fields import DeviceField, _SeededForMask, _as_state, _device, _native_f64, _p, _stream, _wrap
-from .packs import MaterialMap, _MapLoss, _MapPhase, _MapSource, _triples
+from .packs import MaterialMap, _MapLoss, _MapPhase, _MapSource, _MapTransitions, _triples, _face_spec_args
 from .heat_source import GoldakSource, _source_block
 from .surface_loss import SurfaceLoss
 from .phase import PhaseChange
@@ -336,3 +337,203 @@ class MapSource(_MapSource):
         self.set_block(blk, t, params.dt)
         self.add_r0(out, params, blk)
         return _wrap(out, kind)
+
+
+class MaterialTransitions(_MapTransitions):
+    """Cells of a MaterialMap that change their material because of what the step did to them: loose powder that reaches its
+    liquidus is dense metal for the rest of the run, a flux burns off, a wire that was molten once has other properties.
+    rules: one entry per material of `mm`, None or (to, T_at): a cell of that material whose temperature is at or above T_at
+        (finite) becomes material `to` (another material of the map).
+    phase (optional): the MapPhaseField of the same map the step runs with; a changed cell's f becomes f_eq(T) under the law of
+        its new material, 0 if that has none (the field's invariant: f = 0 in law-less cells).
+    Pass it to the step as `transitions=` next to `material_map=mm` (and `phase=` if given here): one launch on the step's output
+    after the latent-heat correction and before the recorders, captured into a StagedStepper's graph -- so ids change between
+    replayed steps, without a host round trip or a rebuild().
+
+    THE MODEL: the properties switch at constant temperature.  T is never written, so the heat content sum C_id V T jumps by
+    (C_to - C_m) V T per changed cell, as in finite-element powder-bed codes that swap the property set at the liquidus; the
+    switch does not conserve enthalpy (a FieldMonitor's sum_wT shows the jump, with the new ids).  A cell changes at most once
+    per step: where the new material has a rule of its own and the cell is hot enough for that too, it waits for the next step.
+    In-mask cells only; Dirichlet cells never change.
+
+    A changed cell gets its id byte, its six pack values (those mm.rebuild() would write: they depend on the cell's own id and
+    its neighbours' mask only) and, with `phase`, its f.  With a MapLossPacks the map was built with robin_h=None, so the three
+    `coeff` values written here are the zeros of that build until the next step's adi_matmap_loss_update -- the first launch of
+    that step -- rewrites every exposed cell: no step ever reads the zeros, and no second loss evaluation is made here.
+
+    The pass reads one word per 16^3 brick first, the set of ids among the brick's in-mask cells: `phase.brick_ids` itself when a
+    phase is given (no copy; the pass keeps those words exact), an array of the same definition this object owns otherwise
+    (adi_matmap_brick_sets).  The object remembers grid.mask_version and the map's id version: after either changed the step
+    raises ValueError until sync_mask() (after mph.sync_mask(T) when there is a phase).  A transition itself is no such change:
+    a captured graph holds the id field by pointer.  After a launch `mm.ids` downloads the field.  Needs mm.ids_all_valid.
+        apply(T, d_dir_mask=None)   the pass on a device field in the grid's layout (T is only read): one launch
+        changed / reset_count()     the cells changed since construction or the last reset (reading it synchronises)
+        sync_mask()                 see above
+        snapshot() / restore(s)     the id field, the words and the counter; restore also rewrites the packs (mm.update)
+    `apply_reference` is the definition in NumPy fp64."""
+
+    def __init__(self, mm, rules, phase=None):
+        if not isinstance(mm, MaterialMap):
+            raise TypeError("MaterialTransitions: mm must be a MaterialMap")
+        self.rules = self._checked_rules(rules, len(mm.materials))
+        if phase is not None:
+            if not isinstance(phase, MapPhaseField):
+                raise TypeError("MaterialTransitions: phase must be a MapPhaseField, got %s" % type(phase).__name__)
+            if phase.mm is not mm:
+                raise ValueError("MaterialTransitions: the MapPhaseField belongs to another MaterialMap")
+        if not mm.ids_all_valid:
+            raise ValueError("MaterialTransitions: the id field holds an id that names no material (off the mask); restore() "
+                             "rewrites the packs with MaterialMap.update, which needs every id below %d" % len(mm.materials))
+        self.mm, self.grid, self.phase = mm, mm.grid, phase
+        self._count = torch.zeros(1, dtype=torch.int64, device=_device())
+        n = len(self.rules)
+        self._to = (ctypes.c_int * n)(*[-1 if r is None else r[0] for r in self.rules])
+        self._T_at = (ctypes.c_double * n)(*[0.0 if r is None else r[1] for r in self.rules])
+        self._C = (ctypes.c_double * n)(*[m.rho * m.cp for m in mm.materials])
+        self._mask_version = self._ids_version = None
+        if phase is None:
+            nw = int(lib.adi_phase_summary_words(*self.grid.layout.pd[:3]))
+            if nw <= 0:
+                raise ValueError("MaterialTransitions: bad grid")
+            self.brick_ids = torch.zeros(nw, dtype=torch.int32, device=_device())
+        else:
+            self.brick_ids = phase.brick_ids
+        self.sync_mask()
+
+    @staticmethod
+    def _checked_rules(rules, nmat):
+        """the rules as a tuple of None / (int to, float T_at) after the checks of the constructor (nothing is launched before
+        they pass)"""
+        try:
+            rules = tuple(rules)
+        except TypeError:
+            raise TypeError("MaterialTransitions: rules must be a sequence with one (to, T_at) or None per material")
+        if len(rules) != nmat:
+            raise ValueError("MaterialTransitions: %d rules for %d materials" % (len(rules), nmat))
+        out = []
+        for m, rule in enumerate(rules):
+            if rule is None:
+                out.append(None)
+                continue
+            try:
+                to, T_at = rule
+            except (TypeError, ValueError):
+                raise TypeError("MaterialTransitions: a rule must be (to, T_at) or None, got %r" % (rule,))
+            if isinstance(to, bool) or not isinstance(to, (int, np.integer)):
+                raise TypeError("MaterialTransitions: the new material of a rule must be an int, got %r" % (to,))
+            if not 0 <= int(to) < nmat:
+                raise ValueError("MaterialTransitions: material %d turns into %d, there are %d materials" % (m, to, nmat))
+            if int(to) == m:
+                raise ValueError("MaterialTransitions: material %d turns into itself" % m)
+            try:
+                T_at = float(T_at)
+            except (TypeError, ValueError):
+                raise TypeError("MaterialTransitions: the temperature of a rule must be a real number, got %r" % (T_at,))
+            if not np.isfinite(T_at):
+                raise ValueError("MaterialTransitions: the temperature of the rule of material %d is not finite" % m)
+            out.append((int(to), T_at))
+        return tuple(out)
+
+    def _check_fresh(self):
+        if self.grid.mask_version != self._mask_version or self.mm._ids_version != self._ids_version:
+            raise ValueError("MaterialTransitions: the grid's mask or the MaterialMap's ids changed since the bricks' id sets "
+                             "were built; call sync_mask()")
+        if self.phase is not None:
+            self.phase._check_fresh()
+
+    def sync_mask(self):
+        """after `grid.mask` or the MaterialMap's ids changed (a birth, a deposit, set_ids): the bricks' id sets are rebuilt
+        when this object owns them; with a phase they are the MapPhaseField's, whose own sync_mask(T) comes first"""
+        g = self.grid
+        if self.phase is not None:
+            self.phase._check_fresh()
+        else:
+            check(lib.adi_matmap_brick_sets(_p(g.d_flags), _p(g.d_bricks), _p(self.mm._d_ids), _p(self.brick_ids), *g.layout.pd,
+                                            _stream()))
+        self._mask_version, self._ids_version = g.mask_version, self.mm._ids_version
+
+    @property
+    def changed(self):
+        """the cells changed since construction or reset_count() (synchronises)"""
+        return int(self._count.item())
+
+    def reset_count(self):
+        self._count.zero_()
+
+    def apply(self, T, d_dir_mask=None):
+        """adi_matmap_transition from T (a DeviceField or device tensor in the grid's layout; only read); d_dir_mask: the
+        Dirichlet cells as a uint8 device tensor in the grid's layout (default: those of the map's packs)"""
+        g, mm, ph = self.grid, self.mm, self.phase
+        t = _native_f64(g, T, "MaterialTransitions.apply: T must be a fp64 device field in the grid's layout")
+        self._check_fresh()
+        mm._check_fresh()
+        dm = d_dir_mask
+        if dm is None and mm.packs[2].has_dir:
+            dm = mm.packs[2].d_dir_mask
+        if dm is not None:
+            assert g.layout.is_native(dm) and dm.dtype == torch.uint8
+        laws = on = None
+        if ph is not None:
+            _, laws, on = ph._c_laws()
+        h_specs, q_specs = mm._face_args()
+        check(lib.adi_matmap_transition(len(self.rules), self._to, self._T_at, laws, on, _p(t), _p(mm._d_ids), _p(g.d_flags),
+                                        _p(g.d_bricks), _p(g.d_mask), _p(dm), _p(None if ph is None else ph.f),
+                                        _p(None if ph is None else ph.summary), _p(self.brick_ids), _p(self._count),
+                                        *g.layout.pd, g.dx, self._C, *_face_spec_args(h_specs), *_face_spec_args(q_specs),
+                                        ptr_array([p.d_coeff.data_ptr() for p in mm.packs]),
+                                        ptr_array([p.d_qflux.data_ptr() for p in mm.packs]), _stream()))
+        mm._ids_stamped = True
+        return T
+
+    def snapshot(self):
+        return self.mm._d_ids.clone(), self.brick_ids.clone(), self._count.clone()
+
+    def restore(self, s):
+        """the id field, the words and the counter as they were, and the packs rewritten for those ids (MaterialMap.update over
+        the whole box: one launch, nothing read back)"""
+        self.mm._d_ids.copy_(s[0])
+        self.brick_ids.copy_(s[1])
+        self._count.copy_(s[2])
+        self.mm.update(0, self.grid.layout.pz)
+
+    def graph_key(self):
+        """what a captured launch holds: the rules by value; the id field, the words, the counter and the six pack arrays by
+        pointer; of the phase its laws by value and f and the summary by pointer"""
+        ph = self.phase
+        return (self.rules, self.mm._d_ids.data_ptr(), self.brick_ids.data_ptr(), self._count.data_ptr(),
+                tuple(p.d_coeff.data_ptr() for p in self.mm.packs), tuple(p.d_qflux.data_ptr() for p in self.mm.packs),
+                None if ph is None else (tuple(None if w is None else w.key() for w in ph.laws), ph.f.data_ptr(),
+                                         ph.summary.data_ptr()))
+
+    # ---- the definition in NumPy fp64 -------------------------------------------------------------------------------------
+    @staticmethod
+    def apply_reference(rules, T, f, mask, ids, dir_mask, laws):
+        """(ids_new, f_new, n_changed) of one pass over the field T: THE DEFINITION.  A cell changes exactly when it is in the
+        mask, is not a Dirichlet cell (dir_mask; None: none), its material m has a rule (to, T_at) and T >= T_at -- equality
+        changes it, a NaN does not -- and it changes once: the test is made on the ids the pass found.  f, laws: the liquid
+        fraction and the laws of the MapPhaseField (both None: no phase, f_new is None); a changed cell gets f_eq(T) of the
+        law of its new material (MapPhaseField.f_eq_of's operations), 0 where that has none; every other f is kept."""
+        T = np.asarray(T, dtype=np.float64)
+        mask = np.asarray(mask, dtype=bool)
+        ids = np.asarray(ids)
+        rules = MaterialTransitions._checked_rules(rules, len(rules))
+        free = mask if dir_mask is None else mask & ~np.asarray(dir_mask, dtype=bool)
+        ids_new = np.array(ids)
+        f_new = None if f is None else np.array(f, dtype=np.float64)
+        changed = np.zeros(mask.shape, bool)
+        for m, rule in enumerate(rules):
+            if rule is None:
+                continue
+            to, T_at = rule
+            with np.errstate(invalid='ignore'):
+                hot = T >= T_at
+            of_m = ids == m
+            cells = free & of_m
+            cells = cells & hot
+            ids_new = np.where(cells, np.asarray(to, ids_new.dtype), ids_new)
+            changed = changed | cells
+            if f_new is not None:
+                law = laws[to]
+                fe = np.zeros(T.shape) if law is None else law.f_eq(T)
+                f_new = np.where(cells, fe, f_new)
+        return ids_new, f_new, int(changed.sum())

@@ -271,6 +271,11 @@ class _MapSource:
     `set_block(blk, t0, dt)`, `shape_key()` and `add_r0(R0, params, blk)`."""
 
 
+class _MapTransitions:
+    """What step.py names of matmap_extras.MaterialTransitions: the material changes of a MaterialMap `.mm` with its liquid
+    fraction `.phase` (or None), with `apply(T, d_dir_mask)`, `_check_fresh()`, `snapshot()`, `restore(s)` and `graph_key()`."""
+
+
 class MaterialMap:
     """A grid of several materials: 1 to 8 (rho, cp, k) and a uint8 id per cell.  The step under it couples a cell of material
     m to an in-mask neighbour of material n with the pair-table entry G[m][n] = (kf(m, n) dt) / (C_m dx^2), kf the harmonic

@@ -9,7 +9,7 @@ from . import _lib
 from ._lib import lib, check
 from ._ledger import PromiseLedger
 from .fields import DeviceField, _as_state, _wrap, _p, _stream
-from .packs import _fc_arg, MaterialMap, _MapLoss, _MapPhase, _MapSource
+from .packs import _fc_arg, MaterialMap, _MapLoss, _MapPhase, _MapSource, _MapTransitions
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .surface_loss import LossPacks
 from .phase import PhaseField, NonlinearPacks
@@ -130,28 +130,31 @@ def _ensure_general(pack):
 
 
 class StepExtras:
-    """The eight optional parts of a step in one record: adi_step_hip_coeff and StagedStepper build it from their keywords,
-    _check_extras, _launch_step and StagedStepper.run take it.  A ninth part is a name here (and in `graph_key`), its check in
+    """The nine optional parts of a step in one record: adi_step_hip_coeff and StagedStepper build it from their keywords,
+    _check_extras, _launch_step and StagedStepper.run take it.  A tenth part is a name here (and in `graph_key`), its check in
     _check_extras, its line in _launch_step and its own module.
         recorders   history, solidification, monitor: those present, in the order they launch; each keeps a clock of its own
-        stateful    phase, then the recorders: what a step changes besides the field (run() holds a snapshot of each over its
-                    warm-up steps; `material` is stateless and `surface_loss` is rewritten from the field at every step)"""
+        stateful    phase, transitions, then the recorders: what a step changes besides the field (run() holds a snapshot of
+                    each over its warm-up steps; `material` is stateless and `surface_loss` is rewritten from the field at
+                    every step)"""
     __slots__ = ('source', 'surface_loss', 'phase', 'history', 'material', 'solidification', 'material_map', 'monitor',
-                 'recorders')
+                 'transitions', 'recorders')
 
     def __init__(self, source=None, surface_loss=None, phase=None, history=None, material=None, solidification=None,
-                 material_map=None, monitor=None):
+                 material_map=None, monitor=None, transitions=None):
         self.source, self.surface_loss, self.phase, self.history = source, surface_loss, phase, history
         self.material, self.solidification, self.material_map, self.monitor = material, solidification, material_map, monitor
+        self.transitions = transitions
         self.recorders = [x for x in (history, solidification, monitor) if x is not None]
 
     @property
     def stateful(self):
-        return self.recorders if self.phase is None else [self.phase] + self.recorders
+        return [x for x in (self.phase, self.transitions) if x is not None] + self.recorders
 
     def graph_key(self):
         """What a graph captured by StagedStepper.run holds of the optional parts: one entry each, None for an absent one, in
-        the order below (the monitor's only when there is one: without it the key is what it was before there were monitors).
+        the order below (the monitor's and the transitions' only when there is one: without them the key is what it was before
+        there were any).
         Every launch named here is captured with the step (X -> Y reads X, Y -> X reads Y).
           source: the moving source, corrected after sweep 0 (adi_source_lines0), its time read from a device block whose step
             counter a captured tick advances -- power, origin, velocity, eta and f_f may change between runs without a new graph;
@@ -175,11 +178,20 @@ class StepExtras:
             device block by pointer and ticked in the capture; the extent of its support travels by value (shape_key) and the
             C table by value in the launch, everything else of the source through the block, as for a GoldakSource.
           monitor: the record of the step's OUTPUT buffer and the tick of its block, the last launches of all; probes, regions
-            and weights travel by value and its buffers by pointer."""
+            and weights travel by value and its buffers by pointer.
+          transitions: a MaterialTransitions of the material_map: the change of the id, pack values and f of the cells of the
+            step's OUTPUT buffer that got hot enough (adi_matmap_transition), one launch after the phase's and before the
+            recorders'; the rules travel by value, the id field, the bricks' id sets, the counter, the six pack arrays and the
+            phase's f and summary by pointer.  A transition is not a change of the map's ids in the sense of its version: the
+            graph holds the id field by pointer and replays on."""
         key = (None if self.source is None else self.source.shape_key(),) + tuple(
             None if x is None else x.graph_key()
             for x in (self.surface_loss, self.phase, self.history, self.material, self.solidification, self.material_map))
-        return key if self.monitor is None else key + (self.monitor.graph_key(),)
+        if self.monitor is not None:
+            key += (self.monitor.graph_key(),)
+        if self.transitions is not None:
+            key += (('transitions', self.transitions.graph_key()),)
+        return key
 
 
 def _check_extras(grid, mat, params, packs, extras):
@@ -191,6 +203,7 @@ def _check_extras(grid, mat, params, packs, extras):
     StagedStepper.__init__ does not, and StagedStepper.run checks every recorder."""
     x = extras
     source, surface_loss, phase, material, mm = x.source, x.surface_loss, x.phase, x.material, x.material_map
+    tr = x.transitions
 
     def same_grid(kw, part, cls):
         if part.grid is not grid:
@@ -226,6 +239,17 @@ def _check_extras(grid, mat, params, packs, extras):
         mm._check_fresh()
         if phase is not None:
             phase._check_fresh()
+    if tr is not None:
+        if not isinstance(tr, _MapTransitions):
+            raise TypeError("transitions must be a MaterialTransitions")
+        if mm is None:
+            raise ValueError("transitions: a MaterialTransitions needs material_map= (its MaterialMap's step)")
+        if tr.mm is not mm:
+            raise ValueError("transitions: the MaterialTransitions belongs to another MaterialMap")
+        if tr.phase is not phase:
+            raise ValueError("transitions: the MaterialTransitions' phase is not the step's phase= (the same MapPhaseField in "
+                             "both places, or none in both: a changed cell's liquid fraction is set in the step's own field)")
+        tr._check_fresh()
     if material is not None:
         if not isinstance(material, NonlinearPacks):
             raise TypeError("material must be a NonlinearPacks")
@@ -294,12 +318,16 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, extras, d_S=N
     `extras.source` is a MapSource and the order is: the map's explicit stage, the source added to its output
     (adi_matmap_source_add_r0, the block set just ahead of it when t_set is given), adi_source_tick when captured, sweep 0 -- no
     correction after sweep 0.
-    extras.monitor: a FieldMonitor: its record of `out` and its tick are the last launches of all, after solidification's."""
+    extras.monitor: a FieldMonitor: its record of `out` and its tick are the last launches of all, after solidification's.
+    extras.transitions: a MaterialTransitions of the material_map: its pass over `out` (adi_matmap_transition) follows the
+    latent-heat correction and precedes the recorders, which so record the step's final (T, f, id)."""
     x, mm = extras, extras.material_map
     (ta, tb), _, _ = grid.scratch(2)
     u = t_in                                               # what the linear step runs on
     if mm is not None:
         mm._check_fresh()
+        if x.transitions is not None:
+            x.transitions._check_fresh()                   # (before the first launch, not after the sweeps)
         fused = False
 
         def explicit(dst):
@@ -351,12 +379,14 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, extras, d_S=N
         x.material.recover(t_in, out)
     if x.phase is not None:
         x.phase.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
+    if x.transitions is not None:
+        x.transitions.apply(out, packs[2].d_dir_mask if packs[2].has_dir else None)
     for rec in x.recorders:
         rec._record_step(t_in, out, params.dt, captured)
 
 
 def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, surface_loss=None, phase=None, history=None,
-                       material=None, solidification=None, material_map=None, monitor=None):
+                       material=None, solidification=None, material_map=None, monitor=None, transitions=None):
     """adi3d_numba_coeff.py:290-302 / adi3d_gpu_coeff.py:213-230: explicit stage, then the three
     implicit sweeps in the order axis 0, 1, 2.  Returns a NEW array of the kind it was given;
     `Tn` is never modified.
@@ -395,12 +425,16 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     monitor: a FieldMonitor of the grid (with the step's material_map, if any): the result's value at its probes and the count,
     extrema and sums of its regions become one row of its device log, and its clock moves on by dt (adi_monitor_record and
     adi_history_tick on its block, the last launches of all).  Combines with every other argument.  None: no such launch.
+    transitions: a MaterialTransitions of the material_map (made with the step's `phase`, if any): after the latent-heat correction
+    the in-mask cells of the result that are at or above the threshold of their material's rule change their material -- id, pack
+    values and liquid fraction, at constant temperature (adi_matmap_transition, one launch before the recorders'; DESIGN.md
+    6l4).  Needs material_map=.  None: no such launch.
     Every optional argument is checked before the first launch (_check_extras); the launches are _launch_step's."""
     if isinstance(S, (ScanPath, ScanPathSource)):
         raise TypeError("adi_step_hip_coeff: a scan path enters the step as its field: S=path.sample_step(grid, t, dt) from the "
                         "host, or S=path.on_device().sample_step_device(grid, t, dt) evaluated on the device")
     source = S if isinstance(S, (GoldakSource, _MapSource)) else None
-    extras = StepExtras(source, surface_loss, phase, history, material, solidification, material_map, monitor)
+    extras = StepExtras(source, surface_loss, phase, history, material, solidification, material_map, monitor, transitions)
     _check_extras(grid, mat, params, packs, extras)
     if history is not None:
         history._check_mask()                              # (here and not in _check_extras: see there)
@@ -449,12 +483,15 @@ class StagedStepper:
     which stays the source's time origin) and moves that clock on by nsteps*dt.  With `solidification=` (a SolidificationRecord
     of the grid) its record launch and tick come after those, the last launches of every step, on the recorder's own clock in
     the same way.  With `monitor=` (a FieldMonitor of the grid) its record of the step's output and its tick are the last launches
-    of all, on the monitor's own clock in the same way."""
+    of all, on the monitor's own clock in the same way.  With `transitions=` (a MaterialTransitions of the material_map) its pass
+    follows the latent-heat correction and precedes the recorders; `run` captures it with the step, and its warm-up steps leave
+    ids, packs, f and the bricks' words as they were."""
 
     def __init__(self, grid, mat, params, packs, Tinf=0.0, fused=None, source=None, surface_loss=None, phase=None,
-                 history=None, material=None, solidification=None, material_map=None, monitor=None):
+                 history=None, material=None, solidification=None, material_map=None, monitor=None, transitions=None):
         # the optional parts: what each does in a step and what a captured graph holds of it is written at StepExtras.graph_key
-        self.extras = StepExtras(source, surface_loss, phase, history, material, solidification, material_map, monitor)
+        self.extras = StepExtras(source, surface_loss, phase, history, material, solidification, material_map, monitor,
+                                 transitions)
         _check_extras(grid, mat, params, packs, self.extras)
         self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
         self.captures = 0              # HIP graphs captured by run() so far

@@ -1171,6 +1171,38 @@ int adi_matmap_loss_update(const void *d_table, double Tinf, double min_T_offset
                            double dx, double *const d_coeff[3], int k_begin, int k_end, int full, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Several materials: transitions.  A cell of material m that has a rule (to_m, T_at_m) turns into
+ * material to_m when its temperature is at or above T_at_m: loose powder that reaches its liquidus is dense metal from then
+ * on.  h_to: nmat ints, the new material of m (another one of the nmat) or < 0 for no rule; h_T_at: nmat doubles, finite where
+ * there is a rule and not read elsewhere.  A cell changes exactly when it is in the mask, is not a Dirichlet cell
+ * (d_dir_mask, NULL: none), its material has a rule and T >= T_at (equality changes it, a NaN does not); it changes at most
+ * once per call -- the decision is taken on the id the call found.  A changed cell gets
+ *     its id byte                  to_m
+ *     its six pack values          those of adi_matmap_build_coeffs with the new C (d_mask, the face specs and the six arrays
+ *                                  of that build; no other cell's values depend on this cell's id)
+ *     with a liquid fraction, f    f_eq(T) of the new material's law as adi_matmap_phase_seed evaluates it, 0 without a law
+ * and d_T is never written: the properties switch at constant temperature, so sum C_id V T jumps by (C_to - C_m) V T per cell.
+ * h_laws / h_on / d_f / d_summary: all of them (the arguments of adi_matmap_phase_seed) or all NULL.
+ * d_brick_ids: the id sets of "Several materials: latent heat" (adi_phase_summary_words of them), read FIRST and believed: a
+ * brick whose set holds no material with a rule is left at once; otherwise flags and T of its in-mask cells are read, and the
+ * id bytes only where some cell is at or above the smallest threshold among the set's ruled materials.  The words of a brick
+ * that changed are rewritten for the new ids; with a liquid fraction so is its summary word, by the rule of adi_phase_apply.
+ * d_count: one 64-bit counter on the device, the number of changed cells is added to it (integer atomics, one per brick that
+ * changed something).  One launch, capturable.
+ * ---------------------------------------------------------------------------------------------- */
+int adi_matmap_transition(int nmat, const int *h_to, const double *h_T_at, const adi_phase_change *h_laws, const int *h_on,
+                          const double *d_T, uint8_t *d_ids, const uint8_t *d_flags, const uint32_t *d_bricks,
+                          const uint8_t *d_mask, const uint8_t *d_dir_mask, double *d_f, uint32_t *d_summary,
+                          uint32_t *d_brick_ids, unsigned long long *d_count, int nx, int ny, int nz, long plane_stride,
+                          double dx, const double *h_C, const int *h_mode, const double *h_scalar,
+                          const double *const *d_h_field, const int *q_mode, const double *q_scalar,
+                          const double *const *d_q_field, double *const *d_coeff, double *const *d_qflux, void *stream);
+/* every word of d_brick_ids from d_flags and d_ids (d_bricks: the flags summary, optional): what adi_matmap_phase_seed leaves
+ * there, for a caller that holds no liquid fraction */
+int adi_matmap_brick_sets(const uint8_t *d_flags, const uint32_t *d_bricks, const uint8_t *d_ids, uint32_t *d_brick_ids, int nx,
+                          int ny, int nz, long plane_stride, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Context API: the library owns the device memory; callers hand over HOST arrays.
  * One context per GPU and thread; no hidden global state.
  * ---------------------------------------------------------------------------------------------- */
