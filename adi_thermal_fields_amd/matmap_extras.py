@@ -365,7 +365,8 @@ class MaterialTransitions(_MapTransitions):
     phase is given (no copy; the pass keeps those words exact), an array of the same definition this object owns otherwise
     (adi_matmap_brick_sets).  The object remembers grid.mask_version and the map's id version: after either changed the step
     raises ValueError until sync_mask() (after mph.sync_mask(T) when there is a phase).  A transition itself is no such change:
-    a captured graph holds the id field by pointer.  After a launch `mm.ids` downloads the field.  Needs mm.ids_all_valid.
+    a captured graph holds the id field by pointer.  After a launch `mm.ids` downloads the field, after the replays of
+    StagedStepper.run too (after_replay).  Needs mm.ids_all_valid.
         apply(T, d_dir_mask=None)   the pass on a device field in the grid's layout (T is only read): one launch
         changed / reset_count()     the cells changed since construction or the last reset (reading it synchronises)
         sync_mask()                 see above
@@ -484,6 +485,12 @@ class MaterialTransitions(_MapTransitions):
                                         ptr_array([p.d_qflux.data_ptr() for p in mm.packs]), _stream()))
         mm._ids_stamped = True
         return T
+
+    def after_replay(self):
+        """StagedStepper.run calls this after it replayed a graph that holds this object's pass: the device id field may have
+        changed without a call of apply(), so the map's host copy is stale and `mm.ids` downloads the field when it is read next.
+        Nothing is launched or synchronised here."""
+        self.mm._ids_stamped = True
 
     def snapshot(self):
         return self.mm._d_ids.clone(), self.brick_ids.clone(), self._count.clone()

@@ -273,7 +273,8 @@ class _MapSource:
 
 class _MapTransitions:
     """What step.py names of matmap_extras.MaterialTransitions: the material changes of a MaterialMap `.mm` with its liquid
-    fraction `.phase` (or None), with `apply(T, d_dir_mask)`, `_check_fresh()`, `snapshot()`, `restore(s)` and `graph_key()`."""
+    fraction `.phase` (or None), with `apply(T, d_dir_mask)`, `_check_fresh()`, `snapshot()`, `restore(s)`, `graph_key()` and
+    `after_replay()` (run() replayed a graph that holds the pass: the map's host copy of the ids is stale)."""
 
 
 class MaterialMap:

@@ -574,6 +574,8 @@ class StagedStepper:
             for _ in range(nsteps // 2):
                 st['g'].replay()
             done = 2 * (nsteps // 2)
+            if done and x.transitions is not None:
+                x.transitions.after_replay()               # (no Python ran between the replayed steps: ids changed unseen)
         cur, oth = X, Y
         for _ in range(nsteps - done):
             self._step_into(cur, oth)
