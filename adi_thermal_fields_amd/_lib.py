@@ -170,6 +170,12 @@ SIGNATURES = {
                                      c_double, c_void_p]),
     'adi_scan_sample': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_int, c_int, c_long, c_double, c_double,
                                 c_double, c_void_p, c_void_p]),
+    'adi_scan_window_box': (c_int, [c_void_p, c_void_p, c_int, c_double, c_int, c_int, c_int, c_double, c_double, c_double,
+                                    c_int_p, c_int_p]),
+    'adi_matmap_scan_add_r0': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_int, c_long, c_double, c_double, c_double, c_int, c_double_p, c_int_p, c_void_p]),
+    'adi_matmap_scan_add_r0_host': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                            c_int, c_double, c_double, c_double, c_int, c_double_p, c_int_p]),
     'adi_bead_index_box': (c_int, [c_void_p, c_void_p, c_int, c_double, c_int, c_int, c_int, c_double, c_double, c_double,
                                    c_int_p, c_int_p]),
     'adi_bead_deposit_host': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_int, c_int, c_int, c_double,

@@ -32,7 +32,7 @@ materials in one grid); heat_source.py --
 GoldakSource, ScanPath, ScanPathSource and the one host definition of Goldak's double ellipsoid; deposition.py -- the surface impulse, the
 perimeter ratio, birth_planes, BirthPacks, BeadProfile, PathDeposit (births along a scan path); surface_loss.py -- SurfaceLoss, LossPacks; phase.py -- PhaseChange, PhaseField, MaterialLaw, NonlinearPacks;
 matmap_extras.py -- MapPhaseField, MapLossPacks (latent heat and surface loss with one law per material of a MaterialMap) and
-MapSource (a moving GoldakSource inside the step of a MaterialMap), MaterialTransitions (cells that change their material when
+MapSource (a moving GoldakSource inside the step of a MaterialMap), MapPathSource (a ScanPath inside it), MaterialTransitions (cells that change their material when
 they get hot enough);
 history.py -- HistoryLevels, ThermalHistory, SolidificationRecord; monitor.py -- FieldMonitor (probes, region extrema and sums; it
 imports fields, packs and history, and step.py knows it by history._StepRecorder, the base the three recorders share); step.py --
@@ -52,7 +52,7 @@ from .deposition import (apply_surface_impulse_Q, exposed_faces_per_layer, count
                          BirthPacks, BeadProfile, PathDeposit)
 from .surface_loss import SurfaceLoss, LossPacks
 from .phase import PhaseChange, PhaseField, MaterialLaw, NonlinearPacks
-from .matmap_extras import MapPhaseField, MapLossPacks, MapSource, MaterialTransitions
+from .matmap_extras import MapPhaseField, MapLossPacks, MapSource, MapPathSource, MaterialTransitions
 from .history import HistoryLevels, ThermalHistory, SolidificationRecord
 from .monitor import FieldMonitor
 from .step import (adi_explicit_rhs, adi_sweep_axis, adi_explicit_sweep_axis0, adi_step_hip_coeff, adi_step_numba_coeff,
@@ -65,7 +65,7 @@ __all__ = ['Grid3D', 'Material', 'Params', 'AxisCoeffPack', 'exposed_mask', 'pre
            'exposed_faces_per_layer', 'count_exposed_faces', 'perimeter_ratio', 'birth_planes', 'BirthPacks',
            'GoldakSource', 'ScanPath', 'SurfaceLoss', 'LossPacks', 'PhaseChange', 'PhaseField', 'HistoryLevels',
            'ThermalHistory']
-# (ScanPathSource, BeadProfile, PathDeposit, MaterialLaw, NonlinearPacks, SolidificationRecord, MaterialMap, MapPhaseField, MapLossPacks, MapSource, MaterialTransitions and FieldMonitor are exported like the names above but are not part of the pinned `__all__`)
+# (ScanPathSource, BeadProfile, PathDeposit, MaterialLaw, NonlinearPacks, SolidificationRecord, MaterialMap, MapPhaseField, MapLossPacks, MapSource, MapPathSource, MaterialTransitions and FieldMonitor are exported like the names above but are not part of the pinned `__all__`)
 
 # an assignment to a name above reaches the module that defined it (_facade.ReExporting)
 sys.modules[__name__].__class__ = ReExporting

@@ -204,4 +204,48 @@ inline void scan_sample_host(const adi_scan_shape &h, const double *tab, int K, 
             }
 }
 
+// The window of the step [t, t + dt] as a launch carries it: the segment range and the index box, found on the host
+struct ScanWindow {
+    int k0, k1;
+    ScanBox B;
+};
+inline ScanWindow scan_window_of(const adi_scan_shape &h, const double *tab, int K, double t_end, int nx, int ny, int nz,
+                                 double dx, double t, double dt)
+{
+#pragma clang fp contract(off)
+    ScanWindow W;
+    const double t1 = t + dt;
+    scan_window(tab, K, t, t1, W.k0, W.k1);
+    const int n[3] = {nx, ny, nz};
+    scan_window_box(h, tab, K, t_end, W.k0, W.k1, t, t1, n, dx, W.B);
+    return W;
+}
+
+// One cell of the path added to R0 on a grid of several materials: r + (dt * q_step) / C[id], r itself where q_step is 0 (the
+// caller then writes nothing).  C: the kMapMaxMat = 8 entries, the id masked as everywhere.
+ADI_SCAN_HD bool scan_add_r0_cell(const adi_scan_shape &h, const double *tab, int K, double t_end, int k0, int k1, double t,
+                                  double dt, double dx, int i, int j, int k, const double *C, unsigned id, double &r)
+{
+#pragma clang fp contract(off)
+    const double q = scan_q_step(h, tab, K, t_end, k0, k1, t, t + dt, dt, (i + 0.5) * dx, (j + 0.5) * dx, (k + 0.5) * dx);
+    if (q == 0.0) return false;
+    r = r + (dt * q) / C[id & 7u];
+    return true;
+}
+
+// adi_matmap_scan_add_r0_host's loop over the window's box of dense C-order (nx, ny, nz) host arrays (mask NULL: every cell)
+inline void scan_add_r0_host(const adi_scan_shape &h, const double *tab, int K, double t_end, const ScanWindow &W, double *R0,
+                             const uint8_t *mask, const uint8_t *ids, int ny, int nz, double dx, double t, double dt,
+                             const double *C)
+{
+    for (int i = W.B.lo[0]; i < W.B.hi[0]; ++i)
+        for (int j = W.B.lo[1]; j < W.B.hi[1]; ++j)
+            for (int k = W.B.lo[2]; k < W.B.hi[2]; ++k) {
+                const long p = ((long)i * ny + j) * nz + k;
+                if (mask != nullptr && !mask[p]) continue;
+                double r = R0[p];
+                if (scan_add_r0_cell(h, tab, K, t_end, W.k0, W.k1, t, dt, dx, i, j, k, C, ids[p], r)) R0[p] = r;
+            }
+}
+
 }  // namespace adi

@@ -1,7 +1,7 @@
 """Latent heat and temperature-dependent surface loss on a grid of several materials: `MapPhaseField`, the
 liquid fraction of a MaterialMap's grid under one PhaseChange law per material, and `MapLossPacks`, the MaterialMap's own packs
 rewritten in place by one SurfaceLoss per material; `MapSource`, a moving GoldakSource inside the step of a MaterialMap
-(DESIGN.md section 6l3); and `MaterialTransitions`, cells that change their material when they get hot enough (DESIGN.md section
+(DESIGN.md section 6l3); `MapPathSource`, a ScanPath inside it without a source field; and `MaterialTransitions`, cells that change their material when they get hot enough (DESIGN.md section
 6l4)."""
 import ctypes
 
@@ -11,8 +11,8 @@ import torch
 from . import _lib
 from ._lib import lib, check, ptr_array, FACES
 from .fields import DeviceField, _SeededForMask, _as_state, _device, _native_f64, _p, _stream, _wrap
-from .packs import MaterialMap, _MapLoss, _MapPhase, _MapSource, _MapTransitions, _triples, _face_spec_args
-from .heat_source import GoldakSource, _source_block
+from .packs import MaterialMap, _MapLoss, _MapPhase, _MapSource, _MapPathSource, _MapTransitions, _triples, _face_spec_args
+from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block
 from .surface_loss import SurfaceLoss
 from .phase import PhaseChange
 
@@ -336,6 +336,60 @@ class MapSource(_MapSource):
         blk = _source_block(self)
         self.set_block(blk, t, params.dt)
         self.add_r0(out, params, blk)
+        return _wrap(out, kind)
+
+
+class MapPathSource(_MapPathSource):
+    """A ScanPath for the step of one MaterialMap, without a source field: pass it as `S=` of adi_step_numba_coeff next to
+    `material_map=mm` and `t=`.  src: a ScanPathSource, or a ScanPath, which is frozen here with on_device().  After the map's
+    explicit stage and before sweep 0 one launch adds the step-averaged source of [t, t + dt] to the stage's output,
+        R0 = R0 + (dt * q_step(x; t, dt)) / C[id]     on the in-mask cells of the window's index box,
+    the operations of the field form S=src.sample_step_device(grid, t, dt), in its order, with q_step evaluated in the kernel
+    (adi_matmap_scan_add_r0): the results are equal bit for bit, and neither the field's pass over the grid nor its 8 B/cell in
+    the explicit stage is paid.  The segment range and the box of each step are found on the host from the snapshot's table
+    and travel by value, so these are plain launches only: a StagedStepper refuses it (TypeError), and nothing is replayed.
+    Combines with everything the field form combines with.  `window(t, dt)` is what a step will launch on."""
+
+    def __init__(self, mm, src):
+        if not isinstance(mm, MaterialMap):
+            raise TypeError("MapPathSource: mm must be a MaterialMap")
+        if isinstance(src, ScanPath):
+            src = src.on_device()
+        if not isinstance(src, ScanPathSource):
+            raise TypeError("MapPathSource: src must be a ScanPath or a ScanPathSource, got %s" % type(src).__name__)
+        self.mm, self.grid, self.src = mm, mm.grid, src
+
+    def _h_table(self):
+        """the library's path arguments with the snapshot's HOST table: (shape, table, K, t_end)"""
+        return self.src._path_args(self.src._h_table.ctypes.data)
+
+    def window(self, t, dt):
+        """(k0, k1, ((i0, i1), (j0, j1), (k0', k1'))): the segments [k0, k1) the step [t, t + dt] can overlap and the index box
+        its launch covers, [lo, hi) per axis; the box is all zeros when the step meets no powered piece"""
+        g = self.grid
+        seg, box = (ctypes.c_int * 2)(), (ctypes.c_int * 6)()
+        check(lib.adi_scan_window_box(*self._h_table(), int(g.nx), int(g.ny), int(g.nz), float(g.dx), float(t), float(dt),
+                                      seg, box))
+        return seg[0], seg[1], ((box[0], box[1]), (box[2], box[3]), (box[4], box[5]))
+
+    def add_r0(self, R0, params, t):
+        """R0 (a device tensor in the grid's layout, the explicit stage's output) gains the source of the step [t, t + dt], in
+        place: one launch on the window's box, none when it is empty"""
+        mm, g, s = self.mm, self.grid, self.src
+        _, C = mm._tables(params.dt)
+        shape, h_table, K, t_end = self._h_table()
+        check(lib.adi_matmap_scan_add_r0(shape, h_table, _p(s.d_table), K, t_end, _p(R0),
+                                         _p(g.d_flags), _p(mm._d_ids), *g.layout.pd, g.dx, float(t), params.dt,
+                                         len(mm.materials), C, None, _stream()))
+
+    def explicit_rhs(self, T, params, t=0.0):
+        """R0 of the step that starts at time t (stage entry point): mm.explicit_rhs(T, params) plus this path over [t, t + dt]"""
+        mm, g = self.mm, self.grid
+        mm._check_fresh()
+        x, kind = _as_state(T, g)
+        out = g.layout.empty()
+        mm._explicit_into(x, None, out, params)
+        self.add_r0(out, params, t)
         return _wrap(out, kind)
 
 

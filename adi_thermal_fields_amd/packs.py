@@ -271,6 +271,12 @@ class _MapSource:
     `set_block(blk, t0, dt)`, `shape_key()` and `add_r0(R0, params, blk)`."""
 
 
+class _MapPathSource(_MapSource):
+    """What step.py names of matmap_extras.MapPathSource: a ScanPathSource `.src` for the step of a MaterialMap `.mm`, with
+    `add_r0(R0, params, t)`: plain launches only, the window of the step travels by value from the host (no device block, no
+    graph)."""
+
+
 class _MapTransitions:
     """What step.py names of matmap_extras.MaterialTransitions: the material changes of a MaterialMap `.mm` with its liquid
     fraction `.phase` (or None), with `apply(T, d_dir_mask)`, `_check_fresh()`, `snapshot()`, `restore(s)`, `graph_key()` and

@@ -9,7 +9,7 @@ from . import _lib
 from ._lib import lib, check
 from ._ledger import PromiseLedger
 from .fields import DeviceField, _as_state, _wrap, _p, _stream
-from .packs import _fc_arg, MaterialMap, _MapLoss, _MapPhase, _MapSource, _MapTransitions
+from .packs import _fc_arg, MaterialMap, _MapLoss, _MapPhase, _MapSource, _MapPathSource, _MapTransitions
 from .heat_source import GoldakSource, ScanPath, ScanPathSource, _source_block, _source_work
 from .surface_loss import LossPacks
 from .phase import PhaseField, NonlinearPacks
@@ -194,16 +194,20 @@ class StepExtras:
         return key
 
 
-def _check_extras(grid, mat, params, packs, extras):
+def _check_extras(grid, mat, params, packs, extras, stepper=False):
     """TypeError / ValueError for an optional part of the step that is of the wrong kind or was made for other packs, another
     grid or another cp, and the rules about which parts combine: once per adi_step_hip_coeff call and once per StagedStepper,
     before anything is launched.
     One asymmetry, kept because code that builds a StagedStepper before `sync_mask` works and must go on working: the mask of
     the solidification record is checked here, the history's is not -- adi_step_hip_coeff checks it itself before it launches,
-    StagedStepper.__init__ does not, and StagedStepper.run checks every recorder."""
+    StagedStepper.__init__ does not, and StagedStepper.run checks every recorder.
+    stepper: the caller is a StagedStepper, whose steps a graph may replay: a MapPathSource is refused there."""
     x = extras
     source, surface_loss, phase, material, mm = x.source, x.surface_loss, x.phase, x.material, x.material_map
     tr = x.transitions
+    if stepper and isinstance(source, _MapPathSource):
+        raise TypeError("source: a MapPathSource does not ride a captured graph (the window of each step travels by value from "
+                        "the host in a plain launch); step with adi_step_numba_coeff(..., material_map=mm, S=msrc, t=t)")
 
     def same_grid(kw, part, cls):
         if part.grid is not grid:
@@ -317,7 +321,8 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, extras, d_S=N
     first, and `phase` a MapPhaseField, whose correction of `out` follows sweep 2; the recorders follow as ever.  With it
     `extras.source` is a MapSource and the order is: the map's explicit stage, the source added to its output
     (adi_matmap_source_add_r0, the block set just ahead of it when t_set is given), adi_source_tick when captured, sweep 0 -- no
-    correction after sweep 0.
+    correction after sweep 0.  A MapPathSource takes the same place with one plain launch (adi_matmap_scan_add_r0 on the window
+    of [t_set, t_set + dt], found on the host): no block, no tick, and only adi_step_hip_coeff reaches here with one.
     extras.monitor: a FieldMonitor: its record of `out` and its tick are the last launches of all, after solidification's.
     extras.transitions: a MaterialTransitions of the material_map: its pass over `out` (adi_matmap_transition) follows the
     latent-heat correction and precedes the recorders, which so record the step's final (T, f, id)."""
@@ -356,7 +361,9 @@ def _launch_step(t_in, out, grid, mat, params, packs, Tinf, fused, extras, d_S=N
         _explicit_sweep0_into(u, tb, grid, mat, params, packs[0], Tinf)
     else:
         explicit(ta)
-        if mm is not None and x.source is not None:
+        if isinstance(x.source, _MapPathSource):
+            x.source.add_r0(ta, params, t_set)             # (a plain launch, the window by value: never captured)
+        elif mm is not None and x.source is not None:
             if t_set is not None:
                 x.source.set_block(_source_block(owner), t_set, params.dt)
             x.source.add_r0(ta, params, _source_block(owner))
@@ -421,7 +428,9 @@ def adi_step_hip_coeff(Tn, grid, mat, params, packs, Tinf=0.0, S=None, t=0.0, su
     surface_loss= when that is a MapLossPacks of the map and with phase= when that is a MapPhaseField of the map (one law per
     material: adi_matmap_loss_update first, adi_matmap_phase_apply after sweep 2); not with a GoldakSource object,
     a LossPacks, a PhaseField or material=.  A moving Goldak source goes in wrapped, S=MapSource(mm, src): it is added to the
-    explicit stage's output with each cell's own C (adi_matmap_source_add_r0).  None: the launches of before.
+    explicit stage's output with each cell's own C (adi_matmap_source_add_r0).  A scan path goes in wrapped too,
+    S=MapPathSource(mm, path): its step-averaged source of [t, t + dt] is added in the same place on the window's index box
+    (adi_matmap_scan_add_r0, one plain launch), without the field.  None: the launches of before.
     monitor: a FieldMonitor of the grid (with the step's material_map, if any): the result's value at its probes and the count,
     extrema and sums of its regions become one row of its device log, and its clock moves on by dt (adi_monitor_record and
     adi_history_tick on its block, the last launches of all).  Combines with every other argument.  None: no such launch.
@@ -492,7 +501,7 @@ class StagedStepper:
         # the optional parts: what each does in a step and what a captured graph holds of it is written at StepExtras.graph_key
         self.extras = StepExtras(source, surface_loss, phase, history, material, solidification, material_map, monitor,
                                  transitions)
-        _check_extras(grid, mat, params, packs, self.extras)
+        _check_extras(grid, mat, params, packs, self.extras, stepper=True)
         self.grid, self.mat, self.params, self.packs, self.Tinf = grid, mat, params, packs, float(Tinf)
         self.captures = 0              # HIP graphs captured by run() so far
         self.fused = fused_supported(grid) if fused is None else (bool(fused) and fused_supported(grid))

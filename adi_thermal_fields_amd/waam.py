@@ -502,7 +502,8 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
     material_map: see waam.MAP_DOC, with one more key, wire=m: the id of what the path lays -- a wire of one alloy on a base plate
     of another.  Every deposit writes m into the map's device id field on its newborn cells (PathDeposit(material_map=,
     material_id=)) and the map's packs are rewritten on the planes it changed (MaterialMap.update); nothing is read back.
-    heat=True stays the field form.
+    With heat=True the path enters the map's step itself, S=backend.MapPathSource(mm, path): added to the explicit stage's
+    output on the window's index box, bit for bit what the field gives, without the field.
     on_frame(t, T, active): called after every step with the time reached and NumPy copies (a download; None: none).
     Returns (T_final, active mask, number of ADI steps), all host side, then the final liquid fraction, history_result and
     solidification_result for those that were asked for, in this order, then the monitor's traces() and region_log(mat)."""
@@ -527,6 +528,7 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
                                keys=('materials', 'ids', 'wire'))
         dep = backend.PathDeposit(grid, src, bead, Ts, within=within, material_map=mm, material_id=material_map['wire'])
         mat, packs = mm.mat, mm.packs
+        msrc = backend.MapPathSource(mm, src) if heat else None
     else:
         dep = backend.PathDeposit(grid, src, bead, Ts, within=within)
         bpacks = backend.BirthPacks(grid, mat, robin_h=robin) if surface_loss is None else \
@@ -548,7 +550,7 @@ def run_path_deposition(backend, base_mask, path, bead, dx, mat_args, h, Tinf, T
             live = True
         if live:
             params.dt = d
-            S = src.sample_step_device(grid, t, d) if heat else None
+            S = None if not heat else (msrc if mm is not None else src.sample_step_device(grid, t, d))
             T = backend.adi_step_numba_coeff(T, grid, mat, params, packs, Tinf=Tinf, S=S, t=t, **kw)
             nsteps += 1
         else:

@@ -676,7 +676,8 @@ int adi_explicit_rhs_src(const double *d_T, const double *d_S, const uint8_t *d_
  * memory; the kernels read it only at rows [0, K), K travelling by value in every launch.
  *
  * The step takes the result as a source FIELD (adi_explicit_rhs_src); a correction of sweep 0 from the path itself, as
- * adi_source_lines0 does for the moving source, is not part of the library.
+ * adi_source_lines0 does for the moving source, is not part of the library.  The step of several materials materialises R0
+ * and takes the path itself, added there (adi_matmap_scan_add_r0).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct adi_scan_shape {
     double eta;          /* efficiency */
@@ -697,6 +698,31 @@ int adi_scan_sample_host(const adi_scan_shape *h_shape, const double *h_table, i
  * the K rows in device memory. */
 int adi_scan_sample(const adi_scan_shape *h_shape, const double *d_table, int K, double t_end, const uint8_t *d_flags, int nx,
                     int ny, int nz, long plane_stride, double dx, double t, double dt, double *d_out, void *stream);
+/* The window of the step [t, t + dt] on an (nx, ny, nz) grid, from the host table alone (no HIP call): h_seg_out receives the
+ * segment range { k0, k1 } the step can overlap, h_box_out { i0, i1, j0, j1, k0, k1 }, the union of the index boxes of its
+ * powered pieces as [lo, hi) per axis, all zeros when there is none.  What adi_matmap_scan_add_r0 launches on. */
+int adi_scan_window_box(const adi_scan_shape *h_shape, const double *h_table, int K, double t_end, int nx, int ny, int nz,
+                        double dx, double t, double dt, int *h_seg_out, int *h_box_out);
+/* The path inside the step of a grid of several materials ("Several materials" below), without the field: added to the explicit
+ * stage's output,
+ *     R0_i = R0_i + (dt q_step(x_i; t, dt)) / C_{id_i}     on the in-mask cells of the window's index box,
+ * the operations of adi_matmap_explicit's d_S term, in its order, with q_step evaluated in the kernel at the cell centres
+ * ((i + 1/2) dx, ...).  The segment range [k0, k1) of the window and the union of the index boxes of its powered pieces are
+ * found ON THE HOST from h_table (the K rows in host memory, checked as adi_scan_sample_host checks them) and travel by value
+ * with t and dt in one plain launch, one thread per cell of the box; d_table is the same rows in device memory.  The kernel
+ * reads d_table, d_flags, d_ids (one byte per cell, the material id) and R0 and writes R0: 17 bytes per in-mask cell of the box.
+ * A cell whose q_step is 0 and an off-mask cell are not written.  h_C: C_m = rho_m cp_m of the nmat (1 to ADI_MATMAP_MAX)
+ * materials, finite and > 0.  A window that meets no powered piece launches nothing.  h_box_out (NULL, or six ints): receives
+ * { i0, i1, j0, j1, k0, k1 }, the box as [lo, hi) per axis, all zeros when it is empty.  Every argument is checked before any
+ * HIP call. */
+int adi_matmap_scan_add_r0(const adi_scan_shape *h_shape, const double *h_table, const double *d_table, int K, double t_end,
+                           double *d_R0, const uint8_t *d_flags, const uint8_t *d_ids, int nx, int ny, int nz, long plane_stride,
+                           double dx, double t, double dt, int nmat, const double *h_C, int *h_box_out, void *stream);
+/* The same on the CPU over dense C-order (nx, ny, nz) HOST arrays: h_R0 in place, h_mask 0 / 1 bytes (NULL: every cell is in),
+ * h_ids the id bytes.  No HIP call: the twin of the kernel, as adi_scan_sample_host is of adi_scan_sample. */
+int adi_matmap_scan_add_r0_host(const adi_scan_shape *h_shape, const double *h_table, int K, double t_end, double *h_R0,
+                                const uint8_t *h_mask, const uint8_t *h_ids, int nx, int ny, int nz, double dx, double t,
+                                double dt, int nmat, const double *h_C, int *h_box_out);
 
 /* ------------------------------------------------------------------------------------------------
  * Bead deposition along a scan path: the cells a path brings to life during a step [t, t + dt].  A segment of the table

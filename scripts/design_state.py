@@ -46,6 +46,7 @@ FOOT = [
     ('adi::k_matmap_build_coeffs', 'several materials: the coefficient build'),
     ('adi::k_mapcoeffs_planes', 'several materials (section 6l3): the coefficient build on a range of axis-2 planes'),
     ('adi::k_mapsource_add_r0', 'several materials (section 6l3): a moving Goldak source added to R0, 17 B per in-mask cell of the support'),
+    ('adi::k_mapscan_add_r0', 'several materials (section 6l5): the step-averaged source of a ScanPath added to R0 on the window\'s index box, 17 B per in-mask cell of the box'),
     ('adi::k_maptransition<true, true>', 'several materials (section 6l4): cells change their material at a temperature, with a liquid fraction; 9 B per cell of a brick that holds a ruled material'),
     ('adi::k_maptransition<true, false>', 'the same without a liquid fraction'),
     ('adi::k_mapbricksets<true>', 'several materials (section 6l4): the id set of every brick from flags and ids'),
