@@ -218,6 +218,18 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p]),
     'adi_cyl_step_src': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p]),
     'adi_cyl_sweep_src': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p]),
+    'adi_cyl_phase_apply': (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                    c_long, c_void_p]),
+    'adi_cyl_phase_apply_host': (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                         c_int, c_long]),
+    'adi_cyl_phase_seed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    'adi_cyl_history_record': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int, c_int, c_int, c_long, c_void_p]),
+    'adi_cyl_history_record_host': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_int, c_int, c_long]),
+    'adi_cyl_history_seed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long,
+                                     c_void_p]),
+    'adi_cyl_history_reset_log': (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
     'adi_matmap_build_coeffs': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_int, c_double_p,
                                         c_int_p, c_double_p, c_void_pp, c_int_p, c_double_p, c_void_pp, c_void_pp, c_void_pp,
                                         c_void_p]),
@@ -271,6 +283,7 @@ MATLAW_MAX_KNOTS = 16        # ADI_MATLAW_MAX_KNOTS
 MATMAP_MAX = 8               # ADI_MATMAP_MAX: materials per grid
 HISTORY_BLOCK_BYTES = 40     # ADI_HISTORY_BLOCK_BYTES: { double t0, dt; int64 n, slot, capacity }
 HISTORY_LOG_INTS = 8         # ADI_HISTORY_LOG_INTS: { cells, lo[3], hi[3], pad }
+CYL_HISTORY_LOG_INTS = 12    # ADI_CYL_HISTORY_LOG_INTS: { cells, lo[3], hi[3], pad, int64 sum_i, pad, pad }
 MONITOR_MAX_REGIONS = 8      # ADI_MONITOR_MAX_REGIONS
 MONITOR_MAX_PROBES = 256     # ADI_MONITOR_MAX_PROBES
 MONITOR_REGION_WORDS = 6     # ADI_MONITOR_REGION_WORDS: { cells, T_min, T_max, sum_T, sum_wT, sum_extra }

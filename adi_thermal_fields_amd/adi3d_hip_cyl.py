@@ -17,8 +17,12 @@ from . import _lib
 from ._lib import lib, check
 from .fields import DeviceField, Layout, to_device, _device, _stream, _p, _as_state, _wrap
 from .heat_source import goldak_shape, goldak_q, _source_block
+from .phase import PhaseChange
+from .history import HistoryLevels
+from .cyl_extras import CylPhaseField, CylThermalHistory
 
-__all__ = ['StagedCylStepper', 'CylGoldakSource', 'GridCyl', 'Material', 'Params', 'RobinR', 'ZBC', 'adi_step', 'adi_step_masked', 'DeviceField', 'to_device']
+__all__ = ['StagedCylStepper', 'CylGoldakSource', 'GridCyl', 'Material', 'Params', 'RobinR', 'ZBC', 'adi_step', 'adi_step_masked', 'DeviceField', 'to_device',
+           'CylPhaseField', 'CylThermalHistory', 'PhaseChange', 'HistoryLevels']
 
 
 class GridCyl:  # adi3d_cyl_phi_v3.py:33-43
@@ -185,12 +189,38 @@ def _plan(grid, mat, dt, robin_r, zbc):
     return pl
 
 
-def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None):
+def _check_extras(who, grid, phase, history):
+    """TypeError for an object of the wrong type, ValueError for one built for another grid: before the first launch"""
+    if phase is not None and not isinstance(phase, CylPhaseField):
+        raise TypeError("%s: phase must be a CylPhaseField" % who)
+    if history is not None and not isinstance(history, CylThermalHistory):
+        raise TypeError("%s: history must be a CylThermalHistory" % who)
+    for name, obj in (('phase', phase), ('history', history)):
+        if obj is not None and obj.grid is not grid:
+            raise ValueError("%s: %s was built for another grid" % (who, name))
+
+
+def _zbc_skips(zbc):
+    """(skip_k0, skip_kN) of CylPhaseField.apply: the planes the z sweep pins"""
+    return zbc.kind_bot == 'dirichlet', zbc.kind_top == 'dirichlet'
+
+
+def _extras(x, out, prm, zbc, d_act, phase, history):
+    """what follows the sweeps of a plain step x -> out: the latent-heat pass on out, then the record of (x, out)"""
+    if phase is not None:
+        skip_k0, skip_kN = _zbc_skips(zbc)
+        phase.apply(out, T_in=x, active=d_act, skip_k0=skip_k0, skip_kN=skip_kN)
+    if history is not None:
+        history._record_step(x, out, prm.dt, captured=False, d_act=d_act)
+
+
+def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None, phase=None, history=None):
     # adi3d_cyl_phi_v3.py:335: `scheme = prm.scheme if prm.scheme in ('be', 'douglas') else 'be'` -- every string but
     # 'douglas' is backward Euler in the reference, and so it is here
     if prm.scheme == "douglas":
         raise NotImplementedError("adi3d_hip_cyl does not serve scheme='douglas': the reference's branch is numerically "
                                   "broken (reads uninitialised memory, omits alpha), so it has no valid oracle")
+    _check_extras('adi_step' if active is None else 'adi_step_masked', grid, phase, history)
     src = S if isinstance(S, CylGoldakSource) else None
     if src is not None and t is None:
         raise ValueError("t (the step's start time) is required when S is a CylGoldakSource")
@@ -202,10 +232,12 @@ def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None):
         blk = _source_block(grid)
         src.set_block(blk, t, prm.dt)
         check(lib.adi_cyl_step_src(pl.handle, _p(blk), _p(x), _p(out), _p(d_act), float(T_void), float(T_inner), _stream()))
+        _extras(x, out, prm, zbc, d_act, phase, history)
         return _wrap(out, kind)
     d_S = None if S is None else grid.layout.to_layout(S, torch.float64)
     check(lib.adi_cyl_step(pl.handle, _p(x), _p(out), None, None, _p(d_S), _p(d_act),
                            float(T_void), float(T_inner), _stream()))
+    _extras(x, out, prm, zbc, d_act, phase, history)
     return _wrap(out, kind)
 
 
@@ -214,18 +246,24 @@ class StagedCylStepper:
     `events`: optional list of 4 torch.cuda.Event recorded on the launch stream before / between / after the r, phi
     and z sweeps (adi_cyl_sweep of the C ABI).
     source: a CylGoldakSource, evaluated in the r sweep's load at each step's mid-time from a device block (adi_cyl_sweep_src)
-    whose step counter the z sweep advances; None issues the launches of a plain step."""
+    whose step counter the z sweep advances; None issues the launches of a plain step.
+    phase (a CylPhaseField of this grid): the latent-heat pass follows the z sweep, the planes a 'dirichlet' closure pins left
+    alone.  history (a CylThermalHistory of this grid): the record of every step follows that, at the recorder's own clock; the
+    record needs the step's input, so `run` then steps between two persistent fields instead of in place."""
     stage_names = ['sweep_r', 'sweep_phi', 'sweep_z_contig']
     stage_bytes_per_cell = [16.0, 16.0, 16.0]          # SURVEY.md 8(d): field in + field out per sweep
 
-    def __init__(self, grid, mat, prm, robin_r, zbc, source=None):
+    def __init__(self, grid, mat, prm, robin_r, zbc, source=None, phase=None, history=None):
         if prm.scheme == "douglas":
             raise NotImplementedError("scheme='douglas' has no valid oracle (see adi_step)")
         if source is not None and not isinstance(source, CylGoldakSource):
             raise TypeError("StagedCylStepper: source must be a CylGoldakSource (pass a source field to adi_step)")
+        _check_extras('StagedCylStepper', grid, phase, history)
         self.grid = grid
         self.dt = float(prm.dt)
         self.plan = _plan(grid, mat, prm.dt, robin_r, zbc)
+        self.phase, self.history = phase, history
+        self._skips = _zbc_skips(zbc)
         self.source = source
         self.captures = 0
         if source is not None:
@@ -247,8 +285,17 @@ class StagedCylStepper:
         if self.source is not None:
             self.source.set_block(_source_block(self), t, self.dt)
         out = g.layout.empty()
-        self._sweeps(g.layout.to_layout(T, torch.float64), out, events)
+        self._step_into(g.layout.to_layout(T, torch.float64), out, events, captured=False)
         return DeviceField(out)
+
+    def _step_into(self, x, out, events=None, captured=True):
+        """the launches of one step x -> out (two fields): the sweeps, the latent-heat pass on out with newborn cells seeded
+        from x, the record of (x, out) and the tick.  captured: a graph may replay them and `run` keeps the recorder's clock"""
+        self._sweeps(x, out, events)
+        if self.phase is not None:
+            self.phase.apply(out, T_in=x, skip_k0=self._skips[0], skip_kN=self._skips[1])
+        if self.history is not None:
+            self.history._record_step(x, out, self.dt, captured)
 
     def _sweeps(self, x, out, events):
         """the launches of one step: the r sweep x -> out, then the phi and z sweeps in place on out (out may be x)"""
@@ -265,6 +312,8 @@ class StagedCylStepper:
         """one step on x in place (native-layout device tensor), no allocation: what a HIP graph captures.
         events: as in step()"""
         self._sweeps(x, x, events)
+        if self.phase is not None:                     # (nothing to seed from: `run` seeds the newborn cells before the loop)
+            self.phase.apply(x, skip_k0=self._skips[0], skip_kN=self._skips[1])
 
     def run(self, T, nsteps, graph=True, t0=0.0):
         """`nsteps` BE steps with the same plan on a device-resident field (the drivers' inner loops,
@@ -274,20 +323,42 @@ class StagedCylStepper:
         launches of one step are captured once into a HIP graph and replayed.  Bit-identical to calling step() nsteps
         times.  graph=False: plain launches.
         t0: time at the start of the first step (a source's step i runs at t0 + i*dt + dt/2).  The source's block is written
-        here, so its parameters as they are now hold for this run; a change of its support's shape recaptures."""
+        here, so its parameters as they are now hold for this run; a change of its support's shape recaptures.
+        With a `phase` its launch follows the z sweep, in place as well.  With a `history` the step's input must survive the
+        step: see _run_recorded."""
         g = self.grid
         nsteps = int(nsteps)
         st = getattr(self, '_graph', None)
-        key = None if self.source is None else self.source.shape_key()
+        key = (None if self.source is None else self.source.shape_key(),
+               None if self.phase is None else self.phase.graph_key(),
+               None if self.history is None else self.history.graph_key())
         if st is None or st.get('key') != key:
-            st = self._graph = dict(X=g.layout.empty(), g=None, key=key)
+            st = self._graph = dict(X=g.layout.empty(), Y=None if self.history is None else g.layout.empty(), g=None, key=key)
         X = st['X']
         X.copy_(g.layout.to_layout(T, torch.float64))
         if self.source is not None:
             self.source.set_block(_source_block(self), t0, self.dt)
+        if self.history is not None:
+            return self._run_recorded(st, T, nsteps, graph, t0)
+        if self.phase is not None:
+            # the loop steps in place and so has no input to seed a newborn cell from: every cell the phase field has never
+            # seen active is seeded here, from the field the first step starts with -- what step() would seed it from (the
+            # planes the z sweep pins excepted, as there).  Looked for once per seed / restore of the phase field, not per run.
+            if getattr(self, '_nan_free_at', None) != self.phase._edits:
+                newborn = torch.isnan(self.phase.f)
+                if self._skips[0]:
+                    newborn[:, :, 0] = False
+                if self._skips[1]:
+                    newborn[:, :, -1] = False
+                if bool(newborn.any().item()):
+                    self.phase.seed(X, sel=newborn)
+                self._nan_free_at = self.phase._edits
         if graph and nsteps >= 2 and st['g'] is None:
+            held = None if self.phase is None else self.phase.snapshot()
             self._step_inplace(X)                          # warm-up outside the capture (lazy module loads)
             X.copy_(g.layout.to_layout(T, torch.float64))
+            if held is not None:
+                self.phase.restore(held)
             torch.cuda.synchronize()
             cg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(cg):
@@ -305,20 +376,65 @@ class StagedCylStepper:
         out.copy_(X)
         return DeviceField(out)
 
+    def _run_recorded(self, st, T, nsteps, graph, t0):
+        """`run` with a history: the record needs the step's input, so the loop keeps two persistent fields -- r sweep X -> Y,
+        phi and z in place on Y, the latent-heat pass on Y, the record of (X, Y) and the tick, then the roles swap.  The launches
+        of two steps (X -> Y -> X) are captured once and replayed, an odd last step is launched plainly: no per-step copy of the
+        field, and the bits of step() called nsteps times.  The recorder's block is set from the recorder's own clock."""
+        g, hist = self.grid, self.history
+        X, Y = st['X'], st['Y']
+        stateful = [s for s in (self.phase, hist) if s is not None]
+        if graph and nsteps >= 2 and st['g'] is None:
+            held = [s.snapshot() for s in stateful]        # (the warm-up steps would advance f, the state, the log and the clock)
+            hist.set_clock(self.dt)
+            self._step_into(X, Y); self._step_into(Y, X)   # warm-up outside the capture (lazy module loads)
+            X.copy_(g.layout.to_layout(T, torch.float64))
+            for s, snap in zip(stateful, held):
+                s.restore(snap)
+            torch.cuda.synchronize()
+            cg = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(cg):
+                self._step_into(X, Y)
+                self._step_into(Y, X)
+            st['g'] = cg
+            self.captures += 1
+            if self.source is not None:
+                self.source.set_block(_source_block(self), t0, self.dt)   # (after the warm-up: the counter starts at 0)
+        hist.set_clock(self.dt)
+        done = 0
+        if graph and st['g'] is not None:
+            for _ in range(nsteps // 2):
+                st['g'].replay()
+            done = 2 * (nsteps // 2)
+        cur, oth = X, Y
+        for _ in range(nsteps - done):
+            self._step_into(cur, oth)
+            cur, oth = oth, cur
+        hist.advance_clock(hist.t, self.dt, nsteps)
+        out = g.layout.empty()
+        out.copy_(cur)
+        return DeviceField(out)
 
-def adi_step(Tn, grid, mat, prm, robin_r, zbc, S=None, theta=None, t=None):
+
+def adi_step(Tn, grid, mat, prm, robin_r, zbc, S=None, theta=None, t=None, phase=None, history=None):
     """adi3d_cyl_phi_v3.py:332-350 (BE branch: r -> phi -> z with theta = 1; `theta` is unused there too).
     S: a source field [W/m^3] of the grid's shape (the reference's argument), or a CylGoldakSource evaluated at t + dt/2 in
-    the r sweep's load -- then `t`, the step's start time, is required."""
-    return _run(Tn, grid, mat, prm, robin_r, zbc, S, None, 0.0, 0.0, t)
+    the r sweep's load -- then `t`, the step's start time, is required.
+    phase (a CylPhaseField of this grid): after the sweeps the latent-heat correction of the result, the planes a 'dirichlet'
+    closure of `zbc` pins left alone.  history (a CylThermalHistory of this grid): then the record of the step Tn -> result at
+    the recorder's own clock.  Both None: the launches and the bits of the call without them."""
+    return _run(Tn, grid, mat, prm, robin_r, zbc, S, None, 0.0, 0.0, t, phase, history)
 
 
-def adi_step_masked(Tn, grid, mat, prm, robin_outer, zbc, active, robin_inner=None, robin_void=None, S=None, t=None):
+def adi_step_masked(Tn, grid, mat, prm, robin_outer, zbc, active, robin_inner=None, robin_void=None, S=None, t=None,
+                    phase=None, history=None):
     """quick_spiral_deposition_gif_v5.py:31-70: void cells clamped to robin_void.T_inf before and after
     the step, inactive axis-row cells to robin_inner.T_inf; the clamps are fused into the r-sweep load
     and the z-sweep store.
     S: a CylGoldakSource (q(t + dt/2) added on active cells only; `t` required), or a source field added to the clamped
-    field as adi_step(T_work, S=S) adds it."""
+    field as adi_step(T_work, S=S) adds it.
+    phase, history: as in adi_step, on the active cells; a cell that `active` holds for the first time is seeded from Tn (which
+    equals the clamped field on every active cell), so an activation needs no call."""
     robin_inner = robin_inner or robin_outer
     robin_void = robin_void or robin_outer
-    return _run(Tn, grid, mat, prm, robin_outer, zbc, S, active, robin_void.T_inf, robin_inner.T_inf, t)
+    return _run(Tn, grid, mat, prm, robin_outer, zbc, S, active, robin_void.T_inf, robin_inner.T_inf, t, phase, history)

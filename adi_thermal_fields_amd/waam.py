@@ -116,11 +116,13 @@ def _is_device_backend(backend):
     return hasattr(backend, 'to_device')
 
 
-def _require_device_loop(who, backend, dev_loop, **asked):
-    """ValueError for an option (name = value) that is set where the loop cannot serve it"""
+def _require_device_loop(who, backend, dev_loop, classes=None, **asked):
+    """ValueError for an option (name = value) that is set where the loop cannot serve it.  classes: {option: the backend's
+    class that serves it} where that is not the Cartesian one"""
     for name, cls in (('surface_loss', 'LossPacks'), ('phase_change', 'PhaseField'), ('history', 'ThermalHistory'),
                       ('material_law', 'NonlinearPacks'), ('solidification', 'SolidificationRecord'),
                       ('monitor', 'FieldMonitor'), ('material_map', 'MaterialMap')):
+        cls = (classes or {}).get(name, cls)
         if asked.get(name) is not None and not (dev_loop and hasattr(backend, cls)):
             raise ValueError("%s: %s needs the device loop of a backend with %s" % (who, name, cls))
 
@@ -570,7 +572,7 @@ def ring_source(heat_source, R_in, wall, z_top, tau):
 
 
 def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_side, h_end, z_back, layer_h, n_layers, tau,
-                          nr, nphi, heat_source=None, device_resident=True):
+                          nr, nphi, heat_source=None, device_resident=True, phase_change=None, history=None):
     """The ring-by-ring deposition loop of quick_spiral_deposition_gif_v5.py on an annular wall (R_in, R_in + wall): one
     z-cell per layer, nphi cells per turn, dt = tau / nphi, BE.  Before each step the arc swept during it is activated at Tdep
     in whole radial columns, then adi_step_masked advances the field (Robin h_side on the outer wall, neumann0 below, Robin
@@ -578,7 +580,11 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
     heat_source (a CylGoldakSource of the backend): the arc as a moving volumetric source on the ring being deposited
     (ring_source; the ring's top z, a new one when a layer completes), on active cells, during the steps that deposit; None:
     the reference's loop.  With a device backend and device_resident, T and the active mask stay in HBM and an arc's
-    activation is two slice assignments.  Returns (grid, fields, masks): NumPy (nr, nphi, nz) fields and masks at `times`."""
+    activation is two slice assignments.  Returns (grid, fields, masks): NumPy (nr, nphi, nz) fields and masks at `times`.
+    phase_change (a PhaseChange) / history (HistoryLevels): latent heat and the thermal history, device loop only.  One
+    CylPhaseField / CylThermalHistory of the backend lives through the run (the log holds one row per step) and goes to every
+    adi_step_masked; a newborn column is seeded by the step that first sees it active, so an activation needs no call.  Then
+    the liquid fraction (NumPy, 0 where never active) and / or history_result's dict follow the three usual values."""
     dr = wall / nr
     nz = int(round((z_back + layer_h * n_layers) / layer_h))
     grid = backend.GridCyl(nr, nphi, nz, dr, 2.0 * math.pi / nphi, layer_h, R_in + wall, R_in=R_in)
@@ -590,6 +596,19 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
     active = np.zeros((nr, nphi, nz), bool)
     active[:, :, :iz0] = True
     dev = device_resident and _is_device_backend(backend)
+    _require_device_loop('run_spiral_deposition', backend, dev, classes=dict(phase_change='CylPhaseField', history='CylThermalHistory'),
+                         phase_change=phase_change, history=history)
+    ph = hist = None
+    if phase_change is not None:
+        ph = backend.CylPhaseField(grid, m, phase_change, active=active)
+    if history is not None:
+        rows, tt = 0, 0.0
+        for t_goal in times:                      # the steps of the loop below, counted with its own arithmetic
+            while tt < t_goal - 1e-12:
+                tt = min(tt + tau / nphi, t_goal)
+                rows += 1
+        hist = backend.CylThermalHistory(grid, history, capacity=max(1, rows), T=T, t=0.0, active=active)
+    extras = {k: v for k, v in (('phase', ph), ('history', hist)) if v is not None}
     if dev:                                       # T and the mask in HBM: an activation is two slice assignments
         import torch
         T = grid.layout.to_layout(T, torch.float64)           # (a native-layout tensor in, a tensor out of every step)
@@ -625,10 +644,11 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
                         layer = n_layers
             prm.dt = t_next - t
             if src is None:
-                T = backend.adi_step_masked(T, grid, m, prm, wall_bc, zbc, active, robin_inner=wall_bc, robin_void=wall_bc)
+                T = backend.adi_step_masked(T, grid, m, prm, wall_bc, zbc, active, robin_inner=wall_bc, robin_void=wall_bc,
+                                            **extras)
             else:
                 T = backend.adi_step_masked(T, grid, m, prm, wall_bc, zbc, active, robin_inner=wall_bc, robin_void=wall_bc,
-                                            S=src, t=t)
+                                            S=src, t=t, **extras)
             if not dev:
                 T = np.asarray(T).copy()
             t = t_next
@@ -638,7 +658,12 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
         else:
             fields.append(T.copy())
             masks.append(active.copy())
-    return grid, fields, masks
+    more = ()
+    if ph is not None:
+        more += (np.asarray(ph.liquid_fraction),)
+    if hist is not None:
+        more += (history_result(hist),)
+    return (grid, fields, masks) + more
 
 
 def run_layer_birth_slab(comm, i0, i1, mask_full, dx, mat, params_cls, h, Tinf, Ts, theta, cfl, layers, times_birth,

@@ -1229,6 +1229,63 @@ int adi_matmap_brick_sets(const uint8_t *d_flags, const uint32_t *d_bricks, cons
                           int ny, int nz, long plane_stride, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Latent heat and thermal history of the cylindrical step (no counterpart in the reference; both are rules applied around one
+ * of its steps).  The laws are the Cartesian ones ("Latent heat", "Thermal history" above); the conventions are the cylindrical
+ * backend's: fields in the (nr, nphi, nz) layout, cell (i, j, k) at i*plane_stride + j*nz + k (plane_stride 0: nphi*nz),
+ * d_active an optional byte per cell in the same layout (non-zero: active; NULL: every cell is active), no flags, no bricks
+ * and no state to synchronise: a NaN in the state marks a cell that has never been seen active, and the first pass that sees
+ * it active seeds it from the step's input d_T_in (a birth needs no call).  Inactive cells are never written.
+ *
+ * adi_cyl_phase_apply, per active cell, d_T (the step's result T*) and d_f in place, in this order:
+ *     on plane k = 0 with skip_k0, or k = nz - 1 with skip_kN (the z sweep's Dirichlet rows):  nothing is written
+ *     f is NaN (a newborn):  f = min(max((T_in - Ts)/dT, 0), 1), stored even if the cell is then at rest
+ *     then the correction of adi_phase_apply with its rest-state rule
+ * every operation IEEE fp64 in that order, no contraction.  d_T_in (NULL: nothing is seeded) is required with d_active and is
+ * loaded only by threads that hold a newborn.  A value is stored only where its bits change.  The pass reads 1 + 8 + 8 bytes
+ * per cell; there is no summary word and no tile skip.
+ *
+ * adi_cyl_history_record, per active cell, for the step A = d_T_in (at t_n) -> B = d_T_out (at t_n + dt):
+ *     T_peak is NaN (a newborn):  T_peak = A, t_hi = t_lo = NaN
+ *     then rules 1 - 3 of adi_history_record
+ * A is loaded only where not (T_peak <= T_lo) -- true for NaN -- which is exact under that recorder's precondition A <= T_peak.
+ * The clock is a block of the thermal history's layout (ADI_HISTORY_BLOCK_BYTES, adi_history_set_clock, adi_history_tick).
+ * The log is (capacity + 1) rows of ADI_CYL_HISTORY_LOG_INTS 32-bit integers { cells, lo[3], hi[3], pad, sum_i (int64 at
+ * integers 8 and 9), pad, pad }, 8-byte aligned; a step writes row min(slot, capacity) with integer atomics (add / min / max),
+ * so the row does not depend on the order of the workgroups.  cells, lo and hi are over the active cells with B >= T_melt as
+ * (i, j, k); sum_i is the sum of their radial index i, which makes dphi*dz*dr*((r_in + dr/2)*cells + dr*sum_i) the exact
+ * volume of the pool.  An empty row is { 0, INT32_MAX x 3, -1 x 3, 0, 0, 0, 0, 0 }.
+ *
+ * The *_host functions are the same loops over HOST arrays in the same layout with the same per-cell code; they make no HIP
+ * call and run on a machine without a GPU.  adi_cyl_history_record_host reads the clock from h_block (a host copy of the
+ * block), accumulates into the row of h_log that block names and does not tick.
+ * Valid: what the Cartesian passes require of the law and the levels; nr <= 65535, nphi*nz < 2^31; no null array, d_f not
+ * aliasing d_T, no state array aliasing a field or another state array.  Everything else is ADI_ERR_ARG, checked before any
+ * HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADI_CYL_HISTORY_LOG_INTS 12
+int adi_cyl_phase_apply(const adi_phase_change *h_law, double cp, double *d_T, double *d_f, const double *d_T_in,
+                        const uint8_t *d_active, int skip_k0, int skip_kN, int nr, int nphi, int nz, long plane_stride,
+                        void *stream);
+int adi_cyl_phase_apply_host(const adi_phase_change *h_law, double cp, double *h_T, double *h_f, const double *h_T_in,
+                             const uint8_t *h_active, int skip_k0, int skip_kN, int nr, int nphi, int nz, long plane_stride);
+/* f = f_eq(T) on the active cells d_sel selects (uint8, the same layout; NULL: every active cell), NaN on inactive cells;
+ * active cells not selected keep f */
+int adi_cyl_phase_seed(const adi_phase_change *h_law, const double *d_T, double *d_f, const uint8_t *d_active,
+                       const uint8_t *d_sel, int nr, int nphi, int nz, long plane_stride, void *stream);
+int adi_cyl_history_record(const adi_history_levels *h_levels, const void *d_block, const double *d_T_in,
+                           const double *d_T_out, double *d_peak, double *d_t_hi, double *d_t_lo, int32_t *d_log,
+                           const uint8_t *d_active, int nr, int nphi, int nz, long plane_stride, void *stream);
+int adi_cyl_history_record_host(const adi_history_levels *h_levels, const void *h_block, const double *h_T_in,
+                                const double *h_T_out, double *h_peak, double *h_t_hi, double *h_t_lo, int32_t *h_log,
+                                const uint8_t *h_active, int nr, int nphi, int nz, long plane_stride);
+/* T_peak = T, t_hi = t_lo = NaN on the active cells d_sel selects (NULL: every active cell); all three NaN on inactive cells;
+ * active cells not selected keep their state */
+int adi_cyl_history_seed(const double *d_T, double *d_peak, double *d_t_hi, double *d_t_lo, const uint8_t *d_active,
+                         const uint8_t *d_sel, int nr, int nphi, int nz, long plane_stride, void *stream);
+/* every one of the capacity + 1 rows of d_log empty; the block: slot = 0, n = 0, `capacity`; t0 and dt stay */
+int adi_cyl_history_reset_log(void *d_block, int32_t *d_log, long capacity, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Context API: the library owns the device memory; callers hand over HOST arrays.
  * One context per GPU and thread; no hidden global state.
  * ---------------------------------------------------------------------------------------------- */
