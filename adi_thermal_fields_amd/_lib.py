@@ -230,6 +230,11 @@ SIGNATURES = {
     'adi_cyl_history_seed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long,
                                      c_void_p]),
     'adi_cyl_history_reset_log': (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
+    'adi_cyl_monitor_record': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_double,
+                                       c_int, c_int_p, c_int, c_int_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p]),
+    'adi_cyl_monitor_record_host': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double,
+                                            c_double, c_int, c_int_p, c_int, c_int_p, c_void_p, c_long]),
+    'adi_cyl_monitor_reset_log': (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p]),
     'adi_matmap_build_coeffs': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_int, c_double_p,
                                         c_int_p, c_double_p, c_void_pp, c_int_p, c_double_p, c_void_pp, c_void_pp, c_void_pp,
                                         c_void_p]),
@@ -288,6 +293,8 @@ MONITOR_MAX_REGIONS = 8      # ADI_MONITOR_MAX_REGIONS
 MONITOR_MAX_PROBES = 256     # ADI_MONITOR_MAX_PROBES
 MONITOR_REGION_WORDS = 6     # ADI_MONITOR_REGION_WORDS: { cells, T_min, T_max, sum_T, sum_wT, sum_extra }
 MONITOR_PARTIAL_WORDS = 6    # ADI_MONITOR_PARTIAL_WORDS
+CYL_MONITOR_REGION_WORDS = 8   # ADI_CYL_MONITOR_REGION_WORDS: { cells, sum_i, T_min, T_max, sum_T, sum_rT, sum_extra, sum_rextra }
+CYL_MONITOR_PARTIAL_WORDS = 5  # ADI_CYL_MONITOR_PARTIAL_WORDS
 BRICK = 16                # kBrick (csrc/adi_cart_dev.hpp): the edge of a brick of the flags summary
 STLCORR_DROPPED = (1 << 63) - 1   # ADI_STLCORR_DROPPED
 STLCORR_MAX_SUBDIV = 4096    # ADI_STLCORR_MAX_SUBDIV

@@ -20,9 +20,10 @@ from .heat_source import goldak_shape, goldak_q, _source_block
 from .phase import PhaseChange
 from .history import HistoryLevels
 from .cyl_extras import CylPhaseField, CylThermalHistory
+from .cyl_monitor import CylFieldMonitor
 
 __all__ = ['StagedCylStepper', 'CylGoldakSource', 'GridCyl', 'Material', 'Params', 'RobinR', 'ZBC', 'adi_step', 'adi_step_masked', 'DeviceField', 'to_device',
-           'CylPhaseField', 'CylThermalHistory', 'PhaseChange', 'HistoryLevels']
+           'CylPhaseField', 'CylThermalHistory', 'PhaseChange', 'HistoryLevels', 'CylFieldMonitor']
 
 
 class GridCyl:  # adi3d_cyl_phi_v3.py:33-43
@@ -189,13 +190,15 @@ def _plan(grid, mat, dt, robin_r, zbc):
     return pl
 
 
-def _check_extras(who, grid, phase, history):
+def _check_extras(who, grid, phase, history, monitor=None):
     """TypeError for an object of the wrong type, ValueError for one built for another grid: before the first launch"""
     if phase is not None and not isinstance(phase, CylPhaseField):
         raise TypeError("%s: phase must be a CylPhaseField" % who)
     if history is not None and not isinstance(history, CylThermalHistory):
         raise TypeError("%s: history must be a CylThermalHistory" % who)
-    for name, obj in (('phase', phase), ('history', history)):
+    if monitor is not None and not isinstance(monitor, CylFieldMonitor):
+        raise TypeError("%s: monitor must be a CylFieldMonitor" % who)
+    for name, obj in (('phase', phase), ('history', history), ('monitor', monitor)):
         if obj is not None and obj.grid is not grid:
             raise ValueError("%s: %s was built for another grid" % (who, name))
 
@@ -205,22 +208,25 @@ def _zbc_skips(zbc):
     return zbc.kind_bot == 'dirichlet', zbc.kind_top == 'dirichlet'
 
 
-def _extras(x, out, prm, zbc, d_act, phase, history):
-    """what follows the sweeps of a plain step x -> out: the latent-heat pass on out, then the record of (x, out)"""
+def _extras(x, out, prm, zbc, d_act, phase, history, monitor=None):
+    """what follows the sweeps of a plain step x -> out: the latent-heat pass on out, the record of (x, out), then the monitor's
+    row from out"""
     if phase is not None:
         skip_k0, skip_kN = _zbc_skips(zbc)
         phase.apply(out, T_in=x, active=d_act, skip_k0=skip_k0, skip_kN=skip_kN)
     if history is not None:
         history._record_step(x, out, prm.dt, captured=False, d_act=d_act)
+    if monitor is not None:
+        monitor._record_step(x, out, prm.dt, captured=False, d_act=d_act)
 
 
-def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None, phase=None, history=None):
+def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None, phase=None, history=None, monitor=None):
     # adi3d_cyl_phi_v3.py:335: `scheme = prm.scheme if prm.scheme in ('be', 'douglas') else 'be'` -- every string but
     # 'douglas' is backward Euler in the reference, and so it is here
     if prm.scheme == "douglas":
         raise NotImplementedError("adi3d_hip_cyl does not serve scheme='douglas': the reference's branch is numerically "
                                   "broken (reads uninitialised memory, omits alpha), so it has no valid oracle")
-    _check_extras('adi_step' if active is None else 'adi_step_masked', grid, phase, history)
+    _check_extras('adi_step' if active is None else 'adi_step_masked', grid, phase, history, monitor)
     src = S if isinstance(S, CylGoldakSource) else None
     if src is not None and t is None:
         raise ValueError("t (the step's start time) is required when S is a CylGoldakSource")
@@ -232,12 +238,12 @@ def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None, p
         blk = _source_block(grid)
         src.set_block(blk, t, prm.dt)
         check(lib.adi_cyl_step_src(pl.handle, _p(blk), _p(x), _p(out), _p(d_act), float(T_void), float(T_inner), _stream()))
-        _extras(x, out, prm, zbc, d_act, phase, history)
+        _extras(x, out, prm, zbc, d_act, phase, history, monitor)
         return _wrap(out, kind)
     d_S = None if S is None else grid.layout.to_layout(S, torch.float64)
     check(lib.adi_cyl_step(pl.handle, _p(x), _p(out), None, None, _p(d_S), _p(d_act),
                            float(T_void), float(T_inner), _stream()))
-    _extras(x, out, prm, zbc, d_act, phase, history)
+    _extras(x, out, prm, zbc, d_act, phase, history, monitor)
     return _wrap(out, kind)
 
 
@@ -249,20 +255,22 @@ class StagedCylStepper:
     whose step counter the z sweep advances; None issues the launches of a plain step.
     phase (a CylPhaseField of this grid): the latent-heat pass follows the z sweep, the planes a 'dirichlet' closure pins left
     alone.  history (a CylThermalHistory of this grid): the record of every step follows that, at the recorder's own clock; the
-    record needs the step's input, so `run` then steps between two persistent fields instead of in place."""
+    record needs the step's input, so `run` then steps between two persistent fields instead of in place.  monitor (a
+    CylFieldMonitor of this grid): its row of every step is the step's last launch, from the step's final field over every
+    cell; it reads only the result, so it leaves `run` in place.  None: the launches, results and graph key of before."""
     stage_names = ['sweep_r', 'sweep_phi', 'sweep_z_contig']
     stage_bytes_per_cell = [16.0, 16.0, 16.0]          # SURVEY.md 8(d): field in + field out per sweep
 
-    def __init__(self, grid, mat, prm, robin_r, zbc, source=None, phase=None, history=None):
+    def __init__(self, grid, mat, prm, robin_r, zbc, source=None, phase=None, history=None, monitor=None):
         if prm.scheme == "douglas":
             raise NotImplementedError("scheme='douglas' has no valid oracle (see adi_step)")
         if source is not None and not isinstance(source, CylGoldakSource):
             raise TypeError("StagedCylStepper: source must be a CylGoldakSource (pass a source field to adi_step)")
-        _check_extras('StagedCylStepper', grid, phase, history)
+        _check_extras('StagedCylStepper', grid, phase, history, monitor)
         self.grid = grid
         self.dt = float(prm.dt)
         self.plan = _plan(grid, mat, prm.dt, robin_r, zbc)
-        self.phase, self.history = phase, history
+        self.phase, self.history, self.monitor = phase, history, monitor
         self._skips = _zbc_skips(zbc)
         self.source = source
         self.captures = 0
@@ -296,6 +304,8 @@ class StagedCylStepper:
             self.phase.apply(out, T_in=x, skip_k0=self._skips[0], skip_kN=self._skips[1])
         if self.history is not None:
             self.history._record_step(x, out, self.dt, captured)
+        if self.monitor is not None:
+            self.monitor._record_step(x, out, self.dt, captured)
 
     def _sweeps(self, x, out, events):
         """the launches of one step: the r sweep x -> out, then the phi and z sweeps in place on out (out may be x)"""
@@ -314,6 +324,8 @@ class StagedCylStepper:
         self._sweeps(x, x, events)
         if self.phase is not None:                     # (nothing to seed from: `run` seeds the newborn cells before the loop)
             self.phase.apply(x, skip_k0=self._skips[0], skip_kN=self._skips[1])
+        if self.monitor is not None:                   # (the row and the tick alone: `run` keeps the monitor's clock)
+            self.monitor._record_step(None, x, self.dt, captured=True)
 
     def run(self, T, nsteps, graph=True, t0=0.0):
         """`nsteps` BE steps with the same plan on a device-resident field (the drivers' inner loops,
@@ -332,6 +344,8 @@ class StagedCylStepper:
         key = (None if self.source is None else self.source.shape_key(),
                None if self.phase is None else self.phase.graph_key(),
                None if self.history is None else self.history.graph_key())
+        if self.monitor is not None:
+            key += (self.monitor.graph_key(),)
         if st is None or st.get('key') != key:
             st = self._graph = dict(X=g.layout.empty(), Y=None if self.history is None else g.layout.empty(), g=None, key=key)
         X = st['X']
@@ -353,12 +367,14 @@ class StagedCylStepper:
                 if bool(newborn.any().item()):
                     self.phase.seed(X, sel=newborn)
                 self._nan_free_at = self.phase._edits
+        mon = self.monitor
         if graph and nsteps >= 2 and st['g'] is None:
-            held = None if self.phase is None else self.phase.snapshot()
+            stateful = [s for s in (self.phase, mon) if s is not None]
+            held = [s.snapshot() for s in stateful]        # (the warm-up step would advance f, the monitor's log and block)
             self._step_inplace(X)                          # warm-up outside the capture (lazy module loads)
             X.copy_(g.layout.to_layout(T, torch.float64))
-            if held is not None:
-                self.phase.restore(held)
+            for s, snap in zip(stateful, held):
+                s.restore(snap)
             torch.cuda.synchronize()
             cg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(cg):
@@ -367,11 +383,15 @@ class StagedCylStepper:
             self.captures += 1
             if self.source is not None:
                 self.source.set_block(_source_block(self), t0, self.dt)   # (after the warm-up: the counter starts at 0)
+        if mon is not None:
+            mon.set_clock(self.dt)
         for _ in range(nsteps):
             if graph and st['g'] is not None:
                 st['g'].replay()
             else:
                 self._step_inplace(X)
+        if mon is not None:
+            mon.advance_clock(mon.t, self.dt, nsteps)
         out = g.layout.empty()
         out.copy_(X)
         return DeviceField(out)
@@ -383,7 +403,8 @@ class StagedCylStepper:
         field, and the bits of step() called nsteps times.  The recorder's block is set from the recorder's own clock."""
         g, hist = self.grid, self.history
         X, Y = st['X'], st['Y']
-        stateful = [s for s in (self.phase, hist) if s is not None]
+        mon = self.monitor
+        stateful = [s for s in (self.phase, hist, mon) if s is not None]
         if graph and nsteps >= 2 and st['g'] is None:
             held = [s.snapshot() for s in stateful]        # (the warm-up steps would advance f, the state, the log and the clock)
             hist.set_clock(self.dt)
@@ -401,6 +422,8 @@ class StagedCylStepper:
             if self.source is not None:
                 self.source.set_block(_source_block(self), t0, self.dt)   # (after the warm-up: the counter starts at 0)
         hist.set_clock(self.dt)
+        if mon is not None:
+            mon.set_clock(self.dt)
         done = 0
         if graph and st['g'] is not None:
             for _ in range(nsteps // 2):
@@ -411,30 +434,34 @@ class StagedCylStepper:
             self._step_into(cur, oth)
             cur, oth = oth, cur
         hist.advance_clock(hist.t, self.dt, nsteps)
+        if mon is not None:
+            mon.advance_clock(mon.t, self.dt, nsteps)
         out = g.layout.empty()
         out.copy_(cur)
         return DeviceField(out)
 
 
-def adi_step(Tn, grid, mat, prm, robin_r, zbc, S=None, theta=None, t=None, phase=None, history=None):
+def adi_step(Tn, grid, mat, prm, robin_r, zbc, S=None, theta=None, t=None, phase=None, history=None, monitor=None):
     """adi3d_cyl_phi_v3.py:332-350 (BE branch: r -> phi -> z with theta = 1; `theta` is unused there too).
     S: a source field [W/m^3] of the grid's shape (the reference's argument), or a CylGoldakSource evaluated at t + dt/2 in
     the r sweep's load -- then `t`, the step's start time, is required.
     phase (a CylPhaseField of this grid): after the sweeps the latent-heat correction of the result, the planes a 'dirichlet'
     closure of `zbc` pins left alone.  history (a CylThermalHistory of this grid): then the record of the step Tn -> result at
-    the recorder's own clock.  Both None: the launches and the bits of the call without them."""
-    return _run(Tn, grid, mat, prm, robin_r, zbc, S, None, 0.0, 0.0, t, phase, history)
+    the recorder's own clock.  monitor (a CylFieldMonitor of this grid): last, its row from the result.  All None: the launches
+    and the bits of the call without them."""
+    return _run(Tn, grid, mat, prm, robin_r, zbc, S, None, 0.0, 0.0, t, phase, history, monitor)
 
 
 def adi_step_masked(Tn, grid, mat, prm, robin_outer, zbc, active, robin_inner=None, robin_void=None, S=None, t=None,
-                    phase=None, history=None):
+                    phase=None, history=None, monitor=None):
     """quick_spiral_deposition_gif_v5.py:31-70: void cells clamped to robin_void.T_inf before and after
     the step, inactive axis-row cells to robin_inner.T_inf; the clamps are fused into the r-sweep load
     and the z-sweep store.
     S: a CylGoldakSource (q(t + dt/2) added on active cells only; `t` required), or a source field added to the clamped
     field as adi_step(T_work, S=S) adds it.
     phase, history: as in adi_step, on the active cells; a cell that `active` holds for the first time is seeded from Tn (which
-    equals the clamped field on every active cell), so an activation needs no call."""
+    equals the clamped field on every active cell), so an activation needs no call.  monitor: as in adi_step, over the active
+    cells."""
     robin_inner = robin_inner or robin_outer
     robin_void = robin_void or robin_outer
-    return _run(Tn, grid, mat, prm, robin_outer, zbc, S, active, robin_void.T_inf, robin_inner.T_inf, t, phase, history)
+    return _run(Tn, grid, mat, prm, robin_outer, zbc, S, active, robin_void.T_inf, robin_inner.T_inf, t, phase, history, monitor)

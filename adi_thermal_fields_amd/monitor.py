@@ -32,7 +32,7 @@ class FieldMonitor(_StepRecorder):
         traces()                  t and T[probe, step]
         region_log(mat=None)      t, cells, T_min, T_max, T_mean, sum_T, heat, sum_extra (arrays [region, step]) and dropped
     `record_reference` is the definition, adi_monitor_record the same operations on the device.
-    Not covered: the cylindrical step, SlabStepper and the adi_ctx_* API; probes between cell centres; where the extremum lies;
+    Not covered: SlabStepper and the adi_ctx_* API (the cylindrical step has CylFieldMonitor, cyl_monitor.py); probes between cell centres; where the extremum lies;
     regions given by a label field; control loops that read the log."""
 
     LOG_GUARD = 8        # 8-byte words either side of the log that no launch may touch (tests read them)

@@ -572,7 +572,7 @@ def ring_source(heat_source, R_in, wall, z_top, tau):
 
 
 def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_side, h_end, z_back, layer_h, n_layers, tau,
-                          nr, nphi, heat_source=None, device_resident=True, phase_change=None, history=None):
+                          nr, nphi, heat_source=None, device_resident=True, phase_change=None, history=None, monitor=None):
     """The ring-by-ring deposition loop of quick_spiral_deposition_gif_v5.py on an annular wall (R_in, R_in + wall): one
     z-cell per layer, nphi cells per turn, dt = tau / nphi, BE.  Before each step the arc swept during it is activated at Tdep
     in whole radial columns, then adi_step_masked advances the field (Robin h_side on the outer wall, neumann0 below, Robin
@@ -584,7 +584,10 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
     phase_change (a PhaseChange) / history (HistoryLevels): latent heat and the thermal history, device loop only.  One
     CylPhaseField / CylThermalHistory of the backend lives through the run (the log holds one row per step) and goes to every
     adi_step_masked; a newborn column is seeded by the step that first sees it active, so an activation needs no call.  Then
-    the liquid fraction (NumPy, 0 where never active) and / or history_result's dict follow the three usual values."""
+    the liquid fraction (NumPy, 0 where never active) and / or history_result's dict follow the three usual values.
+    monitor (dict(probes=, regions=, extra_f=False)): a CylFieldMonitor of the backend, device loop only, one through the run
+    on the global time with one row per step; extra_f=True needs phase_change and sums the phase field's f as `extra`.  Its
+    traces() and region_log(mat) follow the values above."""
     dr = wall / nr
     nz = int(round((z_back + layer_h * n_layers) / layer_h))
     grid = backend.GridCyl(nr, nphi, nz, dr, 2.0 * math.pi / nphi, layer_h, R_in + wall, R_in=R_in)
@@ -596,19 +599,27 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
     active = np.zeros((nr, nphi, nz), bool)
     active[:, :, :iz0] = True
     dev = device_resident and _is_device_backend(backend)
-    _require_device_loop('run_spiral_deposition', backend, dev, classes=dict(phase_change='CylPhaseField', history='CylThermalHistory'),
-                         phase_change=phase_change, history=history)
-    ph = hist = None
+    _require_device_loop('run_spiral_deposition', backend, dev,
+                         classes=dict(phase_change='CylPhaseField', history='CylThermalHistory', monitor='CylFieldMonitor'),
+                         phase_change=phase_change, history=history, monitor=monitor)
+    ph = hist = mon = None
     if phase_change is not None:
         ph = backend.CylPhaseField(grid, m, phase_change, active=active)
-    if history is not None:
+    if history is not None or monitor is not None:
         rows, tt = 0, 0.0
         for t_goal in times:                      # the steps of the loop below, counted with its own arithmetic
             while tt < t_goal - 1e-12:
                 tt = min(tt + tau / nphi, t_goal)
                 rows += 1
+    if history is not None:
         hist = backend.CylThermalHistory(grid, history, capacity=max(1, rows), T=T, t=0.0, active=active)
-    extras = {k: v for k, v in (('phase', ph), ('history', hist)) if v is not None}
+    if monitor is not None:
+        extra_f = bool(monitor.get('extra_f', False))
+        if extra_f and ph is None:
+            raise ValueError("run_spiral_deposition: monitor extra_f=True needs phase_change")
+        mon = backend.CylFieldMonitor(grid, probes=monitor.get('probes', ()), regions=monitor.get('regions', ()),
+                                      capacity=max(1, rows), extra=ph.f if extra_f else None, t=0.0)
+    extras = {k: v for k, v in (('phase', ph), ('history', hist), ('monitor', mon)) if v is not None}
     if dev:                                       # T and the mask in HBM: an activation is two slice assignments
         import torch
         T = grid.layout.to_layout(T, torch.float64)           # (a native-layout tensor in, a tensor out of every step)
@@ -663,6 +674,8 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
         more += (np.asarray(ph.liquid_fraction),)
     if hist is not None:
         more += (history_result(hist),)
+    if mon is not None:
+        more += (mon.traces(), mon.region_log(m))
     return (grid, fields, masks) + more
 
 

@@ -1286,6 +1286,58 @@ int adi_cyl_history_seed(const double *d_T, double *d_peak, double *d_t_hi, doub
 int adi_cyl_history_reset_log(void *d_block, int32_t *d_log, long capacity, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Field monitor of the cylindrical step (no counterpart in the reference): one row of a device log per recorded step, taken
+ * from the step's final field T, in the conventions of the cylindrical backend -- fields in the (nr, nphi, nz) layout, cell
+ * (i, j, k) at i*plane_stride + j*nz + k (plane_stride 0: nphi*nz), d_active an optional byte per cell (NULL: every cell is
+ * active), no flags, no bricks, no per-cell state: a birth needs no call.
+ *   probes   nprobe <= ADI_MONITOR_MAX_PROBES cells (i, j, k): T at the cell, NaN where the cell is not active.
+ *   regions  1 <= nreg <= ADI_MONITOR_MAX_REGIONS half-open index boxes { i0, i1, j0, j1, k0, k1 } (h_regions: 6 ints each),
+ *            non-empty, inside the grid along r and z; phi is periodic: 0 <= j0 < nphi, j0 < j1 <= j0 + nphi, the box holds the
+ *            cells j mod nphi.  They may overlap.  Per region, over its active cells, ADI_CYL_MONITOR_REGION_WORDS words:
+ *            { cells (int64), sum_i (int64: the sum of the radial index), T_min, T_max (NaN when cells == 0), sum_T, sum_rT,
+ *              sum_extra, sum_rextra } -- r_i = r_in + (i + 1/2) dr, so dr dphi dz sum_rT is the volume integral of T; the last
+ *            two from d_extra, a second field summed like T with a NaN on an included cell as +0.0; both +0.0 without it.
+ *   row      nprobe + ADI_CYL_MONITOR_REGION_WORDS * nreg 8-byte words: the probes, then the regions.  The log is
+ *            (capacity + 1) rows; a step writes row min(slot, capacity) of the block (the thermal history's,
+ *            ADI_HISTORY_BLOCK_BYTES, adi_history_set_clock / adi_history_tick; read through the pointer).
+ * The order of every sum is fixed by the grid's shape, (r_in, dr) and the region's box alone -- not by pointer alignment, the
+ * width of the loads, the launch box or the scheduling of workgroups.  An excluded cell (inactive, outside the region, the
+ * missing partner of an odd nz) contributes +0.0.
+ *   plane of radius i: per_line = ceil(nz / 2); pair q = j*per_line + p holds the cells (j, 2p), (j, 2p + 1): pair = v0 + v1.
+ *     Chunk c holds the pairs 256c .. 256c + 255, one per thread (+0.0 past the last pair); the 64 lanes of a wave by
+ *     xor-butterfly v = v + v[lane ^ o], o = 1, 2, 4, 8, 16, 32; the four waves ((w0 + w1) + w2) + w3: partial[i][c].  Over
+ *     the nchunk = ceil(nphi*per_line / 256) partials: thread t of 256, acc = +0.0; acc = acc + partial[i][n] for
+ *     n = t, t + 256, ...; the same butterfly and wave order: S_i.  A chunk that holds no cell of the region has partial +0.0
+ *     and may be skipped: acc is never -0.0.
+ *   region: sum_T: acc = +0.0; acc = acc + S_i for i = i0 .. i1 - 1.  sum_rT: p = r_i * S_i first (one operation), then
+ *     acc = acc + p; r_i = r_in + ((i + 1/2) * dr).  No contraction.  sum_extra and sum_rextra likewise.
+ * Rounding operations from a cell to the logged sum: d = 19 + ceil(nchunk / 256) + (i1 - i0), one more for the r-weighted
+ * sums.  No floating-point atomics.  T_min / T_max are the extrema in the total order of the finite doubles in which
+ * -0.0 < +0.0; NaN must not occur on active cells.
+ * d_partial: ADI_CYL_MONITOR_PARTIAL_WORDS 8-byte words per (region, radius, chunk) and per (region, radius):
+ * partial_words >= ADI_CYL_MONITOR_PARTIAL_WORDS * sum over the regions of (i1 - i0) * (nchunk + 1).  d_probes: the device
+ * copy of h_probes (3 ints per probe).
+ * adi_cyl_monitor_record_host is the same code over HOST arrays (block, T, extra, active, log) and returns the same bits; it
+ * makes no HIP call, needs no partial buffer and does not tick.  It touches (nr - 1)*plane_stride + nphi*nz elements of a
+ * field, ADI_HISTORY_BLOCK_BYTES of the block and one row of the (capacity + 1) rows of the log.
+ * Valid: non-null block, T, partial, log (d_active and d_extra may be null; probes null only with nprobe == 0), regions and
+ * probes as above, capacity >= 1, finite r_in >= 0 and dr > 0, nr <= 65535, nphi*nz < 2^31, neither the log nor the partials
+ * aliasing T or the extra field.  Everything else is ADI_ERR_ARG, checked before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADI_CYL_MONITOR_REGION_WORDS 8
+#define ADI_CYL_MONITOR_PARTIAL_WORDS 5
+/* the three kernels for the field d_T into row min(slot, capacity) of d_log; the caller ticks the block */
+int adi_cyl_monitor_record(const void *d_block, const double *d_T, const double *d_extra, const uint8_t *d_active, int nr,
+                           int nphi, int nz, long plane_stride, double r_in, double dr, int nreg, const int *h_regions,
+                           int nprobe, const int *h_probes, const int *d_probes, double *d_partial, long partial_words,
+                           double *d_log, long capacity, void *stream);
+int adi_cyl_monitor_record_host(const void *h_block, const double *h_T, const double *h_extra, const uint8_t *h_active, int nr,
+                                int nphi, int nz, long plane_stride, double r_in, double dr, int nreg, const int *h_regions,
+                                int nprobe, const int *h_probes, double *h_log, long capacity);
+/* every word of the capacity + 1 rows of d_log NaN; the block: slot = 0, n = 0, `capacity`; t0 and dt stay */
+int adi_cyl_monitor_reset_log(void *d_block, double *d_log, long capacity, long row_words, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Context API: the library owns the device memory; callers hand over HOST arrays.
  * One context per GPU and thread; no hidden global state.
  * ---------------------------------------------------------------------------------------------- */
