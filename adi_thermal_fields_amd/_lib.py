@@ -235,6 +235,13 @@ SIGNATURES = {
     'adi_cyl_monitor_record_host': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double,
                                             c_double, c_int, c_int_p, c_int, c_int_p, c_void_p, c_long]),
     'adi_cyl_monitor_reset_log': (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p]),
+    'adi_cyl_solid_record': (c_int, [c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    'adi_cyl_solid_record_host': (c_int, [c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_long]),
+    'adi_cyl_solid_hot_seed': (c_int, [c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p]),
+    'adi_cyl_solid_hot_seed_host': (c_int, [c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long]),
     'adi_matmap_build_coeffs': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_double, c_int, c_double_p,
                                         c_int_p, c_double_p, c_void_pp, c_int_p, c_double_p, c_void_pp, c_void_pp, c_void_pp,
                                         c_void_p]),
@@ -289,6 +296,7 @@ MATMAP_MAX = 8               # ADI_MATMAP_MAX: materials per grid
 HISTORY_BLOCK_BYTES = 40     # ADI_HISTORY_BLOCK_BYTES: { double t0, dt; int64 n, slot, capacity }
 HISTORY_LOG_INTS = 8         # ADI_HISTORY_LOG_INTS: { cells, lo[3], hi[3], pad }
 CYL_HISTORY_LOG_INTS = 12    # ADI_CYL_HISTORY_LOG_INTS: { cells, lo[3], hi[3], pad, int64 sum_i, pad, pad }
+CYL_SOLID_TILE = 512         # ADI_CYL_SOLID_TILE: cells of a (phi, z) plane per hot word of the cylindrical solidification record
 MONITOR_MAX_REGIONS = 8      # ADI_MONITOR_MAX_REGIONS
 MONITOR_MAX_PROBES = 256     # ADI_MONITOR_MAX_PROBES
 MONITOR_REGION_WORDS = 6     # ADI_MONITOR_REGION_WORDS: { cells, T_min, T_max, sum_T, sum_wT, sum_extra }

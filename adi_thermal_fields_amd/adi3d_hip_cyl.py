@@ -21,9 +21,10 @@ from .phase import PhaseChange
 from .history import HistoryLevels
 from .cyl_extras import CylPhaseField, CylThermalHistory
 from .cyl_monitor import CylFieldMonitor
+from .cyl_solid import CylSolidificationRecord
 
 __all__ = ['StagedCylStepper', 'CylGoldakSource', 'GridCyl', 'Material', 'Params', 'RobinR', 'ZBC', 'adi_step', 'adi_step_masked', 'DeviceField', 'to_device',
-           'CylPhaseField', 'CylThermalHistory', 'PhaseChange', 'HistoryLevels', 'CylFieldMonitor']
+           'CylPhaseField', 'CylThermalHistory', 'PhaseChange', 'HistoryLevels', 'CylFieldMonitor', 'CylSolidificationRecord']
 
 
 class GridCyl:  # adi3d_cyl_phi_v3.py:33-43
@@ -190,7 +191,7 @@ def _plan(grid, mat, dt, robin_r, zbc):
     return pl
 
 
-def _check_extras(who, grid, phase, history, monitor=None):
+def _check_extras(who, grid, phase, history, monitor=None, solidification=None):
     """TypeError for an object of the wrong type, ValueError for one built for another grid: before the first launch"""
     if phase is not None and not isinstance(phase, CylPhaseField):
         raise TypeError("%s: phase must be a CylPhaseField" % who)
@@ -198,7 +199,9 @@ def _check_extras(who, grid, phase, history, monitor=None):
         raise TypeError("%s: history must be a CylThermalHistory" % who)
     if monitor is not None and not isinstance(monitor, CylFieldMonitor):
         raise TypeError("%s: monitor must be a CylFieldMonitor" % who)
-    for name, obj in (('phase', phase), ('history', history), ('monitor', monitor)):
+    if solidification is not None and not isinstance(solidification, CylSolidificationRecord):
+        raise TypeError("%s: solidification must be a CylSolidificationRecord" % who)
+    for name, obj in (('phase', phase), ('history', history), ('monitor', monitor), ('solidification', solidification)):
         if obj is not None and obj.grid is not grid:
             raise ValueError("%s: %s was built for another grid" % (who, name))
 
@@ -208,25 +211,28 @@ def _zbc_skips(zbc):
     return zbc.kind_bot == 'dirichlet', zbc.kind_top == 'dirichlet'
 
 
-def _extras(x, out, prm, zbc, d_act, phase, history, monitor=None):
-    """what follows the sweeps of a plain step x -> out: the latent-heat pass on out, the record of (x, out), then the monitor's
-    row from out"""
+def _extras(x, out, prm, zbc, d_act, phase, history, monitor=None, solidification=None):
+    """what follows the sweeps of a plain step x -> out: the latent-heat pass on out, the history's record of (x, out), the
+    solidification record of (x, out), then the monitor's row from out"""
     if phase is not None:
         skip_k0, skip_kN = _zbc_skips(zbc)
         phase.apply(out, T_in=x, active=d_act, skip_k0=skip_k0, skip_kN=skip_kN)
     if history is not None:
         history._record_step(x, out, prm.dt, captured=False, d_act=d_act)
+    if solidification is not None:                     # (no hot words: a caller of the plain step may activate cells)
+        solidification._record_step(x, out, prm.dt, captured=False, d_act=d_act)
     if monitor is not None:
         monitor._record_step(x, out, prm.dt, captured=False, d_act=d_act)
 
 
-def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None, phase=None, history=None, monitor=None):
+def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None, phase=None, history=None, monitor=None,
+         solidification=None):
     # adi3d_cyl_phi_v3.py:335: `scheme = prm.scheme if prm.scheme in ('be', 'douglas') else 'be'` -- every string but
     # 'douglas' is backward Euler in the reference, and so it is here
     if prm.scheme == "douglas":
         raise NotImplementedError("adi3d_hip_cyl does not serve scheme='douglas': the reference's branch is numerically "
                                   "broken (reads uninitialised memory, omits alpha), so it has no valid oracle")
-    _check_extras('adi_step' if active is None else 'adi_step_masked', grid, phase, history, monitor)
+    _check_extras('adi_step' if active is None else 'adi_step_masked', grid, phase, history, monitor, solidification)
     src = S if isinstance(S, CylGoldakSource) else None
     if src is not None and t is None:
         raise ValueError("t (the step's start time) is required when S is a CylGoldakSource")
@@ -238,12 +244,12 @@ def _run(Tn, grid, mat, prm, robin_r, zbc, S, active, T_void, T_inner, t=None, p
         blk = _source_block(grid)
         src.set_block(blk, t, prm.dt)
         check(lib.adi_cyl_step_src(pl.handle, _p(blk), _p(x), _p(out), _p(d_act), float(T_void), float(T_inner), _stream()))
-        _extras(x, out, prm, zbc, d_act, phase, history, monitor)
+        _extras(x, out, prm, zbc, d_act, phase, history, monitor, solidification)
         return _wrap(out, kind)
     d_S = None if S is None else grid.layout.to_layout(S, torch.float64)
     check(lib.adi_cyl_step(pl.handle, _p(x), _p(out), None, None, _p(d_S), _p(d_act),
                            float(T_void), float(T_inner), _stream()))
-    _extras(x, out, prm, zbc, d_act, phase, history, monitor)
+    _extras(x, out, prm, zbc, d_act, phase, history, monitor, solidification)
     return _wrap(out, kind)
 
 
@@ -257,20 +263,24 @@ class StagedCylStepper:
     alone.  history (a CylThermalHistory of this grid): the record of every step follows that, at the recorder's own clock; the
     record needs the step's input, so `run` then steps between two persistent fields instead of in place.  monitor (a
     CylFieldMonitor of this grid): its row of every step is the step's last launch, from the step's final field over every
-    cell; it reads only the result, so it leaves `run` in place.  None: the launches, results and graph key of before."""
+    cell; it reads only the result, so it leaves `run` in place.  solidification (a CylSolidificationRecord of this grid): its
+    record of every step follows the history's and needs the step's input as well, so `run` takes the two-field loop with it
+    too; inside `run` -- no births, every input the previous result -- it is passed the hot words, which `run` seeds from its
+    input.  None: the launches, results and graph key of before."""
     stage_names = ['sweep_r', 'sweep_phi', 'sweep_z_contig']
     stage_bytes_per_cell = [16.0, 16.0, 16.0]          # SURVEY.md 8(d): field in + field out per sweep
 
-    def __init__(self, grid, mat, prm, robin_r, zbc, source=None, phase=None, history=None, monitor=None):
+    def __init__(self, grid, mat, prm, robin_r, zbc, source=None, phase=None, history=None, monitor=None, solidification=None):
         if prm.scheme == "douglas":
             raise NotImplementedError("scheme='douglas' has no valid oracle (see adi_step)")
         if source is not None and not isinstance(source, CylGoldakSource):
             raise TypeError("StagedCylStepper: source must be a CylGoldakSource (pass a source field to adi_step)")
-        _check_extras('StagedCylStepper', grid, phase, history, monitor)
+        _check_extras('StagedCylStepper', grid, phase, history, monitor, solidification)
         self.grid = grid
         self.dt = float(prm.dt)
         self.plan = _plan(grid, mat, prm.dt, robin_r, zbc)
         self.phase, self.history, self.monitor = phase, history, monitor
+        self.solidification = solidification
         self._skips = _zbc_skips(zbc)
         self.source = source
         self.captures = 0
@@ -298,12 +308,15 @@ class StagedCylStepper:
 
     def _step_into(self, x, out, events=None, captured=True):
         """the launches of one step x -> out (two fields): the sweeps, the latent-heat pass on out with newborn cells seeded
-        from x, the record of (x, out) and the tick.  captured: a graph may replay them and `run` keeps the recorder's clock"""
+        from x, the records of (x, out) and their ticks.  captured: a graph may replay them and `run` keeps the recorders'
+        clocks -- and the solidification record takes the hot words `run` has seeded"""
         self._sweeps(x, out, events)
         if self.phase is not None:
             self.phase.apply(out, T_in=x, skip_k0=self._skips[0], skip_kN=self._skips[1])
         if self.history is not None:
             self.history._record_step(x, out, self.dt, captured)
+        if self.solidification is not None:
+            self.solidification._record_step(x, out, self.dt, captured, hot=captured)
         if self.monitor is not None:
             self.monitor._record_step(x, out, self.dt, captured)
 
@@ -336,8 +349,8 @@ class StagedCylStepper:
         times.  graph=False: plain launches.
         t0: time at the start of the first step (a source's step i runs at t0 + i*dt + dt/2).  The source's block is written
         here, so its parameters as they are now hold for this run; a change of its support's shape recaptures.
-        With a `phase` its launch follows the z sweep, in place as well.  With a `history` the step's input must survive the
-        step: see _run_recorded."""
+        With a `phase` its launch follows the z sweep, in place as well.  With a `history` or a `solidification` the step's
+        input must survive the step: see _run_recorded."""
         g = self.grid
         nsteps = int(nsteps)
         st = getattr(self, '_graph', None)
@@ -346,13 +359,16 @@ class StagedCylStepper:
                None if self.history is None else self.history.graph_key())
         if self.monitor is not None:
             key += (self.monitor.graph_key(),)
+        if self.solidification is not None:
+            key += (self.solidification.graph_key(),)
+        recorded = self.history is not None or self.solidification is not None
         if st is None or st.get('key') != key:
-            st = self._graph = dict(X=g.layout.empty(), Y=None if self.history is None else g.layout.empty(), g=None, key=key)
+            st = self._graph = dict(X=g.layout.empty(), Y=g.layout.empty() if recorded else None, g=None, key=key)
         X = st['X']
         X.copy_(g.layout.to_layout(T, torch.float64))
         if self.source is not None:
             self.source.set_block(_source_block(self), t0, self.dt)
-        if self.history is not None:
+        if recorded:
             return self._run_recorded(st, T, nsteps, graph, t0)
         if self.phase is not None:
             # the loop steps in place and so has no input to seed a newborn cell from: every cell the phase field has never
@@ -397,17 +413,19 @@ class StagedCylStepper:
         return DeviceField(out)
 
     def _run_recorded(self, st, T, nsteps, graph, t0):
-        """`run` with a history: the record needs the step's input, so the loop keeps two persistent fields -- r sweep X -> Y,
-        phi and z in place on Y, the latent-heat pass on Y, the record of (X, Y) and the tick, then the roles swap.  The launches
-        of two steps (X -> Y -> X) are captured once and replayed, an odd last step is launched plainly: no per-step copy of the
-        field, and the bits of step() called nsteps times.  The recorder's block is set from the recorder's own clock."""
-        g, hist = self.grid, self.history
+        """`run` with a history or a solidification record: a record needs the step's input, so the loop keeps two persistent
+        fields -- r sweep X -> Y, phi and z in place on Y, the latent-heat pass on Y, the records of (X, Y) and their ticks, then
+        the roles swap.  The launches of two steps (X -> Y -> X) are captured once and replayed, an odd last step is launched
+        plainly: no per-step copy of the field, and the bits of step() called nsteps times.  Every recorder's block is set from
+        the recorder's own clock; the solidification record's hot words are seeded from the run's input, after any warm-up."""
+        g, sol = self.grid, self.solidification
         X, Y = st['X'], st['Y']
-        mon = self.monitor
-        stateful = [s for s in (self.phase, hist, mon) if s is not None]
+        clocked = [s for s in (self.history, sol, self.monitor) if s is not None]
+        stateful = [s for s in (self.phase,) if s is not None] + clocked
         if graph and nsteps >= 2 and st['g'] is None:
             held = [s.snapshot() for s in stateful]        # (the warm-up steps would advance f, the state, the log and the clock)
-            hist.set_clock(self.dt)
+            for s in clocked:
+                s.set_clock(self.dt)
             self._step_into(X, Y); self._step_into(Y, X)   # warm-up outside the capture (lazy module loads)
             X.copy_(g.layout.to_layout(T, torch.float64))
             for s, snap in zip(stateful, held):
@@ -421,9 +439,10 @@ class StagedCylStepper:
             self.captures += 1
             if self.source is not None:
                 self.source.set_block(_source_block(self), t0, self.dt)   # (after the warm-up: the counter starts at 0)
-        hist.set_clock(self.dt)
-        if mon is not None:
-            mon.set_clock(self.dt)
+        for s in clocked:
+            s.set_clock(self.dt)
+        if sol is not None:
+            sol.seed_hot(X)
         done = 0
         if graph and st['g'] is not None:
             for _ in range(nsteps // 2):
@@ -433,35 +452,37 @@ class StagedCylStepper:
         for _ in range(nsteps - done):
             self._step_into(cur, oth)
             cur, oth = oth, cur
-        hist.advance_clock(hist.t, self.dt, nsteps)
-        if mon is not None:
-            mon.advance_clock(mon.t, self.dt, nsteps)
+        for s in clocked:
+            s.advance_clock(s.t, self.dt, nsteps)
         out = g.layout.empty()
         out.copy_(cur)
         return DeviceField(out)
 
 
-def adi_step(Tn, grid, mat, prm, robin_r, zbc, S=None, theta=None, t=None, phase=None, history=None, monitor=None):
+def adi_step(Tn, grid, mat, prm, robin_r, zbc, S=None, theta=None, t=None, phase=None, history=None, monitor=None,
+             solidification=None):
     """adi3d_cyl_phi_v3.py:332-350 (BE branch: r -> phi -> z with theta = 1; `theta` is unused there too).
     S: a source field [W/m^3] of the grid's shape (the reference's argument), or a CylGoldakSource evaluated at t + dt/2 in
     the r sweep's load -- then `t`, the step's start time, is required.
     phase (a CylPhaseField of this grid): after the sweeps the latent-heat correction of the result, the planes a 'dirichlet'
     closure of `zbc` pins left alone.  history (a CylThermalHistory of this grid): then the record of the step Tn -> result at
-    the recorder's own clock.  monitor (a CylFieldMonitor of this grid): last, its row from the result.  All None: the launches
-    and the bits of the call without them."""
-    return _run(Tn, grid, mat, prm, robin_r, zbc, S, None, 0.0, 0.0, t, phase, history, monitor)
+    the recorder's own clock.  solidification (a CylSolidificationRecord of this grid): then its record of the same step, at its
+    own clock.  monitor (a CylFieldMonitor of this grid): last, its row from the result.  All None: the launches and the bits of
+    the call without them."""
+    return _run(Tn, grid, mat, prm, robin_r, zbc, S, None, 0.0, 0.0, t, phase, history, monitor, solidification)
 
 
 def adi_step_masked(Tn, grid, mat, prm, robin_outer, zbc, active, robin_inner=None, robin_void=None, S=None, t=None,
-                    phase=None, history=None, monitor=None):
+                    phase=None, history=None, monitor=None, solidification=None):
     """quick_spiral_deposition_gif_v5.py:31-70: void cells clamped to robin_void.T_inf before and after
     the step, inactive axis-row cells to robin_inner.T_inf; the clamps are fused into the r-sweep load
     and the z-sweep store.
     S: a CylGoldakSource (q(t + dt/2) added on active cells only; `t` required), or a source field added to the clamped
     field as adi_step(T_work, S=S) adds it.
     phase, history: as in adi_step, on the active cells; a cell that `active` holds for the first time is seeded from Tn (which
-    equals the clamped field on every active cell), so an activation needs no call.  monitor: as in adi_step, over the active
-    cells."""
+    equals the clamped field on every active cell), so an activation needs no call.  solidification, monitor: as in adi_step,
+    over the active cells; the front's gradient takes a neighbour only where `active` holds it."""
     robin_inner = robin_inner or robin_outer
     robin_void = robin_void or robin_outer
-    return _run(Tn, grid, mat, prm, robin_outer, zbc, S, active, robin_void.T_inf, robin_inner.T_inf, t, phase, history, monitor)
+    return _run(Tn, grid, mat, prm, robin_outer, zbc, S, active, robin_void.T_inf, robin_inner.T_inf, t, phase, history, monitor,
+                solidification)

@@ -16,8 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libadi_hip.so')
 STAMP_SRC = 'adi_stamp.hip'
-SOURCES = ['adi_cart_api.hip', 'adi_explicit.hip', 'adi_fields.hip', 'adi_sweep_contig.hip', 'adi_sweep_contig_x.hip', 'adi_sweep_strided.hip', 'adi_sweep_strided_x.hip', 'adi_sweep_strided_y.hip', 'adi_sweep_strided_fc.hip', 'adi_sweep_strided_fx.hip', 'adi_sweep_strided_fy.hip', 'adi_sweep_strided_gc.hip', 'adi_sweep_strided_gk.hip', 'adi_condense.hip', 'adi_interface.hip', 'adi_cyl.hip', 'adi_cyl_extras.hip', 'adi_cyl_monitor.hip', 'adi_ctx.hip', 'adi_morph.hip', 'adi_source.hip', 'adi_scan.hip', 'adi_bead.hip', 'adi_surface_loss.hip', 'adi_phase.hip', 'adi_matlaw.hip', 'adi_matmap.hip', 'adi_matmap_phase.hip', 'adi_matmap_loss.hip', 'adi_matmap_transition.hip', 'adi_history.hip', 'adi_solidify.hip', 'adi_monitor.hip', 'adi_stlcorr.hip', 'adi_voxelize.hip', STAMP_SRC]
-HEADERS = ['adi_core.hpp', 'adi_common.hpp', 'adi_cart_dev.hpp', 'adi_cart_host.hpp', 'adi_cell_dev.hpp', 'adi_axis0_weights.hpp', 'adi_strided_dev.hpp', 'adi_strided_fast.hpp', 'adi_strided_general.hpp', 'adi_contig_dev.hpp', 'adi_scan_eval.hpp', 'adi_scan_check.hpp', 'adi_bead_eval.hpp', 'adi_goldak_dev.hpp', 'adi_cyl_dev.hpp', 'adi_cyl_source_dev.hpp', 'adi_cyl_plan.hpp', 'adi_cyl_extras_dev.hpp', 'adi_cyl_monitor_dev.hpp', 'adi_brick_dev.hpp', 'adi_phase_dev.hpp', 'adi_history_dev.hpp', 'adi_monitor_dev.hpp', 'adi_surface_loss_dev.hpp', 'adi_matlaw_dev.hpp', 'adi_matmap_dev.hpp', os.path.join('..', '..', 'include', 'adi_hip.h')]
+SOURCES = ['adi_cart_api.hip', 'adi_explicit.hip', 'adi_fields.hip', 'adi_sweep_contig.hip', 'adi_sweep_contig_x.hip', 'adi_sweep_strided.hip', 'adi_sweep_strided_x.hip', 'adi_sweep_strided_y.hip', 'adi_sweep_strided_fc.hip', 'adi_sweep_strided_fx.hip', 'adi_sweep_strided_fy.hip', 'adi_sweep_strided_gc.hip', 'adi_sweep_strided_gk.hip', 'adi_condense.hip', 'adi_interface.hip', 'adi_cyl.hip', 'adi_cyl_extras.hip', 'adi_cyl_monitor.hip', 'adi_cyl_solid.hip', 'adi_ctx.hip', 'adi_morph.hip', 'adi_source.hip', 'adi_scan.hip', 'adi_bead.hip', 'adi_surface_loss.hip', 'adi_phase.hip', 'adi_matlaw.hip', 'adi_matmap.hip', 'adi_matmap_phase.hip', 'adi_matmap_loss.hip', 'adi_matmap_transition.hip', 'adi_history.hip', 'adi_solidify.hip', 'adi_monitor.hip', 'adi_stlcorr.hip', 'adi_voxelize.hip', STAMP_SRC]
+HEADERS = ['adi_core.hpp', 'adi_common.hpp', 'adi_cart_dev.hpp', 'adi_cart_host.hpp', 'adi_cell_dev.hpp', 'adi_axis0_weights.hpp', 'adi_strided_dev.hpp', 'adi_strided_fast.hpp', 'adi_strided_general.hpp', 'adi_contig_dev.hpp', 'adi_scan_eval.hpp', 'adi_scan_check.hpp', 'adi_bead_eval.hpp', 'adi_goldak_dev.hpp', 'adi_cyl_dev.hpp', 'adi_cyl_source_dev.hpp', 'adi_cyl_plan.hpp', 'adi_cyl_extras_dev.hpp', 'adi_cyl_monitor_dev.hpp', 'adi_cyl_solid_dev.hpp', 'adi_brick_dev.hpp', 'adi_phase_dev.hpp', 'adi_history_dev.hpp', 'adi_monitor_dev.hpp', 'adi_surface_loss_dev.hpp', 'adi_matlaw_dev.hpp', 'adi_matmap_dev.hpp', os.path.join('..', '..', 'include', 'adi_hip.h')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-fast-math', '-Wall',
          '-Wno-unused-function']

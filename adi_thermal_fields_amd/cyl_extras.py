@@ -31,6 +31,21 @@ def _seeded_state(grid, d_act, value):
     return flat
 
 
+def _decode_log(rec):
+    """the cylindrical log of a recorder (`d_log`, `capacity`, `slot`, `_times`, `grid`) over its recorded steps: what
+    CylThermalHistory.melt_pool and CylSolidificationRecord.front return"""
+    slot = rec.slot
+    n = min(slot, rec.capacity)
+    rows = rec.d_log.cpu().numpy().reshape(rec.capacity + 1, _lib.CYL_HISTORY_LOG_INTS)[:n]
+    cells, lo, hi = rows[:, 0].copy(), rows[:, 1:4].copy(), rows[:, 4:7].copy()
+    sum_i = np.ascontiguousarray(rows[:, 8:10]).view(np.int64)[:, 0].copy()
+    g = rec.grid
+    volume = CylThermalHistory.pool_volume(g, cells, sum_i)
+    span = np.where((cells > 0)[:, None], hi.astype(np.int64) - lo.astype(np.int64) + 1, 0)
+    return dict(t=np.asarray(rec._times[:n], dtype=np.float64), cells=cells, lo=lo, hi=hi, sum_i=sum_i, volume=volume,
+                extent_r=span[:, 0] * g.dr, extent_z=span[:, 2] * g.dz, dropped=max(0, slot - rec.capacity))
+
+
 class CylPhaseField:
     """The liquid fraction of a GridCyl under a PhaseChange law, on the device: `f` (fp64, the grid's layout), NaN on a cell that
     has never been seen active, 0, 1 or in between otherwise.  T (optional): f = f_eq(T) on the cells of `active` (None: all)
@@ -268,13 +283,4 @@ class CylThermalHistory(_StepRecorder):
         in metres (0 where the pool is empty), and dropped: the steps recorded past the capacity, which the log does not hold.
         lo and hi are plain minima and maxima of the indices: a pool that straddles the seam j = nphi - 1 -> 0 shows lo_j = 0
         and hi_j = nphi - 1, so no extent along phi is reported."""
-        slot = self.slot
-        n = min(slot, self.capacity)
-        rows = self.d_log.cpu().numpy().reshape(self.capacity + 1, _lib.CYL_HISTORY_LOG_INTS)[:n]
-        cells, lo, hi = rows[:, 0].copy(), rows[:, 1:4].copy(), rows[:, 4:7].copy()
-        sum_i = np.ascontiguousarray(rows[:, 8:10]).view(np.int64)[:, 0].copy()
-        g = self.grid
-        volume = self.pool_volume(g, cells, sum_i)
-        span = np.where((cells > 0)[:, None], hi.astype(np.int64) - lo.astype(np.int64) + 1, 0)
-        return dict(t=np.asarray(self._times[:n], dtype=np.float64), cells=cells, lo=lo, hi=hi, sum_i=sum_i, volume=volume,
-                    extent_r=span[:, 0] * g.dr, extent_z=span[:, 2] * g.dz, dropped=max(0, slot - self.capacity))
+        return _decode_log(self)

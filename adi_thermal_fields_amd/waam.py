@@ -572,7 +572,8 @@ def ring_source(heat_source, R_in, wall, z_top, tau):
 
 
 def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_side, h_end, z_back, layer_h, n_layers, tau,
-                          nr, nphi, heat_source=None, device_resident=True, phase_change=None, history=None, monitor=None):
+                          nr, nphi, heat_source=None, device_resident=True, phase_change=None, history=None, monitor=None,
+                          solidification=None):
     """The ring-by-ring deposition loop of quick_spiral_deposition_gif_v5.py on an annular wall (R_in, R_in + wall): one
     z-cell per layer, nphi cells per turn, dt = tau / nphi, BE.  Before each step the arc swept during it is activated at Tdep
     in whole radial columns, then adi_step_masked advances the field (Robin h_side on the outer wall, neumann0 below, Robin
@@ -587,7 +588,11 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
     the liquid fraction (NumPy, 0 where never active) and / or history_result's dict follow the three usual values.
     monitor (dict(probes=, regions=, extra_f=False)): a CylFieldMonitor of the backend, device loop only, one through the run
     on the global time with one row per step; extra_f=True needs phase_change and sums the phase field's f as `extra`.  Its
-    traces() and region_log(mat) follow the values above."""
+    traces() and region_log(mat) follow the values above.
+    solidification (T_freeze): the conditions at the freezing front, device loop only.  One CylSolidificationRecord of the
+    backend lives through the run on the global time with one log row per step and goes to every adi_step_masked; a birth
+    needs no call.  After the liquid fraction and the history's dict, and before the monitor's two values, follows the dict of
+    solidification_result with `front`, the record's front() log, added."""
     dr = wall / nr
     nz = int(round((z_back + layer_h * n_layers) / layer_h))
     grid = backend.GridCyl(nr, nphi, nz, dr, 2.0 * math.pi / nphi, layer_h, R_in + wall, R_in=R_in)
@@ -600,12 +605,13 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
     active[:, :, :iz0] = True
     dev = device_resident and _is_device_backend(backend)
     _require_device_loop('run_spiral_deposition', backend, dev,
-                         classes=dict(phase_change='CylPhaseField', history='CylThermalHistory', monitor='CylFieldMonitor'),
-                         phase_change=phase_change, history=history, monitor=monitor)
-    ph = hist = mon = None
+                         classes=dict(phase_change='CylPhaseField', history='CylThermalHistory', monitor='CylFieldMonitor',
+                                      solidification='CylSolidificationRecord'),
+                         phase_change=phase_change, history=history, monitor=monitor, solidification=solidification)
+    ph = hist = mon = sol = None
     if phase_change is not None:
         ph = backend.CylPhaseField(grid, m, phase_change, active=active)
-    if history is not None or monitor is not None:
+    if history is not None or monitor is not None or solidification is not None:
         rows, tt = 0, 0.0
         for t_goal in times:                      # the steps of the loop below, counted with its own arithmetic
             while tt < t_goal - 1e-12:
@@ -619,7 +625,9 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
             raise ValueError("run_spiral_deposition: monitor extra_f=True needs phase_change")
         mon = backend.CylFieldMonitor(grid, probes=monitor.get('probes', ()), regions=monitor.get('regions', ()),
                                       capacity=max(1, rows), extra=ph.f if extra_f else None, t=0.0)
-    extras = {k: v for k, v in (('phase', ph), ('history', hist), ('monitor', mon)) if v is not None}
+    if solidification is not None:
+        sol = backend.CylSolidificationRecord(grid, solidification, capacity=max(1, rows), t=0.0)
+    extras = {k: v for k, v in (('phase', ph), ('history', hist), ('monitor', mon), ('solidification', sol)) if v is not None}
     if dev:                                       # T and the mask in HBM: an activation is two slice assignments
         import torch
         T = grid.layout.to_layout(T, torch.float64)           # (a native-layout tensor in, a tensor out of every step)
@@ -674,6 +682,8 @@ def run_spiral_deposition(backend, times, mat_args, Tinf, Tdep, R_in, wall, h_si
         more += (np.asarray(ph.liquid_fraction),)
     if hist is not None:
         more += (history_result(hist),)
+    if sol is not None:
+        more += (dict(solidification_result(sol), front=sol.front()),)
     if mon is not None:
         more += (mon.traces(), mon.region_log(m))
     return (grid, fields, masks) + more

@@ -1338,6 +1338,56 @@ int adi_cyl_monitor_record_host(const void *h_block, const double *h_T, const do
 int adi_cyl_monitor_reset_log(void *d_block, double *d_log, long capacity, long row_words, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Solidification record of the cylindrical step (no counterpart in the reference): the conditions at the freezing front, in
+ * the conventions of the cylindrical backend -- fields in the (nr, nphi, nz) layout, cell (i, j, k) at
+ * i*plane_stride + j*nz + k (plane_stride 0: nphi*nz), d_active an optional byte per cell (NULL: every cell is active), no
+ * flags, no bricks.  NaN in the state means "never froze", whether or not the cell was ever active: nothing is seeded and a
+ * birth needs no call.
+ *
+ * adi_cyl_solid_record, for the step A = d_T_in (at t_n) -> B = d_T_out (at t_n + dt): an active cell with A > T_freeze and
+ * B <= T_freeze freezes in the step and has its three values overwritten; every other cell is never written.
+ *     den = A - B, num = A - T_freeze, fr = num/den, off = dt*fr, t_solid = t_n + off, rate = den/dt
+ *     per axis, for F in (A, B): d/(2h) central where both neighbours are present, d/h one-sided where one is, 0 where none is;
+ *       dg = gB - gA, sg = fr*dg, g = gA + sg
+ *     g2 = (g_r*g_r + g_phi*g_phi) + g_z*g_z
+ * h = dr along r, dz along z and r_i*dphi along phi with r_i = r_in + ((i + 0.5)*dr).  The neighbours are i -+ 1 and k -+ 1
+ * inside the box (a box face counts as absent) and (j -+ 1) mod nphi: none with nphi == 1, the same cell twice with nphi == 2
+ * (a central difference of +0.0).  A neighbour is present only where d_active holds it; the values of inactive cells never
+ * enter.  Every operation IEEE fp64 in that order, no contraction.  The clock is a block of the thermal history's layout
+ * (ADI_HISTORY_BLOCK_BYTES, adi_history_set_clock, adi_history_tick), the log is the cylindrical history's
+ * (ADI_CYL_HISTORY_LOG_INTS integers per row, adi_cyl_history_reset_log): row min(slot, capacity) takes { cells, lo[3], hi[3],
+ * sum_i } over the cells that froze in the step, with integer atomics.
+ *
+ * A tile is ADI_CYL_SOLID_TILE consecutive cells p = j*nz + k of one radius' plane; d_hot (optional) holds one 32-bit word per
+ * tile, word i*ntile + q with ntile = ceil(nphi*nz / ADI_CYL_SOLID_TILE): set iff some active cell of the tile had
+ * T > T_freeze in the field of the last record (its B) or of adi_cyl_solid_hot_seed.  With d_hot a tile whose word is clear
+ * reads d_active and B only -- nothing can have frozen there -- and every tile's word is rewritten where it changes.  That is
+ * exact under the precondition that on every active cell this record's A is bitwise the previous record's B (or the seeded
+ * field) and d_active is unchanged; a birth breaks it, so a caller that activates cells passes NULL.  NULL: every tile runs
+ * the full path, with no precondition.
+ *
+ * The *_host functions are the same loops over HOST arrays with the same per-cell code; they make no HIP call.
+ * adi_cyl_solid_record_host reads the clock from h_block, accumulates into the row of h_log that block names and does not tick.
+ * Valid: no null array but d_active and d_hot, d_T_in != d_T_out, no state array aliasing a field or another state array,
+ * finite T_freeze, finite dr, dphi, dz > 0, finite r_in >= 0, block and log 8-byte aligned, nr <= 65535, nphi*nz < 2^31.
+ * Everything else is ADI_ERR_ARG, checked before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADI_CYL_SOLID_TILE 512
+int adi_cyl_solid_record(double T_freeze, double r_in, double dr, double dphi, double dz, const void *d_block,
+                         const double *d_T_in, const double *d_T_out, double *d_t_solid, double *d_rate, double *d_g2,
+                         int32_t *d_log, const uint8_t *d_active, int32_t *d_hot, int nr, int nphi, int nz, long plane_stride,
+                         void *stream);
+int adi_cyl_solid_record_host(double T_freeze, double r_in, double dr, double dphi, double dz, const void *h_block,
+                              const double *h_T_in, const double *h_T_out, double *h_t_solid, double *h_rate, double *h_g2,
+                              int32_t *h_log, const uint8_t *h_active, int32_t *h_hot, int nr, int nphi, int nz,
+                              long plane_stride);
+/* every word of d_hot from d_T: 1 where an active cell of the tile has T > T_freeze, else 0 */
+int adi_cyl_solid_hot_seed(double T_freeze, const double *d_T, const uint8_t *d_active, int32_t *d_hot, int nr, int nphi, int nz,
+                           long plane_stride, void *stream);
+int adi_cyl_solid_hot_seed_host(double T_freeze, const double *h_T, const uint8_t *h_active, int32_t *h_hot, int nr, int nphi,
+                                int nz, long plane_stride);
+
+/* ------------------------------------------------------------------------------------------------
  * Context API: the library owns the device memory; callers hand over HOST arrays.
  * One context per GPU and thread; no hidden global state.
  * ---------------------------------------------------------------------------------------------- */
